@@ -14,11 +14,16 @@ Gram all-reduces, all-gather of the finished basis block) runs INSIDE libbigsnpr
 (bsn_comm_*); this script only carries the RCCL unique id between the ranks (gloo) and times.
 
 Extra JSON objects: "roofline" (dominant streaming kernel: algorithmic bytes per launch / HIP-event
-duration measured inside the timed solves), "cpu_baseline" (the OpenMP CPU restatement of the reference
-kernels, oracle/bsn_oracle.c, on a bounded sample of the same matrix on this host; rank 0, N = 1 only)
-and "ingest" (bsn_bed_open of a real .bed file of a bounded size: host -> HBM rate, BASELINE.md §2
+duration measured inside the timed solves).  With --full (svd, rank 0, N = 1) also "cpu_baseline" (the OpenMP
+CPU restatement of the reference kernels, oracle/bsn_oracle.c, on a bounded sample of the same matrix on this
+host) and "ingest" (bsn_bed_open of a real .bed file of a bounded size: host -> HBM rate, BASELINE.md §2
 "reported separately"; never part of `value`); "cold" (the first solves of a fresh process), "accuracy" (two matrices),
-"auto_svd" (the caller of the hot path, snp_autoSVD, twice on the timed image) — all outside the timed region.
+"fp64_equivalent" (solves on wider panels), "auto_svd" (the caller of the hot path, snp_autoSVD, twice on the timed
+image) — all outside the timed region.  A plain run (no --full) sets up, warms up, times the steps and prints the line.
+
+--dump-outputs DIR (svd): after the timed steps, what the last timed solve returned to its caller — d, center, scale
+and, unless --no-uv, u and v — as DIR/<name>.npy in float64; an array of more rows than its share of the 64-MB budget
+allows is written as a fixed, seeded sample of its rows (the same rows on every run of the same arguments).
 """
 import argparse
 import json
@@ -101,7 +106,17 @@ def parse():
     ap.add_argument("--verbose", type=int, default=0, help="1: residual trajectory of every solve on stderr")
     ap.add_argument("--warm-start", type=int, default=0, help="warm-start iterations (0 = library default 1, -1 = none)")
     ap.add_argument("--warm-den", type=int, default=0, help="warm start on the leading 1/N of the variants (0 = 16)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="svd: also take the records outside the timed region (cold, accuracy, fp64_equivalent, cpu_baseline, "
+                         "auto_svd, ingest; each can still be left out with its --no-* option); a plain run only sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="svd: write what the last timed solve returned (d, center, scale, u, v) as DIR/<name>.npy (float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the rows of a larger array)")
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload != "svd":
+        ap.error("--dump-outputs: the svd workload only")
+    return a
 
 
 def host_threads():
@@ -138,6 +153,24 @@ def log(msg):
 
 
 T_START = time.time()
+
+DUMP_BYTES_PER_ARRAY = 12 << 20     # d, center, scale, u, v: at most 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64; one of more rows than its share of the budget holds is
+    cut to a sorted sample of its rows drawn by a fixed seed (the same rows for the same shape on every run)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        if x is None:
+            continue
+        x = np.asarray(x, dtype=np.float64)
+        row_bytes = 8 * max(1, x[0].size if x.ndim > 1 else 1)
+        keep = max(1, DUMP_BYTES_PER_ARRAY // row_bytes)
+        if x.ndim >= 1 and x.shape[0] > keep:
+            x = x[np.sort(np.random.default_rng(20250905).choice(x.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x))
 
 
 def cold_child(a):
@@ -310,8 +343,8 @@ def main():
             raise err
 
     cold = None
-    if (world == 1 and rank == 0 and a.workload == "svd" and not a.no_cold and a.shard_of <= 1 and a.ind_col_fraction <= 0
-            and not a.force_dist):
+    if (a.full and world == 1 and rank == 0 and a.workload == "svd" and not a.no_cold and a.shard_of <= 1
+            and a.ind_col_fraction <= 0 and not a.force_dist):
         cold = {"what": "a FRESH process: library + runtime, a new handle, then the first five bed_randomSVD(k = %d) calls on it; "
                         "the first solve runs on the variant-major image alone; the sample-major copy is made behind it, for the later ones" % a.k,
                 "synthetic_full_size": cold_record(a)}
@@ -413,6 +446,11 @@ def main():
     sync()
     wall = time.perf_counter() - t0
     log("timed solves done (%.1f ms per solve)" % (1e3 * wall / a.steps))
+    if a.dump_outputs and rank == 0:
+        last = infos[-1]
+        dump_outputs(a.dump_outputs, {"d": last["d"], "center": last["center"], "scale": last["scale"],
+                                      "u": last_uv[0], "v": last_uv[1]})
+        log("outputs of the last timed solve written to %s" % a.dump_outputs)
     per_rank = None
     if world > 1:
         # every rank's own wall time and streaming-kernel averages travel to rank 0 (gloo): the JSON names the slowest
@@ -568,7 +606,7 @@ def main():
                                for k, v in kern.items()}},
     }
 
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         ref = None
         if not a.no_accuracy and not a.no_uv and a.shard_of <= 1:
             out["accuracy"], ref = accuracy(ba, gb, a, infos[-1], last_uv)

@@ -130,12 +130,31 @@ def test_other_workloads_print_one_line():
 
 
 def test_single_gpu_line_carries_the_autosvd_record():
-    """the driver's command shape at a toy size: one line, with the objects measured outside the timed region — among them
-    `auto_svd` (round 6: snp_autoSVD twice on the timed image, stage by stage)"""
-    rec, _ = _run([sys.executable, "bench.py"] + ARGS + ["--no-cold", "--no-wide"])
+    """the driver's command shape at a toy size with --full: one line, with the objects measured outside the timed region —
+    among them `auto_svd` (round 6: snp_autoSVD twice on the timed image, stage by stage)"""
+    rec, _ = _run([sys.executable, "bench.py", "--full"] + ARGS + ["--no-cold", "--no-wide"])
     for key in ("metric", "value", "roofline", "accuracy", "auto_svd"):
         assert key in rec, key
     av = rec["auto_svd"]
     assert "error" not in av, av
     assert av["second_call_s"] > 0 and 0 < av["kept_variants"] <= av["variants"] == 60000
     assert {"snp_clumping", "big_randomSVD", "dist_ogk"} <= set(av["stages_second_call_s"])
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """without --full the line carries the timed figures only; --dump-outputs writes what the last timed solve returned,
+    in float64, and two runs of the same arguments write the same inputs' results"""
+    outs = []
+    for tag in ("a", "b"):
+        rec, _ = _run([sys.executable, "bench.py", "--gpus", "1", "--dump-outputs", str(tmp_path / tag)] + ARGS)
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in rec, key
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert not {"accuracy", "fp64_equivalent", "cpu_baseline", "auto_svd", "ingest", "cold"} & set(rec)
+        got = {name: np.load(str(tmp_path / tag / (name + ".npy"))) for name in ("d", "center", "scale", "u", "v")}
+        assert all(x.dtype == np.float64 for x in got.values())
+        assert got["d"].shape == (5,) and got["u"].shape == (20000, 5) and got["v"].shape == (60000, 5)
+        np.testing.assert_allclose(got["d"][:5], rec["sigma"], rtol=1e-12)
+        outs.append(got)
+    for name in outs[0]:
+        np.testing.assert_allclose(outs[1][name], outs[0][name], rtol=1e-9, atol=1e-12)

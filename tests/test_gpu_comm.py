@@ -46,6 +46,19 @@ def test_single_rank_communicator_is_the_identity(ba):
         comm.close()
 
 
+# The suite keeps at most six processes on one GPU at a time: this one and five ranks.  A larger world of the stand-in
+# transport runs its ranks as threads of the worker processes, two (or more) to a process.
+RANK_PROCESSES = 5
+
+
+def _processes(world, env):
+    """worker processes for `world` ranks; sets the worker's switches when a process has to hold several ranks"""
+    per = -(-world // RANK_PROCESSES)
+    if per > 1:
+        env.update(BSN_TEST_RANKS_PER_PROCESS=str(per), BSN_TEST_WORLD=str(world))
+    return -(-world // per)
+
+
 def _mock_rccl():
     sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
     import build_native
@@ -70,7 +83,7 @@ def test_ranks_over_the_collective_calls(tmp_path, ba, transport, world, n):
     with socket.socket() as sock:
         sock.bind(("127.0.0.1", 0))
         port = str(sock.getsockname()[1])
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(_processes(world, env)),
            "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(ROOT, "tests", "helpers", "rccl_svd_worker.py"), str(n), str(m), str(k), out]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -104,7 +117,7 @@ def test_product_pass_in_segments_with_overlapped_reduce_scatter(tmp_path, ba, w
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0))
             port = str(sock.getsockname()[1])
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(_processes(world, env)),
                "--master-addr", "127.0.0.1", "--master-port", port,
                os.path.join(ROOT, "tests", "helpers", "rccl_svd_worker.py"), str(n), str(m), str(k), out]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
