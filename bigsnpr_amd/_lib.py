@@ -129,6 +129,11 @@ SIGNATURES = {
                                           i64, f64p, f64p, i32p]),
     "bsn_snp_grid_prs": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, i32p, C.POINTER(C.c_uint8), i64, i64,
                                    C.c_int, f64p]),
+    "bsn_sfbm_from_csc": (C.c_int, [i64p, i32p, f64p, i64, C.c_int, C.POINTER(vp)]),
+    "bsn_sfbm_ncol": (C.c_int, [vp, i64p, i64p, i64p]),
+    "bsn_sfbm_free": (C.c_int, [vp]),
+    "bsn_lassosum2": (C.c_int, [vp, f64p, i64, f64p, f64p, f64p, i64, i64p, C.c_double, C.c_int32, C.c_double,
+                                f64p, i32p, f64p]),
     "bsn_malloc": (C.c_int, [C.POINTER(vp), i64]),
     "bsn_free": (C.c_int, [vp]),
     "bsn_host_alloc": (C.c_int, [C.POINTER(vp), i64]),

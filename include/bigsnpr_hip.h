@@ -483,6 +483,27 @@ int bsn_robust_mc_window(const double *d_up, int64_t nu, const double *d_lo, int
  * them last, as R does). */
 int bsn_order_decreasing(const double *S, int64_t m, const int64_t *group_off, int32_t ngroups, int32_t *ord, int32_t *rank);
 
+/* ---- sparse LD matrix in HBM and lassosum2 over it --------------------------------------------------------------------
+ * bigsparser's SFBM as R/lassosum2.R receives it (`corr`): full columns of a sparse symmetric LD matrix, held on the
+ * device and reused across calls.  From a CSC with p [m2 + 1] (0-based offsets), rows i [p[m2]] strictly ascending in
+ * each column, values x [p[m2]]: upper = 1 reads the upper triangle with the diagonal (the @i / @p / @x of bsn_cormat_fetch,
+ * uplo = "U") and expands it to full columns on the device; upper = 0 reads full columns (a dgCMatrix).  Bad p, rows out
+ * of range or unsorted rows are refused before any device work. */
+typedef struct bsn_sfbm bsn_sfbm;
+int bsn_sfbm_from_csc(const int64_t *p, const int32_t *i, const double *x, int64_t m2, int upper, bsn_sfbm **out);
+/* columns, stored entries of the full columns and bandwidth (max |row - column| over stored entries); any may be NULL */
+int bsn_sfbm_ncol(const bsn_sfbm *s, int64_t *m2_out, int64_t *nnz_out, int64_t *bandwidth_out);
+int bsn_sfbm_free(bsn_sfbm *s);
+/* _bigsnpr_lassosum2 (8 args) src/lassosum2.cpp:8-70, for G grid points per call instead of one.  Grid point g uses
+ * lambda_j = pf[j] * lambda[g] and delta_plus_one_j = pf[j] * delta[g] + 1 (R/lassosum2.R:59-60, formed on the device);
+ * ind_sub [m] (0-based columns of `corr`, any order, NULL: 0 .. m2 - 1 with m = m2).  beta_out [m * G] is column-major,
+ * one column per grid point in the caller's order, NaN where the reference returns NA (gap > gap0); num_iter_out [G]
+ * is the reference's k + 1; time_out [G] (may be NULL) the seconds of each grid point on the device clock.  Every
+ * result equals the sequential loop bit for bit. */
+int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const double *pf, const double *lambda,
+                  const double *delta, int64_t G, const int64_t *ind_sub, double dfmax, int32_t maxiter, double tol,
+                  double *beta_out, int32_t *num_iter_out, double *time_out);
+
 /* ---- device memory + timing helpers for hosts without a HIP binding -------- */
 int bsn_malloc(void **d_ptr, int64_t bytes);
 int bsn_free(void *d_ptr);
