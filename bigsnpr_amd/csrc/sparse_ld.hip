@@ -1,5 +1,6 @@
 // sparse_ld.hip — a sparse LD matrix resident in HBM (bigsparser's SFBM, as R/lassosum2.R receives it through
-// `corr`) and snp_lassosum2's coordinate descent over it, the whole grid of (lambda, delta) in one launch.
+// `corr`), snp_lassosum2's coordinate descent over it, the whole grid of (lambda, delta) in one launch, and the products
+// with it: sp_prodVec, ld_scores_sfbm and sp_solve_sym (MINRES), which snp_ldsc2 and snp_ldpred2_inf run on.
 //
 // The matrix.  snp_cor / bed_cor hand back the upper triangle (with the diagonal) of a symmetric dsCMatrix;
 // bigsparser::as_SFBM turns it into full columns, and SFBM::incr_mult_col(j, v, c) adds x_ij * c to v[i] over the
@@ -32,6 +33,8 @@ struct bsn_sfbm {
   bsn::DevBuf<double> x;    // [nnz]
   std::vector<int32_t> lo, hi;   // row span of each column (lo > hi: empty column)
   int64_t bandwidth = 0;         // max over columns of max(j - lo, hi - j)
+  std::vector<int64_t> hp;       // p on the host: the column lengths choose the kernel of each column (plan_columns)
+  double last_ms = 0;            // device time of the last product / LD-score / solve call (bsn_sfbm_last_ms)
 };
 
 namespace bsn {
@@ -215,6 +218,353 @@ __global__ __launch_bounds__(64) void k_lassosum2(const int64_t *__restrict__ P,
 
 #pragma clang fp contract(on)
 
+// ---- products with the resident matrix: sp_prodVec, ld_scores_sfbm, sp_solve_sym ---------------------------------------
+// Every sum below has a fixed order that depends on the shapes only (no floating-point atomics): lanes stride over a
+// column and are combined by a butterfly, threads stride over a vector and are combined per block, and the per-block
+// partial sums are added up in index order by whoever needs the total.  Two calls on the same inputs give the same bits.
+
+constexpr int kBlock = 256;             // threads per block of every kernel below (4 waves)
+constexpr int kShortLanes = 8;          // lanes that share one short column
+constexpr int64_t kShortBelow = 64;     // a column with fewer stored entries is "short": 8 lanes, 8 columns to a wave
+constexpr int kMaxColBlocks = 2048;     // blocks of a column kernel (waves stride over the columns) ...
+constexpr int kMaxVecBlocks = 1024;     // ... and of a vector kernel: as many partial sums at the most
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the sum over the block, in every thread: butterfly inside each wave, then the four wave sums in wave order
+__device__ __forceinline__ double block_sum(double v, double *lds) {
+  v = wave_sum(v);
+  __syncthreads();   // lds may still be read from the previous call
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// second stage of a reduction, done by every block that needs the total: thread t adds part[t], part[t + 256], ... in order
+__device__ __forceinline__ double total_of(const double *__restrict__ part, int n, double *lds) {
+  double a = 0;
+  for (int k = threadIdx.x; k < n; k += kBlock) a += part[k];
+  return block_sum(a, lds);
+}
+
+// recurrence of the solver, in device memory (two copies: an iteration reads one and writes the other)
+struct SolveState {
+  double beta, oldb, dbar, epsln, phibar, cs, sn;
+  int32_t itn, done, first, pad;
+};
+
+__device__ __forceinline__ bool solve_idle(const SolveState *st, int maxiter) { return st->done || st->itn >= maxiter; }
+
+// The column walk.  MODE 0: out = sum_e x_e v[i_e] (+ dg[j2] v[j2]), and the block's share of sum_j out_j v[j2] in
+// part[blockIdx.x] when part is given.  MODE 1: out = sum_e x_e^2 over the rows with mask[i_e] != 0 (all rows: mask NULL).
+// list [ncols] holds the output positions j served by this launch, ind [m] the column j2 of `corr` behind each (NULL:
+// j2 = j); the result goes to out[j2] when `scatter`, else to out[j].
+// LANES = 64: one wave per column; the lanes take the entries in aligned pairs (16-byte loads of x, 8-byte loads of i;
+// a pair that straddles the column's end is loaded whole and its outside half replaced by zero).  LANES = 8: eight
+// columns to a wave, one entry per lane and step.
+template <int MODE, int LANES>
+__global__ __launch_bounds__(kBlock, 8) void k_columns(const int64_t *__restrict__ P, const int32_t *__restrict__ I,
+                                                    const double *__restrict__ X, const int32_t *__restrict__ list,
+                                                    int64_t ncols, const int64_t *__restrict__ ind,
+                                                    const double *__restrict__ v, const double *__restrict__ dg,
+                                                    const uint8_t *__restrict__ mask, double *__restrict__ out, int scatter,
+                                                    double *__restrict__ part, const SolveState *__restrict__ st,
+                                                    int maxiter) {
+  __shared__ double lds[4];
+  if (st && solve_idle(st, maxiter)) return;
+  const int lane = threadIdx.x % LANES;
+  const int64_t group = ((int64_t)blockIdx.x * kBlock + threadIdx.x) / LANES;
+  const int64_t ngroups = (int64_t)gridDim.x * kBlock / LANES;
+  double dot = 0;
+  for (int64_t c = group; c < ncols; c += ngroups) {
+    const int64_t j = list[c];
+    const int64_t j2 = ind ? ind[j] : j;
+    const int64_t a = P[j2], b = P[j2 + 1];
+    double acc0 = 0, acc1 = 0;
+    if (LANES == 64) {
+#pragma unroll 4
+      for (int64_t e = (a & ~(int64_t)1) + 2 * lane; e < b; e += 128) {
+        const bool k0 = e >= a, k1 = e + 1 < b;
+        const double2 xv = *reinterpret_cast<const double2 *>(X + e);
+        const int2 iv = *reinterpret_cast<const int2 *>(I + e);
+        const int32_t r0 = k0 ? iv.x : 0, r1 = k1 ? iv.y : 0;
+        const double x0 = k0 ? xv.x : 0.0, x1 = k1 ? xv.y : 0.0;
+        if (MODE == 0) {
+          acc0 += x0 * v[r0];
+          acc1 += x1 * v[r1];
+        } else {
+          acc0 += (!mask || mask[r0]) ? x0 * x0 : 0.0;
+          acc1 += (!mask || mask[r1]) ? x1 * x1 : 0.0;
+        }
+      }
+    } else {
+      for (int64_t e = a + lane; e < b; e += LANES) {
+        const int32_t r = I[e];
+        const double x = X[e];
+        if (MODE == 0) acc0 += x * v[r];
+        else acc0 += (!mask || mask[r]) ? x * x : 0.0;
+      }
+    }
+    double s = acc0 + acc1;
+#pragma unroll
+    for (int o = LANES / 2; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) {
+      if (MODE == 0) {
+        const double vj = v[j2];
+        if (dg) s += dg[j2] * vj;
+        dot += s * vj;
+      }
+      out[scatter ? j2 : j] = s;
+    }
+  }
+  if (MODE == 0 && part) {
+    const double t = block_sum(dot, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+  }
+}
+
+__global__ void k_scatter(const double *__restrict__ src, const int64_t *__restrict__ ind, int64_t m, double *__restrict__ dst) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) dst[ind[j]] = src[j];
+}
+
+__global__ void k_gather(const double *__restrict__ src, const int64_t *__restrict__ ind, int64_t m, double *__restrict__ dst) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) dst[j] = src[ind[j]];
+}
+
+__global__ void k_mask(const int64_t *__restrict__ ind, int64_t m, uint8_t *__restrict__ mask) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < m) mask[ind[j]] = 1;   // a repeated index stores the same byte twice
+}
+
+// part[blockIdx.x] = this block's share of sum (a - b)^2 (b NULL: sum a^2); diff (may be NULL) receives a - b
+__global__ __launch_bounds__(kBlock) void k_sumsq(const double *__restrict__ a, const double *__restrict__ b, int64_t n,
+                                                  double *__restrict__ diff, double *__restrict__ part) {
+  __shared__ double lds[4];
+  double s = 0;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
+    const double d = b ? a[k] - b[k] : a[k];
+    if (diff) diff[k] = d;
+    s += d * d;
+  }
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// MINRES (Paige & Saunders 1975) for (A + D) x = rhs, x being ADDED to: the first Lanczos vector from rhs, whose sum of
+// squares is in part [np].  `target` is the absolute residual norm to stop at.
+__global__ __launch_bounds__(kBlock) void k_solve_start(const double *__restrict__ rhs, int64_t n, const double *__restrict__ part,
+                                                        int np, double target, const SolveState *prev, double *__restrict__ r1,
+                                                        double *__restrict__ r2, double *__restrict__ v, double *__restrict__ w1,
+                                                        double *__restrict__ w2, SolveState *st) {
+  __shared__ double lds[4];
+  const int itn0 = prev ? prev->itn : 0;   // read before anything is written: prev is one of st[0], st[1]
+  const double beta1 = sqrt(total_of(part, np, lds));
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
+    const double r = rhs[k];
+    r1[k] = r;
+    r2[k] = r;
+    v[k] = beta1 > 0 ? r / beta1 : 0.0;
+    w1[k] = 0;
+    w2[k] = 0;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    SolveState s;
+    s.beta = beta1;
+    s.oldb = 0;
+    s.dbar = 0;
+    s.epsln = 0;
+    s.phibar = beta1;
+    s.cs = -1;
+    s.sn = 0;
+    s.itn = itn0;   // a restart goes on counting
+    s.done = !(beta1 > target);
+    s.first = 1;
+    s.pad = 0;
+    st[0] = s;
+    st[1] = s;
+  }
+}
+
+// first half of an iteration, after t = (A + D) v and partA = the shares of v . t:
+//   alfa = v . t - (beta / oldb) v . r1;  y = t - (beta / oldb) r1 - (alfa / beta) r2;  r1 <- r2;  r2 <- y;  partB = shares of y . y
+// (v . r1, zero in exact arithmetic, comes from the previous iteration in partC: Paige and Saunders take alfa after the
+// first subtraction)
+__global__ __launch_bounds__(kBlock) void k_solve_lanczos(const double *__restrict__ t, double *__restrict__ r1, double *__restrict__ r2,
+                                                          int64_t n, const double *__restrict__ partA, int nA,
+                                                          const double *__restrict__ partC, int nC, const SolveState *__restrict__ st,
+                                                          int maxiter, double *__restrict__ alfa_out, double *__restrict__ partB) {
+  __shared__ double lds[4];
+  if (solve_idle(st, maxiter)) return;
+  const double beta = st->beta;
+  const double c0 = st->first ? 0.0 : beta / st->oldb;
+  double alfa = total_of(partA, nA, lds);
+  if (!st->first) alfa -= c0 * total_of(partC, nC, lds);
+  const double c1 = alfa / beta;
+  double s = 0;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
+    const double r2k = r2[k];
+    const double y = (t[k] - c0 * r1[k]) - c1 * r2k;
+    r1[k] = r2k;
+    r2[k] = y;
+    s += y * y;
+  }
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) {
+    partB[blockIdx.x] = s;
+    if (blockIdx.x == 0) *alfa_out = alfa;
+  }
+}
+
+// second half: the plane rotation, w and x, the next Lanczos vector v = r2 / beta and partC = the shares of v . r1.
+// Every block forms the same scalars from `cur`; block 0 writes them to `next`.
+__global__ __launch_bounds__(kBlock) void k_solve_update(double *__restrict__ v, const double *__restrict__ r1, const double *__restrict__ r2,
+                                                         double *__restrict__ w1, double *__restrict__ w2, double *__restrict__ x, int64_t n,
+                                                         const double *__restrict__ partB, int nB, const double *__restrict__ alfa_in,
+                                                         const SolveState *__restrict__ cur, SolveState *__restrict__ next,
+                                                         double target, int maxiter, double *__restrict__ partC) {
+  __shared__ double lds[4];
+  if (solve_idle(cur, maxiter)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *next = *cur;
+    return;
+  }
+  const double betan = sqrt(total_of(partB, nB, lds));
+  const double alfa = *alfa_in;
+  const double oldeps = cur->epsln;
+  const double delta = cur->cs * cur->dbar + cur->sn * alfa;
+  const double gbar = cur->sn * cur->dbar - cur->cs * alfa;
+  const double epsln = cur->sn * betan;
+  const double dbar = -cur->cs * betan;
+  const double gamma = fmax(sqrt(gbar * gbar + betan * betan), 2.220446049250313e-16);
+  const double cs = gbar / gamma, sn = betan / gamma;
+  const double phi = cs * cur->phibar, phibar = sn * cur->phibar;
+  const double denom = 1.0 / gamma;
+  double s = 0;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n; k += (int64_t)gridDim.x * kBlock) {
+    const double w2k = w2[k];
+    const double wn = ((v[k] - oldeps * w1[k]) - delta * w2k) * denom;
+    w1[k] = w2k;
+    w2[k] = wn;
+    x[k] += phi * wn;
+    const double vn = betan > 0 ? r2[k] / betan : 0.0;
+    v[k] = vn;
+    s += vn * r1[k];
+  }
+  s = block_sum(s, lds);
+  if (threadIdx.x == 0) {
+    partC[blockIdx.x] = s;
+    if (blockIdx.x == 0) {
+      SolveState o;
+      o.beta = betan;
+      o.oldb = cur->beta;
+      o.dbar = dbar;
+      o.epsln = epsln;
+      o.phibar = phibar;
+      o.cs = cs;
+      o.sn = sn;
+      o.itn = cur->itn + 1;
+      o.done = !(phibar > target) || !(betan > 0);
+      o.first = 0;
+      o.pad = 0;
+      *next = o;
+    }
+  }
+}
+
+// which kernel serves which column: the output positions whose column has at least kShortBelow stored entries, then the rest
+struct ColumnPlan {
+  DevBuf<int32_t> d_list;
+  int64_t n_long = 0, n_short = 0;
+  int blocks_long = 0, blocks_short = 0;
+  int parts() const { return blocks_long + blocks_short; }
+};
+
+void plan_columns(const bsn_sfbm *s, const int64_t *ind_sub, int64_t m, ColumnPlan *pl) {
+  std::vector<int32_t> list((size_t)std::max<int64_t>(m, 1));
+  int64_t nl = 0, ns = 0;
+  for (int64_t j = 0; j < m; j++) {
+    const int64_t j2 = ind_sub ? ind_sub[j] : j;
+    if (s->hp[(size_t)j2 + 1] - s->hp[(size_t)j2] >= kShortBelow) list[(size_t)nl++] = (int32_t)j;
+  }
+  for (int64_t j = 0; j < m; j++) {
+    const int64_t j2 = ind_sub ? ind_sub[j] : j;
+    if (s->hp[(size_t)j2 + 1] - s->hp[(size_t)j2] < kShortBelow) list[(size_t)(nl + ns++)] = (int32_t)j;
+  }
+  pl->n_long = nl;
+  pl->n_short = ns;
+  pl->blocks_long = (int)std::min<int64_t>((nl + 3) / 4, kMaxColBlocks);
+  pl->blocks_short = (int)std::min<int64_t>((ns + kBlock / kShortLanes - 1) / (kBlock / kShortLanes), kMaxColBlocks);
+  BSN_HIP(hipMemcpy(pl->d_list.ensure(list.size()), list.data(), list.size() * 4, hipMemcpyHostToDevice));
+}
+
+// the two launches of a column walk; part (MODE 0, may be NULL) receives pl.parts() partial sums
+template <int MODE>
+void launch_columns(const bsn_sfbm *s, const ColumnPlan &pl, const int64_t *d_ind, const double *d_v, const double *d_dg,
+                    const uint8_t *d_mask, double *d_out, int scatter, double *d_part, const SolveState *d_st, int maxiter) {
+  if (pl.n_long)
+    k_columns<MODE, 64><<<pl.blocks_long, kBlock>>>(s->p.p, s->i.p, s->x.p, pl.d_list.p, pl.n_long, d_ind, d_v, d_dg, d_mask,
+                                                    d_out, scatter, d_part, d_st, maxiter);
+  if (pl.n_short)
+    k_columns<MODE, kShortLanes><<<pl.blocks_short, kBlock>>>(s->p.p, s->i.p, s->x.p, pl.d_list.p + pl.n_long, pl.n_short, d_ind,
+                                                              d_v, d_dg, d_mask, d_out, scatter,
+                                                              d_part ? d_part + pl.blocks_long : nullptr, d_st, maxiter);
+  BSN_HIP(hipGetLastError());
+}
+
+int vec_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + kBlock - 1) / kBlock, kMaxVecBlocks)); }
+
+void check_ind_sub(const bsn_sfbm *s, const int64_t *ind_sub, int64_t m, bool refuse_repeats, const char *what) {
+  if (m < 0) fail("%s: 'm' is negative", what);
+  if (!ind_sub) {
+    if (m != s->m2) fail("%s: without 'ind_sub', the vectors need one entry per column of 'corr'", what);
+    return;
+  }
+  std::vector<char> seen(refuse_repeats ? (size_t)s->m2 : 0, 0);
+  for (int64_t j = 0; j < m; j++) {
+    const int64_t j2 = ind_sub[j];
+    if (j2 < 0 || j2 >= s->m2) fail("'ind_sub' has %lld out of range [0, %lld).", (long long)j2, (long long)s->m2);
+    if (refuse_repeats) {
+      if (seen[(size_t)j2]) fail("%s: 'ind_sub' has %lld more than once.", what, (long long)j2);
+      seen[(size_t)j2] = 1;
+    }
+  }
+}
+
+// HIP events around the device work of one call -> s->last_ms
+struct CallTimer {
+  bsn_sfbm *s;
+  hipEvent_t a = nullptr, b = nullptr;
+  explicit CallTimer(bsn_sfbm *s_) : s(s_) {
+    BSN_HIP(hipEventCreate(&a));
+    BSN_HIP(hipEventCreate(&b));
+    BSN_HIP(hipEventRecord(a, nullptr));
+  }
+  void stop() {
+    float ms = 0;
+    BSN_HIP(hipEventRecord(b, nullptr));
+    BSN_HIP(hipEventSynchronize(b));
+    BSN_HIP(hipEventElapsedTime(&ms, a, b));
+    s->last_ms = ms;
+  }
+  ~CallTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+};
+
+double host_total(const double *d_part, int n) {
+  std::vector<double> h((size_t)n);
+  BSN_HIP(hipMemcpy(h.data(), d_part, (size_t)n * 8, hipMemcpyDeviceToHost));
+  double t = 0;
+  for (int k = 0; k < n; k++) t += h[(size_t)k];
+  return t;
+}
+
 }  // namespace
 }  // namespace bsn
 
@@ -258,9 +608,11 @@ int bsn_sfbm_from_csc(const int64_t *p, const int32_t *i, const double *x, int64
       std::copy(p, p + m2 + 1, full_p.begin());
     }
     S->nnz = full_p[(size_t)m2];
+    S->hp = full_p;
     BSN_HIP(hipMemcpy(S->p.ensure((size_t)m2 + 1), full_p.data(), ((size_t)m2 + 1) * 8, hipMemcpyHostToDevice));
-    S->i.ensure((size_t)std::max<int64_t>(S->nnz, 1));
-    S->x.ensure((size_t)std::max<int64_t>(S->nnz, 1));
+    // two entries of slack: the column kernels load entries in aligned pairs and may touch (never use) the pair after the last
+    S->i.ensure((size_t)S->nnz + 2);
+    S->x.ensure((size_t)S->nnz + 2);
     if (!upper) {
       if (nnz) {
         BSN_HIP(hipMemcpy(S->i.p, i, (size_t)nnz * 4, hipMemcpyHostToDevice));
@@ -387,6 +739,164 @@ int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const do
       BSN_HIP(hipMemcpy(t.data(), d_ticks.p, (size_t)G * 8, hipMemcpyDeviceToHost));
       for (int64_t g = 0; g < G; g++) time_out[g] = clock_khz > 0 ? (double)t[(size_t)g] / (clock_khz * 1e3) : NAN;
     }
+  });
+}
+
+int bsn_sfbm_last_ms(const bsn_sfbm *s, double *ms_out) {
+  return guarded([&] {
+    if (!s || !ms_out) fail("bsn_sfbm_last_ms: NULL argument");
+    *ms_out = s->last_ms;
+  });
+}
+
+int bsn_sfbm_prodvec(bsn_sfbm *s, const double *x, const int64_t *ind_sub, int64_t m, double *y_out) {
+  return guarded([&] {
+    if (!s) fail("bsn_sfbm_prodvec: NULL 'corr'");
+    check_ind_sub(s, ind_sub, m, true, "sp_prodVec");
+    if (m > 0 && (!x || !y_out)) fail("bsn_sfbm_prodvec: arguments");
+    if (m == 0) return;
+    require_gpu();
+    ColumnPlan pl;
+    plan_columns(s, ind_sub, m, &pl);
+    DevBuf<double> d_x, d_v, d_y;
+    DevBuf<int64_t> d_ind;
+    BSN_HIP(hipMemcpy(d_x.ensure((size_t)m), x, (size_t)m * 8, hipMemcpyHostToDevice));
+    d_y.ensure((size_t)m);
+    if (ind_sub) {
+      BSN_HIP(hipMemcpy(d_ind.ensure((size_t)m), ind_sub, (size_t)m * 8, hipMemcpyHostToDevice));
+      d_v.ensure((size_t)s->m2);
+    }
+    CallTimer timer(s);
+    if (ind_sub) {
+      BSN_HIP(hipMemsetAsync(d_v.p, 0, (size_t)s->m2 * 8, nullptr));
+      k_scatter<<<(unsigned)((m + kBlock - 1) / kBlock), kBlock>>>(d_x.p, d_ind.p, m, d_v.p);
+    }
+    launch_columns<0>(s, pl, ind_sub ? d_ind.p : nullptr, ind_sub ? d_v.p : d_x.p, nullptr, nullptr, d_y.p, 0, nullptr, nullptr, 0);
+    timer.stop();
+    BSN_HIP(hipMemcpy(y_out, d_y.p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  });
+}
+
+int bsn_sfbm_ld_scores(bsn_sfbm *s, const int64_t *ind_sub, int64_t m, double *out) {
+  return guarded([&] {
+    if (!s) fail("bsn_sfbm_ld_scores: NULL 'corr'");
+    check_ind_sub(s, ind_sub, m, false, "ld_scores_sfbm");
+    if (m > 0 && !out) fail("bsn_sfbm_ld_scores: arguments");
+    if (m == 0) return;
+    require_gpu();
+    ColumnPlan pl;
+    plan_columns(s, ind_sub, m, &pl);
+    DevBuf<double> d_y;
+    DevBuf<int64_t> d_ind;
+    DevBuf<uint8_t> d_mask;
+    d_y.ensure((size_t)m);
+    if (ind_sub) {
+      BSN_HIP(hipMemcpy(d_ind.ensure((size_t)m), ind_sub, (size_t)m * 8, hipMemcpyHostToDevice));
+      d_mask.ensure((size_t)s->m2);
+    }
+    CallTimer timer(s);
+    if (ind_sub) {
+      BSN_HIP(hipMemsetAsync(d_mask.p, 0, (size_t)s->m2, nullptr));
+      k_mask<<<(unsigned)((m + kBlock - 1) / kBlock), kBlock>>>(d_ind.p, m, d_mask.p);
+    }
+    launch_columns<1>(s, pl, ind_sub ? d_ind.p : nullptr, nullptr, nullptr, ind_sub ? d_mask.p : nullptr, d_y.p, 0, nullptr,
+                      nullptr, 0);
+    timer.stop();
+    BSN_HIP(hipMemcpy(out, d_y.p, (size_t)m * 8, hipMemcpyDeviceToHost));
+  });
+}
+
+int bsn_sfbm_solve_sym(bsn_sfbm *s, const double *b, const double *add_to_diag, const int64_t *ind_sub, int64_t m, double tol,
+                       int32_t maxiter, double *x_out, int32_t *iters_out, double *relres_out) {
+  return guarded([&] {
+    if (!s) fail("bsn_sfbm_solve_sym: NULL 'corr'");
+    check_ind_sub(s, ind_sub, m, true, "sp_solve_sym");
+    if (m > 0 && (!b || !add_to_diag || !x_out)) fail("bsn_sfbm_solve_sym: arguments");
+    if (!(tol > 0) || maxiter < 1) fail("sp_solve_sym: 'tol' must be positive and 'maxiter' at least 1");
+    for (int64_t j = 0; j < m; j++)
+      if (!std::isfinite(b[j]) || !std::isfinite(add_to_diag[j])) fail("sp_solve_sym: 'b' and 'add_to_diag' must be finite (element %lld).", (long long)j);
+    if (iters_out) *iters_out = 0;
+    if (relres_out) *relres_out = 0;
+    if (m == 0) return;
+    require_gpu();
+    const int64_t n = s->m2;   // every vector lives on the columns of `corr`, zero outside the subset
+    ColumnPlan pl;
+    plan_columns(s, ind_sub, m, &pl);
+    const int nv = vec_blocks(n), nA = pl.parts();
+    DevBuf<double> d_in, d_ws, d_part, d_alfa;
+    DevBuf<int64_t> d_ind;
+    DevBuf<SolveState> d_st;
+    SolveState *h_st = nullptr;
+    BSN_HIP(hipHostMalloc((void **)&h_st, sizeof(SolveState), hipHostMallocDefault));
+    std::unique_ptr<SolveState, void (*)(SolveState *)> h_guard(h_st, [](SolveState *p) { (void)hipHostFree(p); });
+    d_in.ensure((size_t)(2 * m));
+    BSN_HIP(hipMemcpy(d_in.p, b, (size_t)m * 8, hipMemcpyHostToDevice));
+    BSN_HIP(hipMemcpy(d_in.p + m, add_to_diag, (size_t)m * 8, hipMemcpyHostToDevice));
+    if (ind_sub) BSN_HIP(hipMemcpy(d_ind.ensure((size_t)m), ind_sub, (size_t)m * 8, hipMemcpyHostToDevice));
+    d_ws.ensure((size_t)(10 * n));
+    double *rhs = d_ws.p, *dg = rhs + n, *r1 = dg + n, *r2 = r1 + n, *v = r2 + n, *t = v + n, *w1 = t + n, *w2 = w1 + n,
+           *x = w2 + n, *bb = x + n;
+    d_part.ensure((size_t)(nA + 2 * nv));
+    double *partA = d_part.p, *partB = partA + nA, *partC = partB + nv;
+    d_alfa.ensure(1);
+    d_st.ensure(2);
+    CallTimer timer(s);
+    BSN_HIP(hipMemsetAsync(d_ws.p, 0, (size_t)(10 * n) * 8, nullptr));
+    const unsigned gm = (unsigned)((m + kBlock - 1) / kBlock);
+    if (ind_sub) {
+      k_scatter<<<gm, kBlock>>>(d_in.p, d_ind.p, m, bb);
+      k_scatter<<<gm, kBlock>>>(d_in.p + m, d_ind.p, m, dg);
+    } else {
+      BSN_HIP(hipMemcpyAsync(bb, d_in.p, (size_t)m * 8, hipMemcpyDeviceToDevice, nullptr));
+      BSN_HIP(hipMemcpyAsync(dg, d_in.p + m, (size_t)m * 8, hipMemcpyDeviceToDevice, nullptr));
+    }
+    BSN_HIP(hipMemcpyAsync(rhs, bb, (size_t)n * 8, hipMemcpyDeviceToDevice, nullptr));
+    k_sumsq<<<nv, kBlock>>>(bb, nullptr, n, nullptr, partB);
+    BSN_HIP(hipGetLastError());
+    const double bnorm = std::sqrt(host_total(partB, nv));
+    double relres = 0;
+    int32_t iters = 0;
+    if (bnorm > 0) {
+      const double target = tol * bnorm;
+      const int64_t *ind = ind_sub ? d_ind.p : nullptr;
+      constexpr int kPoll = 8;   // iterations queued between two looks at the state
+      int cur = 0;
+      for (bool restart = false;; restart = true) {
+        // (partB holds the shares of rhs . rhs: of b . b at first, of the true residual's after a restart)
+        k_solve_start<<<nv, kBlock>>>(rhs, n, partB, nv, target, restart ? d_st.p + cur : nullptr, r1, r2, v, w1, w2, d_st.p);
+        BSN_HIP(hipGetLastError());
+        cur = 0;
+        for (;;) {
+          for (int k = 0; k < kPoll; k++, cur ^= 1) {
+            launch_columns<0>(s, pl, ind, v, dg, nullptr, t, 1, partA, d_st.p + cur, maxiter);
+            k_solve_lanczos<<<nv, kBlock>>>(t, r1, r2, n, partA, nA, partC, nv, d_st.p + cur, maxiter, d_alfa.p, partB);
+            k_solve_update<<<nv, kBlock>>>(v, r1, r2, w1, w2, x, n, partB, nv, d_alfa.p, d_st.p + cur, d_st.p + (cur ^ 1), target,
+                                           maxiter, partC);
+            BSN_HIP(hipGetLastError());
+          }
+          BSN_HIP(hipMemcpyAsync(h_st, d_st.p + cur, sizeof(SolveState), hipMemcpyDeviceToHost, nullptr));
+          BSN_HIP(hipStreamSynchronize(nullptr));
+          if (h_st->done || h_st->itn >= maxiter) break;
+        }
+        iters = h_st->itn;
+        // the TRUE residual b - (A + D) x, which also is the right-hand side of a restart
+        launch_columns<0>(s, pl, ind, x, dg, nullptr, t, 1, nullptr, nullptr, 0);
+        k_sumsq<<<nv, kBlock>>>(bb, t, n, rhs, partB);
+        BSN_HIP(hipGetLastError());
+        relres = std::sqrt(host_total(partB, nv)) / bnorm;
+        if (relres <= tol || iters >= maxiter || !std::isfinite(relres)) break;
+      }
+    }
+    if (ind_sub) {
+      k_gather<<<gm, kBlock>>>(x, d_ind.p, m, t);
+      BSN_HIP(hipGetLastError());
+    }
+    timer.stop();
+    BSN_HIP(hipMemcpy(x_out, ind_sub ? t : x, (size_t)m * 8, hipMemcpyDeviceToHost));
+    if (iters_out) *iters_out = iters;
+    if (relres_out) *relres_out = relres;
+    if (!(relres <= tol))
+      fail("sp_solve_sym: not converged after %d iterations: relative residual %.3e > tol = %.3e.", (int)iters, relres, tol);
   });
 }
 

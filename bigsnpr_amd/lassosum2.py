@@ -40,6 +40,12 @@ class SFBM:
         self._fin()
         self.handle = None
 
+    def last_ms(self):
+        """device milliseconds (host copies excluded) of the last sp_prodVec / ld_scores_sfbm / sp_solve_sym on this matrix"""
+        ms = C.c_double(0.0)
+        check(_lib.load().bsn_sfbm_last_ms(self.handle, C.byref(ms)))
+        return ms.value
+
     def __enter__(self):
         return self
 

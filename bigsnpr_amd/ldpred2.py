@@ -1,0 +1,291 @@
+"""LD scores, LD score regression and LDpred2-inf over the resident SFBM — host mirror of R/ldsc.R, R/LDpred2.R:27-42 and of
+bigsparser's sp_prodVec / sp_solve_sym.
+
+The sparse products run on the device (bsn_sfbm_prodvec, bsn_sfbm_ld_scores, bsn_sfbm_solve_sym); the regression itself
+works on vectors of length M and is numpy on the host, as it is R in the reference.  Indices are 0-based.  Every device
+sum has a fixed order: two calls on the same inputs return the same bits."""
+import ctypes as C
+from statistics import NormalDist
+
+import numpy as np
+
+from . import _lib
+from ._lib import as_f64, check, f64p, i64p, ptr
+from .bed import ERROR_DIM
+from .lassosum2 import SFBM, _col, _ncol, as_SFBM
+
+ERROR_LENGTH = ERROR_DIM + "\nArguments should have the same length."
+
+
+class SolveResult(np.ndarray):
+    """the solution of sp_solve_sym; `.iters` MINRES iterations, `.relres` the true ||b - (A + D) x|| / ||b||"""
+    iters = None
+    relres = None
+
+    def __array_finalize__(self, obj):
+        if obj is not None:
+            self.iters = getattr(obj, "iters", None)
+            self.relres = getattr(obj, "relres", None)
+
+
+def _subset(corr, ind, n, name, repeats_ok=False):
+    """the checks on an index vector, before any device work; None when it selects every column in order"""
+    m2 = _ncol(corr)
+    if ind is None:
+        if n is not None and n != m2:
+            raise ValueError(ERROR_LENGTH)
+        return None
+    ind = np.ascontiguousarray(np.ravel(ind), dtype=np.int64)
+    if n is not None and ind.size != n:
+        raise ValueError(ERROR_LENGTH)
+    if not np.all((ind >= 0) & (ind < m2)):
+        raise ValueError("all(%s %%in%% cols_along(corr)) is not TRUE" % name)
+    if not repeats_ok and np.unique(ind).size != ind.size:
+        raise ValueError("'%s' should not have repeated indices." % name)
+    return ind
+
+
+class _Resident:
+    """corr as an SFBM for the length of one call: converted (and freed again) only when it is not one already"""
+
+    def __init__(self, corr):
+        self.own = not isinstance(corr, SFBM)
+        self.corr = corr
+
+    def __enter__(self):
+        self.sf = as_SFBM(self.corr)
+        return self.sf
+
+    def __exit__(self, *exc):
+        if self.own:
+            self.sf.close()
+
+
+def sp_prodVec(corr, x, ind_corr=None):
+    """bigsparser::sp_prodVec on corr[ind_corr, ind_corr] (all of corr by default): corr . x.  A repeated index is refused."""
+    x = as_f64(np.ravel(np.asarray(x, dtype=np.float64)))
+    ind = _subset(corr, ind_corr, x.size, "ind.corr")
+    with _Resident(corr) as sf:
+        y = np.empty(x.size, dtype=np.float64)
+        check(_lib.load().bsn_sfbm_prodvec(sf.handle, ptr(x, f64p), ptr(ind, i64p), x.size, ptr(y, f64p)))
+    return y
+
+
+sp_cprodVec = sp_prodVec   # the matrix is symmetric
+
+
+def ld_scores_sfbm(corr, ind_sub=None):
+    """src/ld-scores-sfbm.cpp:10-69: for each listed column, the sum of x^2 over its stored entries whose row is listed too
+    (all columns by default).  The list is a mask: a repeated index gives a repeated value."""
+    ind = _subset(corr, ind_sub, None, "ind_sub", repeats_ok=True)
+    with _Resident(corr) as sf:
+        m = sf.ncol if ind is None else ind.size
+        out = np.empty(m, dtype=np.float64)
+        check(_lib.load().bsn_sfbm_ld_scores(sf.handle, ptr(ind, i64p), m, ptr(out, f64p)))
+    return out
+
+
+def sp_colSumsSq_sym(p, i, x):
+    """src/sp-colsumssq-sym.cpp:9-32: colSums(A^2) of a symmetric matrix given as the CSC of its upper triangle"""
+    p = np.asarray(p)
+    with SFBM(p, i, x, p.size - 1, upper=True) as sf:
+        return ld_scores_sfbm(sf)
+
+
+def sp_solve_sym(corr, b, add_to_diag=0, tol=1e-10, maxiter=None, ind_corr=None):
+    """Solves (corr[ind_corr, ind_corr] + diag(add_to_diag)) x = b (bigsparser::sp_solve_sym) by MINRES on the device.  The
+    iteration stops on the recurrence's residual, the true residual ||b - (A + D) x|| / ||b|| is then formed with one more
+    product and has to be <= tol; BsnError (naming the iterations and the residual reached) after maxiter iterations
+    without that.  tol = 1e-10 and maxiter = 10 * length(b) are this project's choice.  Returns x with `.iters` and
+    `.relres`."""
+    b = as_f64(np.ravel(np.asarray(b, dtype=np.float64)))
+    m = b.size
+    ind = _subset(corr, ind_corr, m, "ind.corr")
+    d = np.asarray(add_to_diag, dtype=np.float64)
+    if d.ndim == 0 or d.size == 1:
+        d = np.full(m, float(d.ravel()[0]) if d.size else 0.0)
+    d = as_f64(np.ravel(d))
+    if d.size != m:
+        raise ValueError(ERROR_LENGTH)
+    if not tol > 0:
+        raise ValueError("'tol' should have only positive values.")
+    maxiter = 10 * max(m, 1) if maxiter is None else int(maxiter)
+    if maxiter < 1:
+        raise ValueError("'maxiter' should be at least 1.")
+    with _Resident(corr) as sf:
+        x = np.empty(m, dtype=np.float64)
+        iters, relres = C.c_int32(0), C.c_double(0.0)
+        check(_lib.load().bsn_sfbm_solve_sym(sf.handle, ptr(b, f64p), ptr(d, f64p), ptr(ind, i64p), m, float(tol),
+                                             min(maxiter, 2 ** 31 - 1), ptr(x, f64p), C.byref(iters), C.byref(relres)))
+    out = x.view(SolveResult)
+    out.iters, out.relres = int(iters.value), float(relres.value)
+    return out
+
+
+def _sumstats(df_beta):
+    """assert_df_with_names(df_beta, c("beta", "beta_se", "n_eff")); a single n_eff is recycled as a data frame does"""
+    beta, beta_se, n_eff = (_col(df_beta, n) for n in ("beta", "beta_se", "n_eff"))
+    if n_eff.size == 1:
+        n_eff = np.repeat(n_eff, beta.size)
+    return beta, beta_se, n_eff
+
+
+# ---- R/ldsc.R ----------------------------------------------------------------------------------------------------------
+
+def WEIGHTS(pred, w_ld):
+    """heteroscedasticity and overcounting weights (R/ldsc.R:4-6)"""
+    return 1 / (pred ** 2 * w_ld)
+
+
+def wlm(x, y, w):
+    """R/ldsc.R:11-21, equivalent to stats::lm.wfit(cbind(1, x), y, w): (intercept, slope, pred)"""
+    wx = w * x
+    W, WX = np.sum(w), np.sum(wx)
+    WY, WXX, WXY = np.dot(w, y), np.dot(wx, x), np.dot(wx, y)
+    alpha = (WXX * WY - WX * WXY) / (W * WXX - WX ** 2)
+    beta = (WXY * W - WX * WY) / (W * WXX - WX ** 2)
+    return alpha, beta, x * beta + alpha
+
+
+def wlm_no_int(x, y, w):
+    """R/ldsc.R:24-30, equivalent to stats::lm.wfit(as.matrix(x), y, w): (slope, pred)"""
+    wx = w * x
+    beta = np.dot(wx, y) / np.dot(wx, x)
+    return beta, x * beta
+
+
+def _ldsc_two_step(ld_score, ld_size, chi2, sample_size, intercept, chi2_thr1, chi2_thr2):
+    """R/ldsc.R:85-122 (blocks = NULL), chi2 already shifted"""
+    if intercept is None:
+        sub1 = chi2 < chi2_thr1
+        w_ld = np.maximum(ld_score[sub1], 1)
+        x1 = (ld_score / ld_size * sample_size)[sub1]
+        y1 = chi2[sub1]
+        pred0 = y1
+        for _ in range(100):
+            pred = wlm(x1, y1, WEIGHTS(pred0, w_ld))[2]
+            if np.max(np.abs(pred - pred0)) < 1e-6:
+                break
+            pred0 = pred
+        step1_int = wlm(x1, y1, WEIGHTS(pred0, w_ld))[0]
+    else:
+        step1_int = intercept
+    sub2 = chi2 < chi2_thr2
+    w_ld = np.maximum(ld_score[sub2], 1)
+    x = (ld_score / ld_size * sample_size)[sub2]
+    y = chi2[sub2]
+    yp = y - step1_int
+    pred0 = y
+    for _ in range(100):
+        pred = step1_int + wlm_no_int(x, yp, WEIGHTS(pred0, w_ld))[1]
+        if np.max(np.abs(pred - pred0)) < 1e-6:
+            break
+        pred0 = pred
+    step2_h2 = wlm_no_int(x, yp, WEIGHTS(pred0, w_ld))[0]
+    return step1_int, step2_h2
+
+
+def snp_ldsc(ld_score, ld_size, chi2, sample_size, blocks=200, intercept=None, chi2_thr1=30, chi2_thr2=np.inf, ncores=1):
+    """R/ldsc.R:66-158.  Returns a dict with int, int_se, h2, h2_se (int and h2 only when blocks is None).  ncores is
+    accepted for the reference's signature; the jackknife runs on the host, one block after the other."""
+    chi2 = np.ravel(np.asarray(chi2, dtype=np.float64)) + 1e-8
+    ld_score = np.ravel(np.asarray(ld_score, dtype=np.float64))
+    if not np.all(chi2 > 0):
+        raise ValueError("'chi2' should have only positive values.")
+    if chi2.size != ld_score.size:
+        raise ValueError(ERROR_LENGTH)
+    if np.size(ld_size) != 1:
+        raise ValueError(ERROR_LENGTH)
+    ld_size = np.ravel(ld_size)[0]
+    if ld_size != np.trunc(ld_size):
+        raise ValueError("'ld_size' should contain only integers.")
+    ld_size = float(ld_size)
+    if not (int(ncores) == ncores and ncores >= 1):
+        raise ValueError("'ncores' should be an integer >= 1.")
+    M = chi2.size
+    sample_size = np.ravel(np.asarray(sample_size, dtype=np.float64))
+    if sample_size.size == 1:
+        sample_size = np.repeat(sample_size, M)
+    elif sample_size.size != M:
+        raise ValueError(ERROR_LENGTH)
+    intercept = None if intercept is None else float(intercept)
+
+    if blocks is None:
+        a, h2 = _ldsc_two_step(ld_score, ld_size, chi2, sample_size, intercept, chi2_thr1, chi2_thr2)
+        return {"int": float(a), "h2": float(h2)}
+
+    # delete-a-group jackknife variance estimator (R/ldsc.R:126-155)
+    if np.size(blocks) == 1:
+        nb = int(np.ravel(blocks)[0])
+        blocks = np.sort(np.resize(np.arange(1, nb + 1), M))    # sort(rep_len(seq_len(blocks), M))
+    else:
+        blocks = np.ravel(np.asarray(blocks))
+        if blocks.size != M:
+            raise ValueError(ERROR_LENGTH)
+    groups = [np.nonzero(blocks == g)[0] for g in np.unique(blocks)]      # split(seq_along(blocks), blocks)
+    h_blocks = M / np.array([g.size for g in groups], dtype=np.float64)
+
+    def delete(ind_rm):
+        keep = np.ones(M, dtype=bool)
+        if ind_rm is not None:
+            keep[ind_rm] = False
+        # the reference calls itself here with the shifted chi2, which is shifted once more (R/ldsc.R:73, :140)
+        return _ldsc_two_step(ld_score[keep], ld_size, chi2[keep] + 1e-8, sample_size[keep], intercept, chi2_thr1, chi2_thr2)
+
+    estim = delete(None)
+    del_int, del_h2 = (np.array(v, dtype=np.float64) for v in zip(*[delete(g) for g in groups]))
+    # https://doi.org/10.1023/A:1008800423698
+    int_pseudo = h_blocks * estim[0] - (h_blocks - 1) * del_int
+    h2_pseudo = h_blocks * estim[1] - (h_blocks - 1) * del_h2
+    int_J = np.sum(int_pseudo / h_blocks)
+    h2_J = np.sum(h2_pseudo / h_blocks)
+    return {"int": float(int_J),
+            "int_se": float(np.sqrt(np.mean((int_pseudo - int_J) ** 2 / (h_blocks - 1)))),
+            "h2": float(h2_J),
+            "h2_se": float(np.sqrt(np.mean((h2_pseudo - h2_J) ** 2 / (h_blocks - 1))))}
+
+
+def snp_ldsc2(corr, df_beta, blocks=None, intercept=1, ncores=1, ind_beta=None, chi2_thr1=30, chi2_thr2=np.inf):
+    """R/ldsc.R:192-224: the LD scores of every column of corr on the device (ld_scores_sfbm), then snp_ldsc on
+    full_ld[ind_beta] with ld_size = ncol(corr).  corr: an SFBM or anything as_SFBM takes (converted for this call only)."""
+    beta, beta_se, n_eff = _sumstats(df_beta)
+    m2 = _ncol(corr)
+    ind = np.arange(m2, dtype=np.int64) if ind_beta is None else np.ascontiguousarray(np.ravel(ind_beta), dtype=np.int64)
+    if ind.size != beta.size:
+        raise ValueError(ERROR_LENGTH)
+    if not np.all((ind >= 0) & (ind < m2)):
+        raise ValueError("all(ind.beta %in% cols_along(corr)) is not TRUE")
+    if not np.all(beta_se > 0):
+        raise ValueError("'df_beta$beta_se' should have only positive values.")
+    if not (beta.size == beta_se.size == n_eff.size):
+        raise ValueError(ERROR_LENGTH)
+    full_ld = ld_scores_sfbm(corr)
+    return snp_ldsc(full_ld[ind], m2, (beta / beta_se) ** 2, n_eff, blocks=blocks, intercept=intercept, ncores=ncores,
+                    chi2_thr1=chi2_thr1, chi2_thr2=chi2_thr2)
+
+
+def coef_to_liab(K_pop, K_gwas=0.5):
+    """R/ldsc.R:245-250: coefficient to convert e.g. a heritability to the liability scale"""
+    nd = NormalDist()
+    z = nd.pdf(nd.inv_cdf(min(K_pop, 1 - K_pop)))
+    return (K_pop * (1 - K_pop) / z) ** 2 / (K_gwas * (1 - K_gwas))
+
+
+# ---- R/LDpred2.R:27-42 ---------------------------------------------------------------------------------------------------
+
+def snp_ldpred2_inf(corr, df_beta, h2):
+    """R/LDpred2.R:27-42: effects under the infinitesimal model, (corr + diag(ncol(corr) / (h2 N))) x = beta_hat solved on
+    the device (sp_solve_sym with its default tol and maxiter) and scaled back.  corr: an SFBM or anything as_SFBM takes."""
+    beta, beta_se, n_eff = _sumstats(df_beta)
+    m2 = _ncol(corr)
+    if not (m2 == beta.size == beta_se.size == n_eff.size):
+        raise ValueError(ERROR_LENGTH)
+    if not np.all(beta_se > 0):
+        raise ValueError("'df_beta$beta_se' should have only positive values.")
+    if not np.all(np.asarray(h2, dtype=np.float64) > 0):
+        raise ValueError("'h2' should have only positive values.")
+    N = n_eff
+    scale = np.sqrt(N * beta_se ** 2 + beta ** 2)
+    beta_hat = beta / scale
+    beta_inf = sp_solve_sym(corr, beta_hat, add_to_diag=m2 / (float(h2) * N))
+    return np.asarray(beta_inf) * scale

@@ -504,6 +504,26 @@ int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const do
                   const double *delta, int64_t G, const int64_t *ind_sub, double dfmax, int32_t maxiter, double tol,
                   double *beta_out, int32_t *num_iter_out, double *time_out);
 
+/* ---- products with the resident matrix: bigsparser's sp_prodVec and sp_solve_sym, ld_scores_sfbm ------------------------
+ * ind_sub [m] (0-based columns of `corr`, any order; NULL: all of them, m = m2) means "as if run on corr[ind_sub, ind_sub]".
+ * Every sum has a fixed order that depends on the shapes only: two calls on the same inputs return the same bits.
+ *
+ * bsn_sfbm_prodvec: y_out [m] = corr[ind_sub, ind_sub] . x [m] (sp_prodVec; sp_cprodVec is the same call, the matrix is
+ * symmetric).  A repeated index is refused before any device work. */
+int bsn_sfbm_prodvec(bsn_sfbm *s, const double *x, const int64_t *ind_sub, int64_t m, double *y_out);
+/* src/ld-scores-sfbm.cpp:10-69: out [j] = sum of x^2 over the stored entries of column ind_sub[j] whose row is in ind_sub
+ * (a mask: repeated indices are allowed and give repeated values). */
+int bsn_sfbm_ld_scores(bsn_sfbm *s, const int64_t *ind_sub, int64_t m, double *out);
+/* Solves (corr[ind_sub, ind_sub] + diag(add_to_diag)) x = b by MINRES (Paige & Saunders), the iteration on the device.
+ * Stops when the recurrence's residual norm is <= tol * ||b||, then forms the TRUE residual ||b - (A + D) x|| / ||b|| with
+ * one more product (relres_out) and goes on, from that residual, while it exceeds tol.  After maxiter iterations without
+ * that the call returns an error whose message names the iterations and the residual reached; x_out [m], iters_out and
+ * relres_out (either may be NULL) are filled in that case too.  A repeated index is refused before any device work. */
+int bsn_sfbm_solve_sym(bsn_sfbm *s, const double *b, const double *add_to_diag, const int64_t *ind_sub, int64_t m, double tol,
+                       int32_t maxiter, double *x_out, int32_t *iters_out, double *relres_out);
+/* device milliseconds (HIP events, host copies excluded) of the last of the three calls above on this handle */
+int bsn_sfbm_last_ms(const bsn_sfbm *s, double *ms_out);
+
 /* ---- device memory + timing helpers for hosts without a HIP binding -------- */
 int bsn_malloc(void **d_ptr, int64_t bytes);
 int bsn_free(void *d_ptr);

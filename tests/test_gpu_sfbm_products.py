@@ -1,0 +1,354 @@
+"""sp_prodVec, ld_scores_sfbm, sp_solve_sym and the LDSC / LDpred2-inf pipeline on the device.
+
+The bound of every product check.  A computed sum of L products, in ANY order and with or without fused multiply-adds,
+satisfies |fl(sum_k a_k x_k) - sum_k a_k x_k| <= gamma_L sum_k |a_k| |x_k| with gamma_L = L u / (1 - L u) and u = 2^-53
+(Higham, Accuracy and Stability of Numerical Algorithms, 2nd ed., section 3.1: each product carries one rounding, each term
+then takes part in at most L - 1 additions, and (1 + d_1) ... (1 + d_L) = 1 + theta with |theta| <= gamma_L; a fused
+multiply-add only removes roundings).  gamma_L <= (L + 1) u whenever L (L + 1) u <= 1, i.e. for every L below 9e7.  So for
+column j with L_j stored entries inside the subset
+
+    |y_gpu[j] - y_exact[j]| <= (L_j + 1) u (|A| |x|)_j,
+
+y_exact being formed here in rational arithmetic (fractions) on a sample of the columns.  Entries outside a subset meet an
+exact zero of the scattered vector: they add nothing and round nothing.  Against scipy's own fp64 product, which obeys the
+same bound, the bound doubles.  The LD scores obey it with x^2 in the place of |a| |x|."""
+import os
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+sparse = pytest.importorskip("scipy.sparse")
+
+U = 2.0 ** -53
+UQ = Fraction(1, 2 ** 53)
+
+
+@pytest.fixture(scope="module")
+def ba():
+    import bigsnpr_amd
+    return bigsnpr_amd
+
+
+@pytest.fixture(scope="module")
+def data(ba, golden_dir):
+    """the summary statistics of test_gpu_lassosum2.py: marginal regressions of a phenotype simulated from the genotypes"""
+    gb = ba.bed(os.path.join(golden_dir, "example.bed"))
+    G = ba.read_bed(gb, None, None).astype(np.float64)          # n x m, no missing values in this file
+    keep = np.nonzero(G.std(axis=0) > 0)[0]
+    G = G[:, keep]
+    n, m = G.shape
+    rng = np.random.default_rng(42)
+    Z = (G - G.mean(axis=0)) / G.std(axis=0)
+    b = np.where(rng.random(m) < 0.02, rng.normal(0, 0.3, m), 0.0)
+    y = Z @ b + rng.normal(0, 1, n)
+    gc = G - G.mean(axis=0)
+    yc = y - y.mean()
+    sxx = (gc * gc).sum(axis=0)
+    beta = gc.T @ yc / sxx
+    resid = ((yc[:, None] - gc * beta) ** 2).sum(axis=0) / (n - 2)
+    df = {"beta": beta, "beta_se": np.sqrt(resid / sxx),
+          "n_eff": np.round(n * rng.uniform(0.8, 1.0, m))}
+    return gb, keep, df, G
+
+
+@pytest.fixture(scope="module")
+def cors(ba, data):
+    gb, keep = data[0], data[1]
+    return {size: ba.bed_cor(gb, ind_col=keep, size=size) for size in (40, 100, 500)}
+
+
+def full_of(corr):
+    """full columns (scipy CSC, sorted rows) of a CorResult or of a scipy matrix (whole, or its upper triangle)"""
+    A = corr.tocsc() if hasattr(corr, "Dim") else sparse.csc_matrix(corr, dtype=np.float64)
+    if sparse.tril(A, k=-1).nnz == 0:
+        A = A + sparse.triu(A, k=1).T
+    A = sparse.csc_matrix(A)
+    A.sum_duplicates()
+    A.sort_indices()
+    return A
+
+
+def chain_corr(m2, rho):
+    """tridiagonal with rho off the diagonal (tests/test_lassosum2_cpu.py): indefinite for rho > 0.5 at large m2"""
+    R = sparse.diags([np.full(m2 - 1, rho), np.ones(m2), np.full(m2 - 1, rho)], [-1, 0, 1])
+    return sparse.csc_matrix(R)
+
+
+def scipy_matrices():
+    rng = np.random.default_rng(11)
+    R = sparse.random(700, 700, density=0.02, random_state=np.random.RandomState(5), format="csc")
+    irregular = sparse.csc_matrix(R + R.T + sparse.diags(rng.uniform(0.5, 1.5, 700)))
+    E = sparse.lil_matrix(irregular)
+    for j in (0, 17, 18, 350, 699):            # empty columns (and rows: the matrix stays symmetric)
+        E[j, :] = 0
+        E[:, j] = 0
+    empty = sparse.csc_matrix(E)
+    empty.eliminate_zeros()
+    assert np.any(np.diff(empty.indptr) == 0)
+    wide = sparse.csc_matrix(np.corrcoef(rng.normal(size=(300, 150)), rowvar=False))     # every column long (150 entries)
+    return {"irregular": irregular, "empty_columns": empty, "one_by_one": sparse.csc_matrix(np.array([[0.75]])),
+            "dense_columns": wide}
+
+
+def exact_column(A, j, x, square=False):
+    """(sum, sum of absolute values, number of terms) of column j's terms a_ij x_i (a_ij^2 when `square`), in rationals"""
+    lo, hi = A.indptr[j], A.indptr[j + 1]
+    s, sa = Fraction(0), Fraction(0)
+    for r, a in zip(A.indices[lo:hi], A.data[lo:hi]):
+        t = Fraction(float(a)) * (Fraction(float(a)) if square else Fraction(float(x[r])))
+        s += t
+        sa += abs(t)
+    return s, sa, int(hi - lo)
+
+
+def check_exact(A, x, y, cols, square=False):
+    """the bound of the module docstring, in rationals, for the listed columns of A (x: the vector seen by those columns)"""
+    worst = 0.0
+    for j in cols:
+        s, sa, L = exact_column(A, j, x, square)
+        err, bound = abs(Fraction(float(y[j])) - s), (L + 1) * UQ * sa
+        if sa:
+            worst = max(worst, float(err / (UQ * sa)) / (L + 1))
+        assert err <= bound, (j, L, float(err), float(bound))
+    return worst
+
+
+def check_scipy(A, x, y, square=False):
+    """twice the bound, against scipy's fp64 product, for every column"""
+    L = np.diff(A.indptr)
+    if square:
+        ref = mag = np.asarray(A.multiply(A).sum(axis=0)).ravel()
+    else:
+        ref, mag = A.T @ x, abs(A).T @ np.abs(x)
+    assert np.all(np.abs(y - ref) <= 2 * (L + 1) * U * mag), np.max(np.abs(y - ref) / np.maximum(mag, 1e-300))
+
+
+def sample_cols(m, k, seed):
+    rng = np.random.default_rng(seed)
+    return np.arange(m) if m <= k else np.unique(np.concatenate([[0, m - 1], rng.choice(m, k, replace=False)]))
+
+
+def test_product_within_the_summation_bound(ba, cors):
+    mats = dict(("bed_cor_%d" % s, c) for s, c in cors.items())
+    mats.update(scipy_matrices())
+    for name, M in mats.items():
+        A = full_of(M)
+        m2 = A.shape[0]
+        x = np.random.default_rng(3).normal(size=m2)
+        y = ba.sp_prodVec(M, x)
+        assert y.shape == (m2,)
+        check_scipy(A, x, y)
+        worst = check_exact(A, x, y, sample_cols(m2, 150, 1))
+        print("%s: m2 = %d, nnz = %d, worst error / ((L + 1) u |A||x|) = %.3f" % (name, m2, A.nnz, worst))
+        assert np.array_equal(ba.sp_cprodVec(M, x), y)
+
+
+def test_product_on_subsets(ba, cors):
+    rng = np.random.default_rng(7)
+    for M in (cors[100], scipy_matrices()["irregular"]):
+        A = full_of(M)
+        m2 = A.shape[0]
+        k = m2 // 3
+        with ba.as_SFBM(M) as sf:
+            for sub in (np.sort(rng.choice(m2, k, replace=False)), rng.choice(m2, k, replace=False)):
+                x = rng.normal(size=k)
+                y = ba.sp_prodVec(sf, x, ind_corr=sub)
+                As = sparse.csc_matrix(A[sub][:, sub])
+                As.sort_indices()
+                check_scipy(As, x, y)
+                check_exact(As, x, y, sample_cols(k, 100, 2))
+
+
+def test_same_bits_twice_and_through_every_input_form(ba, cors):
+    corr = cors[100]
+    m2 = corr.Dim[1]
+    A = full_of(corr)
+    fp, fi, fx = A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data
+    forms = [corr,                                                        # CorResult (upper, expanded on the device)
+             corr.tocsc(),                                                # scipy, upper triangle
+             sparse.csc_matrix((fx, fi, fp), shape=(m2, m2)),             # scipy, full columns
+             ba.SFBM(fp, fi, fx, m2, False),                              # full columns given directly
+             ba.SFBM(corr.p, corr.i, corr.x, m2, True)]
+    rng = np.random.default_rng(5)
+    x = rng.normal(size=m2)
+    d = rng.uniform(0.5, 2, m2)
+    sub = rng.choice(m2, 900, replace=False)
+    ys = [ba.sp_prodVec(f, x) for f in forms]
+    ls = [ba.ld_scores_sfbm(f) for f in forms]
+    zs = [ba.sp_prodVec(f, x[:900], ind_corr=sub) for f in forms]
+    ss = [ba.sp_solve_sym(f, x, add_to_diag=d) for f in forms]
+    for k in range(1, len(forms)):
+        assert np.array_equal(ys[k], ys[0]) and np.array_equal(ls[k], ls[0]) and np.array_equal(zs[k], zs[0])
+        assert np.array_equal(np.asarray(ss[k]), np.asarray(ss[0]))
+        assert ss[k].iters == ss[0].iters and ss[k].relres == ss[0].relres
+    sf = forms[3]
+    for _ in range(2):
+        assert np.array_equal(ba.sp_prodVec(sf, x), ys[0])
+        assert np.array_equal(ba.ld_scores_sfbm(sf, sub), ba.ld_scores_sfbm(forms[4], sub))
+        again = ba.sp_solve_sym(sf, x, add_to_diag=d)
+        assert np.array_equal(np.asarray(again), np.asarray(ss[0])) and again.iters == ss[0].iters
+    for f in forms[3:]:
+        f.close()
+
+
+def test_ld_scores(ba, cors):
+    rng = np.random.default_rng(9)
+    mats = [cors[40], cors[500]] + list(scipy_matrices().values())
+    for M in mats:
+        A = full_of(M)
+        m2 = A.shape[0]
+        with ba.as_SFBM(M) as sf:
+            ld = ba.ld_scores_sfbm(sf)
+            check_scipy(A, None, ld, square=True)
+            check_exact(A, None, ld, sample_cols(m2, 100, 3), square=True)
+            # test-2-ld-scores.R:82-98: ld_scores_sfbm(as_SFBM(corr0), ind) against sp_colSumsSq_sym of corr0[ind, ind]
+            k = max(1, m2 // 2)
+            for ind in (np.sort(rng.choice(m2, k, replace=False)), rng.choice(m2, k, replace=False)):
+                got = ba.ld_scores_sfbm(sf, ind)
+                As = sparse.csc_matrix(A[ind][:, ind])
+                As.sort_indices()
+                check_scipy(As, None, got, square=True)
+                check_exact(As, None, got, sample_cols(k, 60, 4), square=True)
+                Us = sparse.csc_matrix(sparse.triu(As))
+                Us.sort_indices()
+                sym = ba.sp_colSumsSq_sym(Us.indptr, Us.indices, Us.data)
+                check_scipy(As, None, sym, square=True)
+            # a repeated index gives repeated values (the list is a mask)
+            rep = np.array([0, m2 - 1, 0, 0, m2 - 1])
+            got = ba.ld_scores_sfbm(sf, rep)
+            once = ba.ld_scores_sfbm(sf, np.array([0, m2 - 1]))
+            assert np.array_equal(got, once[[0, 1, 0, 0, 1]])
+
+
+def test_sp_colSumsSq_sym_equals_colsums_of_squares(ba):
+    """test-2-ld-scores.R:68-78 on random symmetric matrices"""
+    for seed, (n, dens) in enumerate([(50, 0.3), (300, 0.05), (1000, 0.01)]):
+        R = sparse.random(n, n, density=dens, random_state=np.random.RandomState(seed), format="csc")
+        S = sparse.csc_matrix(R + R.T)
+        S.sort_indices()
+        Us = sparse.csc_matrix(sparse.triu(S))
+        Us.sort_indices()
+        got = ba.sp_colSumsSq_sym(Us.indptr, Us.indices, Us.data)
+        check_scipy(S, None, got, square=True)
+        check_exact(S, None, got, sample_cols(n, 100, 6), square=True)
+
+
+def check_solve(M, b, d, sol, tol):
+    """the three assertions on a solve of (A + diag(d)) x = b, A the full matrix of M"""
+    A = full_of(M)
+    n = b.size
+    x = np.asarray(sol)
+    assert sol.iters >= 1 and sol.relres <= tol
+    # 1. the residual recomputed here in fp64.  Both this and the device's t = (A + D) x obey the product bound with one term
+    # more (the diagonal shift): e_j = (L_j + 2) u (|A + D| |x|)_j each; b - t adds u |r_j| each, and a norm of n terms
+    # (n + 2) u relative.  So | ||r_host|| - ||r_gpu|| | <= 2 ||e + u |r| || + (n + 2) u (||r_host|| + ||r_gpu||).
+    Md = sparse.csc_matrix(A + sparse.diags(d))
+    r = b - Md @ x
+    relres_host = np.linalg.norm(r) / np.linalg.norm(b)
+    e = (np.diff(A.indptr) + 2) * U * (abs(Md) @ np.abs(x)) + U * np.abs(r)
+    slack = 2 * np.linalg.norm(e) / np.linalg.norm(b) + (n + 2) * U * (relres_host + sol.relres)
+    print("iters %d, relres device %.3e host %.3e (allowed difference %.3e)" % (sol.iters, sol.relres, relres_host, slack))
+    assert abs(relres_host - sol.relres) <= slack
+    # 2. against the dense solve: x - x_dense = (A + D)^-1 (r_dense - r_gpu)
+    dense = Md.toarray()
+    x_dense = np.linalg.solve(dense, b)
+    relres_dense = np.linalg.norm(b - dense @ x_dense) / np.linalg.norm(b)
+    cond = np.linalg.cond(dense)
+    err = np.linalg.norm(x - x_dense) / np.linalg.norm(x_dense)
+    print("cond2 %.4g, relres dense %.3e, ||x - x_dense|| / ||x_dense|| = %.3e" % (cond, relres_dense, err))
+    assert err <= cond * (sol.relres + relres_dense)
+    return x_dense, cond, relres_dense
+
+
+def _inf_system(df, m2, h2):
+    beta, beta_se, N = (np.asarray(df[k], dtype=np.float64) for k in ("beta", "beta_se", "n_eff"))
+    scale = np.sqrt(N * beta_se ** 2 + beta ** 2)
+    return beta / scale, m2 / (h2 * N), scale
+
+
+def test_solve_positive_definite(ba, data, cors):
+    corr = cors[40]
+    m2 = corr.Dim[1]
+    b, d, _ = _inf_system(data[2], m2, 0.3)
+    A = full_of(corr)
+    assert np.linalg.eigvalsh((A + sparse.diags(d)).toarray())[0] > 0
+    with ba.as_SFBM(corr) as sf:
+        sol = ba.sp_solve_sym(sf, b, add_to_diag=d)
+        check_solve(corr, b, d, sol, 1e-10)
+        # a subset, unsorted: as if run on corr[sub, sub]
+        sub = np.random.default_rng(1).choice(m2, 1200, replace=False)
+        sol = ba.sp_solve_sym(sf, b[sub], add_to_diag=d[sub], ind_corr=sub)
+        check_solve(A[sub][:, sub], b[sub], d[sub], sol, 1e-10)
+
+
+def test_solve_indefinite(ba):
+    A = chain_corr(500, 0.9)
+    d = np.full(500, 0.01)
+    ev = np.linalg.eigvalsh((A + sparse.diags(d)).toarray())
+    print("spectrum %.4f .. %.4f, closest to zero %.3e" % (ev[0], ev[-1], np.min(np.abs(ev))))
+    assert ev[0] < 0 < ev[-1]                 # both signs: the case cannot silently turn definite
+    b = np.random.default_rng(0).normal(size=500)
+    sol = ba.sp_solve_sym(A, b, add_to_diag=0.01)
+    check_solve(A, b, d, sol, 1e-10)
+    # a tolerance near what fp64 leaves of the recurrence's own estimate: whatever the solver does about the gap between that
+    # estimate and the true residual (it starts again from the true residual), a call that returns has relres <= tol
+    sol = ba.sp_solve_sym(A, b, add_to_diag=0.01, tol=1e-14)
+    check_solve(A, b, d, sol, 1e-14)
+
+
+def test_not_converged_names_iterations_and_residual(ba, cors):
+    corr = cors[100]
+    m2 = corr.Dim[1]
+    b = np.random.default_rng(2).normal(size=m2)
+    with ba.as_SFBM(corr) as sf:
+        with pytest.raises(ba.BsnError, match=r"not converged after 2 iterations: relative residual [0-9.]+e[-+][0-9]+"):
+            ba.sp_solve_sym(sf, b, add_to_diag=0.001, maxiter=2)
+        # the handle works on
+        sol = ba.sp_solve_sym(sf, b, add_to_diag=1.0)
+        assert sol.relres <= 1e-10 and sol.iters > 2
+        check_scipy(full_of(corr), b, ba.sp_prodVec(sf, b))
+
+
+def test_pipeline_ldsc_and_ldpred2_inf(ba, data, cors):
+    gb, keep, df, G = data
+    corr = cors[40]
+    m2 = corr.Dim[1]
+    beta, beta_se, n_eff = (np.asarray(df[k]) for k in ("beta", "beta_se", "n_eff"))
+    chi2 = (beta / beta_se) ** 2
+    with ba.as_SFBM(corr) as sf:
+        ld = ba.ld_scores_sfbm(sf)
+        # test-8-LDpred2.R:41-44
+        a = ba.snp_ldsc2(sf, df, intercept=None)
+        e = ba.snp_ldsc(ld, m2, chi2, n_eff, blocks=None)
+        assert list(a) == ["int", "h2"] and a == e
+        a = ba.snp_ldsc2(sf, df, blocks=20, intercept=None)
+        e = ba.snp_ldsc(ld, m2, chi2, n_eff, blocks=20)
+        assert list(a) == ["int", "int_se", "h2", "h2_se"] and a == e
+        assert ba.snp_ldsc2(corr, df, intercept=None) == ba.snp_ldsc2(sf, df, intercept=None)
+        # test-8-LDpred2.R:302-307
+        ind = np.random.default_rng(3).choice(m2, m2 // 2, replace=False)
+        dsub = {k: np.asarray(v)[ind] for k, v in df.items()}
+        a = ba.snp_ldsc2(sf, dsub, ind_beta=ind)
+        e = ba.snp_ldsc(ld[ind], m2, chi2[ind], n_eff[ind], blocks=None, intercept=1)
+        assert a == e and a["int"] == 1
+        # LDpred2-inf against the dense pipeline
+        h2 = 0.3
+        b, d, scale = _inf_system(df, m2, h2)
+        beta_inf = ba.snp_ldpred2_inf(sf, df, h2)
+        assert np.array_equal(ba.snp_ldpred2_inf(sf, df, h2), beta_inf)          # test-8-LDpred2.R:166-168
+        sol = ba.sp_solve_sym(sf, b, add_to_diag=d)
+        assert np.array_equal(np.asarray(sol) * scale, beta_inf)
+        x_dense, cond, relres_dense = check_solve(corr, b, d, sol, 1e-10)
+    beta_dense = x_dense * scale
+    # ||x scale - x_dense scale|| <= max(scale) ||x - x_dense||, whose bound check_solve has just asserted
+    bound = np.max(scale) * cond * (sol.relres + relres_dense) * np.linalg.norm(x_dense)
+    assert np.linalg.norm(beta_inf - beta_dense) <= bound
+    # the score: G (beta_inf - beta_dense) is at most ||G||_2 times that bound
+    score = ba.bed_prodVec(gb, beta_inf, ind_col=keep)
+    score_dense = G @ beta_dense
+    print("||score - score_dense|| = %.3e, ||G||_2 x bound = %.3e" % (np.linalg.norm(score - score_dense),
+                                                                     np.linalg.norm(G, 2) * bound))
+    assert np.linalg.norm(score - score_dense) <= np.linalg.norm(G, 2) * bound
