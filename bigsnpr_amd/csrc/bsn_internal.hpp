@@ -17,9 +17,9 @@
 
 namespace bsn {
 // Switches that only exist in the PROFILING build (python -m bigsnpr_amd.build --ablation, libbigsnpr_hip_abl.so): experiments
-// whose records are under profiles/ (BSN_ZQ_SPLIT, BSN_START_SLICES, BSN_LD_NOFUSE, BSN_LD_NO_SHARED_DECODE,
-// BSN_TCROSS_WAVES) beside BSN_TUNE / BSN_KY / BSN_KY_T / BSN_NB3 / BSN_DIGITS.  The product library does not read them
-// (README.md lists the switches it does read).
+// whose records are under profiles/ (BSN_ZQ_SPLIT, BSN_START_SLICES, BSN_TCROSS_WAVES, BSN_TCROSS_PRIO) beside BSN_TUNE /
+// BSN_KY / BSN_KY_T / BSN_NB3 / BSN_DIGITS.  The product library does not read them (README.md lists the switches it does
+// read).  The windowed LD (ld.hip) has none left: DESIGN.md 3.6 says what its seven measured and where the records are.
 inline const char *abl_getenv(const char *name) {
 #ifdef BSN_ABLATION
   return getenv(name);

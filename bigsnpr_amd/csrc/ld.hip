@@ -14,13 +14,12 @@
 // reference's operation order on identical integer inputs.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <unordered_map>
-
-#include <cstdlib>
-
-#include <cstring>
 #include "bsn_internal.hpp"
+#include "ld_plan.hpp"
 
 namespace bsn {
 
@@ -103,15 +102,15 @@ struct BandOut {
 // row = variant of tile I (the "x" / j0 side), col = variant of tile J (the "y" / j side).
 // rowmask (optional): 2 bits per sample, 11 = keep; dropped samples are turned into code 11
 // (missing) so that they vanish from all six sums.
-// ALL = false: only product 0 (xy) is computed and stored — the case of variants without missing
-// values among the selected samples, where the other five sums are per-variant constants.
+// (Variants without missing values among the selected samples need product 0 alone — the other five sums are
+// per-variant constants: k_pair_xy64 / k_pair_xy_f4.)
 // FUSE: the whole sample range is in this workgroup (no K split), so the six sums of a pair sit in
 // one lane's accumulators and the fp64 epilogue runs right here: the band entry is written, the
 // int32 statistics never leave the registers.
 // CONTIG: the variants of a tile lie within 2 GB of its first one (a contiguous ind.col): the genotype loads are
 // buffer loads with one scalar descriptor per operand tile and a 32-bit lane offset instead of four 64-bit lane
 // addresses — the four registers that decide between two and three waves per SIMD (168 registers).
-template <bool ALL, bool FUSE, bool CONTIG = false>
+template <bool FUSE, bool CONTIG = false>
 __global__ __launch_bounds__(256) void k_pair_stats(const uint8_t *__restrict__ img, int64_t pitch,
                                                     const int32_t *__restrict__ cols,
                                                     const int2 *__restrict__ pairs,
@@ -139,14 +138,13 @@ __global__ __launch_bounds__(256) void k_pair_stats(const uint8_t *__restrict__ 
   int64_t b0 = (int64_t)blockIdx.y * kbytes_per_split, b1 = b0 + kbytes_per_split;
   if (b1 > pitch) b1 = pitch;
 
-  constexpr int NP = ALL ? 6 : 1;
-  v4i acc[2][2][NP];
+  v4i acc[2][2][6];
 #pragma unroll
   for (int i = 0; i < 2; i++)
 #pragma unroll
     for (int j = 0; j < 2; j++)
 #pragma unroll
-      for (int p = 0; p < NP; p++) acc[i][j][p] = v4i{0, 0, 0, 0};
+      for (int p = 0; p < 6; p++) acc[i][j][p] = v4i{0, 0, 0, 0};
 
   for (int64_t kb = b0; kb < b1; kb += 64) {  // 64 B per row = 256 samples per iteration
     uint4 a[2], b[2];
@@ -182,17 +180,15 @@ __global__ __launch_bounds__(256) void k_pair_stats(const uint8_t *__restrict__ 
 #pragma unroll
         for (int j = 0; j < 2; j++) {
           acc[i][j][0] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].x, B[j].x, acc[i][j][0], 0, 0, 0);
-          if constexpr (ALL) {
-            acc[i][j][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].x, B[j].m, acc[i][j][1], 0, 0, 0);
-            acc[i][j][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].x2, B[j].m, acc[i][j][2], 0, 0, 0);
-            acc[i][j][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].x, acc[i][j][3], 0, 0, 0);
-            acc[i][j][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].x2, acc[i][j][4], 0, 0, 0);
-            acc[i][j][5] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].m, acc[i][j][5], 0, 0, 0);
-          }
+          acc[i][j][1] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].x, B[j].m, acc[i][j][1], 0, 0, 0);
+          acc[i][j][2] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].x2, B[j].m, acc[i][j][2], 0, 0, 0);
+          acc[i][j][3] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].x, acc[i][j][3], 0, 0, 0);
+          acc[i][j][4] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].x2, acc[i][j][4], 0, 0, 0);
+          acc[i][j][5] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, B[j].m, acc[i][j][5], 0, 0, 0);
         }
     }
   }
-  if constexpr (FUSE && ALL) {
+  if constexpr (FUSE) {
     // The sixteen pairs of a lane go through the fp64 epilogue ONE AT A TIME in a rolled loop: their sums are
     // parked in a run-time-indexed private array (scratch memory, written once, read once).  Unrolled, the
     // sixteen inlined epilogues raised the register allocation of the WHOLE kernel from 168 to 224 — two waves
@@ -224,7 +220,7 @@ __global__ __launch_bounds__(256) void k_pair_stats(const uint8_t *__restrict__ 
 #pragma unroll
     for (int j = 0; j < 2; j++)
 #pragma unroll
-      for (int p = 0; p < NP; p++)
+      for (int p = 0; p < 6; p++)
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int row = wr * 32 + i * 16 + 4 * g + r, col = wc * 32 + j * 16 + r16;
@@ -250,8 +246,8 @@ constexpr int TR = 128, TC = 32;
 // (Round 4: an explicit MFMA : VALU schedule through __builtin_amdgcn_sched_group_barrier, as in k_cprod — 1 or 2 VALU
 // offered behind every MFMA, the column operand's decode pulled into the last K-step — needs 210 registers, and forced
 // back to 168 for the third wave it runs 422 - 434 ms against 292 at C5: profiles/r04_ld.txt.  Not kept.)
-// PRIO (round 6, second session): s_setprio around the matrix instructions of a K-step, as in k_pair_stats_f4 (profiles/r06_ld_raw.txt).
-template <int PRIO = 0>
+// (Round 6, second session: s_setprio around the matrix instructions of a K-step, as in k_pair_stats_f4 — with it the compiler
+// needs 174 registers, two waves per SIMD, and the kernel is 11 % slower: profiles/r06_ld_raw.txt.  Not kept.)
 __global__ __launch_bounds__(256, 2) void k_pair_stats_b(const uint8_t *__restrict__ img, int64_t pitch,
                                                       const int32_t *__restrict__ cols,
                                                       const int2 *__restrict__ pairs,
@@ -322,7 +318,6 @@ __global__ __launch_bounds__(256, 2) void k_pair_stats_b(const uint8_t *__restri
         const uint32_t wa = d == 0 ? a[s].x : d == 1 ? a[s].y : d == 2 ? a[s].z : a[s].w;
         A[s] = decode3(wa | ~mw);
       }
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO);
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const uint4 bx = sB[buf][d][j][0][lane], bx2 = sB[buf][d][j][1][lane], bm = sB[buf][d][j][2][lane];
@@ -338,7 +333,6 @@ __global__ __launch_bounds__(256, 2) void k_pair_stats_b(const uint8_t *__restri
           acc[i][j][5] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[i].m, Bm, acc[i][j][5], 0, 0, 0);
         }
       }
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
     }
     // (Placing this decode between the K-steps above, where the matrix pipe is busy, costs 24 registers — two
     // waves per SIMD instead of three — and 12 % of the time: measured.)
@@ -442,9 +436,9 @@ __device__ __forceinline__ v4f mfma_f4(const v4i &a, const v4i &b, const v4f &c)
 // decoded (a third of the matrix instructions and of the look-ups; their accumulators are not allocated).
 // MASK = false (RAW only): every sample of the image is selected — pad samples are code 0 in the image, and code 0 adds nothing
 // to any of the six raw products (c = H = M = 0), so the keep-mask is neither loaded nor ORed in (npos = n then).
-// PRIO > 0: s_setprio(PRIO) around the matrix instructions of a K-step (with their LDS reads), 0 again for the decode — a wave that
+// s_setprio(2) around the matrix instructions of a K-step (with their LDS reads), 0 again for the decode — a wave that
 // has its operands ready is issued ahead of the waves that are still decoding (measured: profiles/r06_ld_raw.txt).
-template <bool SQ, bool RAW = false, bool MASK = true, int PRIO = 0>
+template <bool SQ, bool RAW = false, bool MASK = true>
 __global__ __launch_bounds__(256, SQ ? 3 : 4) void k_pair_stats_f4(const uint8_t *__restrict__ img, int64_t pitch,
                                                        const int32_t *__restrict__ cols,
                                                        const int2 *__restrict__ pairs,
@@ -506,7 +500,7 @@ __global__ __launch_bounds__(256, SQ ? 3 : 4) void k_pair_stats_f4(const uint8_t
       for (int s = 0; s < 2; s++)
         A[s] = RAW ? decode_f4_raw((d == 0 ? a[s].x : a[s].z) | ~m0, (d == 0 ? a[s].y : a[s].w) | ~m1, SQ)
                    : decode_f4((d == 0 ? a[s].x : a[s].z) | ~m0, (d == 0 ? a[s].y : a[s].w) | ~m1);
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO);
+      __builtin_amdgcn_s_setprio(2);
 #pragma unroll
       for (int j = 0; j < 2; j++) {
         const uint4 bx = sB[buf][d][j][0][lane], bm = sB[buf][d][j][2][lane];
@@ -524,7 +518,7 @@ __global__ __launch_bounds__(256, SQ ? 3 : 4) void k_pair_stats_f4(const uint8_t
           acc[i][j][5] = mfma_f4(A[i].m, Bm, acc[i][j][5]);
         }
       }
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
     }
     stash(buf ^ 1, bn, mkn);
     __syncthreads();
@@ -769,7 +763,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 struct QuadXY {
   int t[4], p[4];
 };
-template <bool MASK, int PRIO = 0>
+template <bool MASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_quad_xy_f4(const uint8_t *__restrict__ img, int64_t pitch,
                                                                                               const int32_t *__restrict__ cols,
                                                                                               const QuadXY *__restrict__ quads,
@@ -827,9 +821,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
           A[s] = nib(d == 0 ? a[s].x : a[s].z, d == 0 ? a[s].y : a[s].w);                               \
           B[s] = nib(d == 0 ? b[s].x : b[s].z, d == 0 ? b[s].y : b[s].w);                               \
         }                                                                                               \
-        if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO);                                         \
         _Pragma("unroll") for (int i = 0; i < 4; i++) _Pragma("unroll") for (int j = 0; j < 4; j++) acc[i][j] = mfma_f4(A[i], B[j], acc[i][j]); \
-        if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);                                            \
       }                                                                                                 \
     }                                                                                                   \
   }
@@ -1214,7 +1206,7 @@ __global__ void k_band_gt_upper(const double *__restrict__ band, const int64_t *
 // what bench.py --workload ld reports: set by every band_run
 struct LdStats {
   double pairs = 0, tile_pairs = 0, stats_ms = 0, launches = 0;
-  int kernel = 0;  // 0: six-product kernel with fused epilogue, 1: six-product + K split, 2: cross product only, 3: byte image with missing values (eight products), 4: six products, column operand decoded once per workgroup (LDS)
+  int kernel = 0;  // an LdKernel (ld_plan.hpp)
 };
 static LdStats g_ld_stats;
 
@@ -1231,7 +1223,6 @@ struct BandJob {
   DevBuf<double> d_cnn;     // 2-bit image: non-missing count per variant over the selected samples (raw-plane kernel)
   DevBuf<long long> d_stats64;
   bool complete = false;  // no missing value among the selected samples of the selected variants
-  bool use_mask = false;
   bool all_rows = false;  // every sample of the image is selected (2-bit image)
   bool contig = false;    // every tile's variants lie within 2 GB of its first one, in ascending order
   int64_t npairs = 0, npairs_b = 0;
@@ -1352,13 +1343,11 @@ static void band_stats(BandJob &J, bsn_bed *bed, const int64_t *ind_row, int64_t
     }
     copy_h2d(bed, J.d_nna.ensure((size_t)m), nna.data(), (size_t)m * 8);
     J.complete = na_total == 0;
-    J.use_mask = true;
     copy_h2d(bed, J.d_cx.ensure((size_t)m), cx.data(), (size_t)m * 8);
     copy_h2d(bed, J.d_cxx.ensure((size_t)m), cxx.data(), (size_t)m * 8);
   } else {
     // rows: keep-mask, 2 bits per sample (also removes the pad samples, which are coded as
     // non-missing genotype 0 in the image).  Lists with repeated samples never get here (row_view).
-    J.use_mask = true;
     {
       std::vector<uint32_t> mask((size_t)(bed->pitch / 4), 0u);
       for (int64_t i = 0; i < n; i++) {
@@ -1425,326 +1414,255 @@ static void band_stats(BandJob &J, bsn_bed *bed, const int64_t *ind_row, int64_t
   J.d_band.ensure((size_t)std::min<int64_t>(J.chunk_cols, (m + TR - 1) / TR * TR) * (size_t)W);
 }
 
+// HIP events around the statistics launches of one band_run — begin, end, begin, end, ... on the one stream — read after the
+// last launch and destroyed with the object, whatever throws in between
+class LaunchTimer {
+  hipStream_t stream_;
+  std::vector<hipEvent_t> ev_;
+ public:
+  explicit LaunchTimer(hipStream_t s) : stream_(s) {}
+  LaunchTimer(const LaunchTimer &) = delete;
+  ~LaunchTimer() { for (hipEvent_t e : ev_) (void)hipEventDestroy(e); }
+  void begin() {
+    hipEvent_t e = nullptr;
+    BSN_HIP(hipEventCreate(&e));
+    ev_.push_back(e);
+    BSN_HIP(hipEventRecord(e, stream_));
+  }
+  void end() {   // after the launch: its error, if any, is reported here
+    BSN_HIP(hipGetLastError());
+    begin();
+  }
+  double launches() const { return (double)(ev_.size() / 2); }
+  float total_ms() {   // waits for the last end(): everything before it on the stream is done then
+    float total = 0.f, ms = 0.f;
+    if (!ev_.empty()) BSN_HIP(hipEventSynchronize(ev_.back()));
+    for (size_t t = 0; t + 1 < ev_.size(); t += 2, total += ms) BSN_HIP(hipEventElapsedTime(&ms, ev_[t], ev_[t + 1]));
+    return total;
+  }
+};
+
+// One band_run: the job, the decision, the epilogue's arguments (mode, thresholds, band) and the run [pA, pB) of tile pairs (of
+// 128 x 32 blocks: shared_decode) whose row variants lie in the block of columns — and the five paths, which only size scratch
+// and launch, all on bed->stream: that is what lets the batches of a path reuse one statistics buffer without a wait.
+struct BandRun {
+  BandJob &J;
+  bsn_bed *bed;
+  const BandPlan P;
+  BandOut bo;
+  int64_t pA, pB;
+  LaunchTimer tm;
+  LdKernel kernel;   // reported: the last batch decides
+  void byte_na(), byte_xy(), shared_decode(), xy(), small_band(), fill_band(int64_t p0, int64_t np);
+};
+constexpr int64_t kBatch = 4096;          // 4096 x 6 x 64 x 64 x 4 B = 403 MB of int32 statistics (two-stage paths only)
+constexpr int64_t kSliceBytes = 131072;   // byte image: samples per int32 accumulator slice
+// second stage of the two-stage paths of the 2-bit image
+void BandRun::fill_band(int64_t p0, int64_t np) {
+  hipLaunchKernelGGL(k_band_fill, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats.p, J.d_pairs.p + p0, (int)np, J.m,
+                     J.d_lo.p, J.W, bo.thr, bo.mode, bo.v1, bo.v2, bo.nrows, bo.band,
+                     J.complete ? J.d_cx.p : (const double *)nullptr, J.complete ? J.d_cxx.p : (const double *)nullptr);
+  BSN_HIP(hipGetLastError());
+}
+
+// byte image, missing values among the selected samples: the six pairwise-complete sums (eight int8 products)
+void BandRun::byte_na() {
+  const int nslice = (int)((bed->pitch + kSliceBytes - 1) / kSliceBytes);   // at most 6: band_run
+  const int64_t batch8 = 512;   // 512 x 8 x 64 x 64 x 8 B = 134 MB of int64 statistics
+  J.d_stats64.ensure((size_t)std::min(batch8, J.npairs) * 8 * TB * TB);
+  for (int64_t p0 = pA; p0 < pB; p0 += batch8) {
+    const int64_t np = std::min(batch8, pB - p0);
+    // enough workgroups to fill the chip; a split never crosses a 131 072-sample slice
+    int64_t ks = std::max<int64_t>(nslice, std::min<int64_t>(std::max<int64_t>(1, 4096 / (np * 4)), bed->pitch / 256));
+    const int64_t kb = std::min(round_up((bed->pitch + ks - 1) / ks, 64), kSliceBytes);
+    ks = (bed->pitch + kb - 1) / kb;
+    BSN_HIP(hipMemsetAsync(J.d_stats64.p, 0, (size_t)np * 8 * TB * TB * 8, bed->stream));
+    tm.begin();
+    hipLaunchKernelGGL(k_pair_stats8, dim3((unsigned)np, (unsigned)ks, 4), dim3(64), 0, bed->stream, bed->d_img,
+                       bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, kb, J.d_stats64.p);
+    tm.end();
+    hipLaunchKernelGGL(k_band_fill8na, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats64.p,
+                       J.d_pairs.p + p0, (int)np, J.m, J.d_lo.p, J.W, bo.thr, bo.mode, bo.nrows, bo.band);
+    BSN_HIP(hipGetLastError());
+  }
+}
+
+// byte image, cross product only
+void BandRun::byte_xy() {
+  const int nslice = (int)((bed->pitch + kSliceBytes - 1) / kSliceBytes);   // at most 6: band_run
+  J.d_stats.ensure((size_t)std::min(kBatch, J.npairs) * 6 * TB * TB);
+  for (int64_t p0 = pA; p0 < pB; p0 += kBatch) {
+    const int64_t np = std::min(kBatch, pB - p0);
+    // K splits never straddle a slice: one slice -> any 64-byte-aligned split of the row; several ->
+    // a power-of-two number of splits per 131 072-byte slice
+    const int64_t want = std::max<int64_t>(1, 8192 / (np * nslice));
+    KSplit ks{1, kSliceBytes};
+    if (nslice == 1) ks = k_split(bed->pitch, want, 64, 256);
+    else
+      while (ks.splits * 2 <= want && ks.splits < 512) ks.splits *= 2, ks.bytes /= 2;
+    BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
+    tm.begin();
+    hipLaunchKernelGGL(k_pair_xy8, dim3((unsigned)np, (unsigned)(ks.splits * nslice)), dim3(64), 0, bed->stream,
+                       bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, ks.bytes, ks.splits, J.d_stats.p);
+    tm.end();
+    hipLaunchKernelGGL(k_band_fill8, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats.p, nslice, J.d_pairs.p + p0,
+                       (int)np, J.m, J.d_lo.p, J.W, bo.thr, bo.mode, bo.v1, bo.v2, bo.nrows, bo.band, J.d_cx.p,
+                       J.d_cxx.p, bed->v_step, bed->v_off, J.complete ? (const double *)nullptr : J.d_nna.p);
+    BSN_HIP(hipGetLastError());
+  }
+}
+
+// enough blocks to fill the chip without a K split: the kernels that share the column operand's decode.
+// (round 6, second session) ONE launch for the whole run: the fused epilogue needs no scratch, every block walks the same
+// sample range (equal work), and a launch of 4 096 blocks on 768 resident workgroups ended with a round that was a third
+// full — 13 such tails at C5 (profiles/r06_ld_raw.txt)
+void BandRun::shared_decode() {
+  const bool sq = bo.mode != (int)LdMode::clump_bed;   // the bed clumping formula reads four of the six sums
+  if (P.raw) bo.cx = J.d_cx.p, bo.cxx = J.d_cxx.p, bo.cnn = J.d_cnn.p, bo.npos = P.nomask ? (double)bed->n : (double)(bed->pitch * 4);
+#define BSN_LAUNCH(...) \
+  hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)(pB - pA)), dim3(256), 0, bed->stream, bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs_b.p + pA, J.d_mask.p, bo)
+  tm.begin();
+  if (!P.f4) BSN_LAUNCH(k_pair_stats_b);
+  else if (!P.raw && sq) BSN_LAUNCH(k_pair_stats_f4<true, false, true>);
+  else if (!P.raw) BSN_LAUNCH(k_pair_stats_f4<false, false, true>);
+  else if (sq && P.nomask) BSN_LAUNCH(k_pair_stats_f4<true, true, false>);
+  else if (sq) BSN_LAUNCH(k_pair_stats_f4<true, true, true>);
+  else if (P.nomask) BSN_LAUNCH(k_pair_stats_f4<false, true, false>);
+  else BSN_LAUNCH(k_pair_stats_f4<false, true, true>);
+#undef BSN_LAUNCH
+  tm.end();
+}
+
+// the 2 x 2 blocks of the tile pairs [pA, pB), batch by batch (k_quad_xy_f4); quad_off[b] = first block of batch b (+ end).
+// Batches of fewer than 64 pairs get none (xy_kernel).
+static void group_quads(const BandJob &J, int64_t pA, int64_t pB, std::vector<QuadXY> &quads, std::vector<int64_t> &quad_off) {
+  std::unordered_map<uint64_t, int> at;
+  const int mt = (int)((J.m + TB - 1) / TB);
+  for (int64_t p0 = pA; p0 < pB; p0 += kBatch) {
+    const int64_t np = std::min(kBatch, pB - p0);
+    quad_off.push_back((int64_t)quads.size());
+    if (np < 64) continue;
+    at.clear();
+    const int64_t base = (int64_t)quads.size();
+    for (int64_t p = p0; p < p0 + np; p++) {
+      const int I = J.pairs_host[(size_t)p].x, Jt = J.pairs_host[(size_t)p].y;
+      const uint64_t key = ((uint64_t)(uint32_t)(I >> 1) << 32) | (uint32_t)(Jt >> 1);
+      auto it = at.find(key);
+      if (it == at.end()) {
+        QuadXY qd;
+        qd.t[0] = (I >> 1) * 2;
+        qd.t[1] = std::min(qd.t[0] + 1, mt - 1);
+        qd.t[2] = (Jt >> 1) * 2;
+        qd.t[3] = std::min(qd.t[2] + 1, mt - 1);
+        qd.p[0] = qd.p[1] = qd.p[2] = qd.p[3] = -1;
+        it = at.emplace(key, (int)((int64_t)quads.size() - base)).first;
+        quads.push_back(qd);
+      }
+      quads[(size_t)(base + it->second)].p[(I & 1) * 2 + (Jt & 1)] = (int)(p - p0);
+    }
+  }
+  quad_off.push_back((int64_t)quads.size());
+}
+
+// 2-bit image, cross product only: K-split partial sums into the statistics buffer, then k_band_fill.
+// (round 6) nothing in this loop waits for the device: the 2 x 2 blocks of tile pairs of ALL batches are grouped and uploaded
+// once, every batch has its own pair of events, and the host reads them after the last launch (a batch used to end with an
+// event wait and its own grouping + upload; measured at a million variants, same box: no difference — the band-fill kernel
+// of a batch covered the host's preparation of the next — kept because it is the simpler order of events)
+void BandRun::xy() {
+  std::vector<QuadXY> quads;
+  std::vector<int64_t> quad_off;
+  if (P.quad_all) group_quads(J, pA, pB, quads, quad_off);
+  if (!quads.empty()) {
+    copy_h2d(bed, J.d_quads.ensure(quads.size()), quads.data(), quads.size() * sizeof(QuadXY));
+    BSN_HIP(hipStreamSynchronize(bed->stream));   // (quads is a host vector)
+  }
+  J.d_stats.ensure((size_t)std::min(kBatch, J.npairs) * 6 * TB * TB);
+  int64_t ib = 0;
+  for (int64_t p0 = pA; p0 < pB; p0 += kBatch, ib++) {
+    const int64_t np = std::min(kBatch, pB - p0);
+    BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
+    tm.begin();
+#define BSN_LAUNCH(KERNEL, NX, THREADS, WORK) \
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)(NX), (unsigned)ks.splits), dim3(THREADS), 0, bed->stream, bed->d_img, bed->pitch, J.d_cols.p, WORK, J.d_mask.p, ks.bytes, J.d_stats.p)
+    if ((kernel = xy_kernel(P, np)) == kLdQuadF4) {
+      const int64_t nq = quad_off[(size_t)ib + 1] - quad_off[(size_t)ib];
+      const QuadXY *d_q = J.d_quads.p + quad_off[(size_t)ib];
+      const KSplit ks = k_split(bed->pitch, std::max<int64_t>(1, 4096 / nq), 128, 1024);
+      if (P.nomask) BSN_LAUNCH(k_quad_xy_f4<false>, nq, 256, d_q);
+      else BSN_LAUNCH(k_quad_xy_f4<true>, nq, 256, d_q);
+    } else {
+      // one wave per workgroup here: four times the K splits of the 4-wave kernel (k_pair_xy_f4 walks whole cache lines)
+      const KSplit ks = k_split(bed->pitch, std::max<int64_t>(4, 8192 / np), 128, 256);
+      if (!P.f4) BSN_LAUNCH(k_pair_xy64, np, 64, J.d_pairs.p + p0);
+      else if (P.nomask) BSN_LAUNCH(k_pair_xy_f4<false>, np, 64, J.d_pairs.p + p0);
+      else BSN_LAUNCH(k_pair_xy_f4<true>, np, 64, J.d_pairs.p + p0);
+    }
+#undef BSN_LAUNCH
+    tm.end();
+    fill_band(p0, np);
+  }
+}
+
+// 2-bit image, six sums, too few blocks for shared_decode: k_pair_stats on 64 x 64 tile pairs, with its fused epilogue
+// when a batch needs no K split, else through the statistics buffer and k_band_fill.  No wait inside the loop either.
+void BandRun::small_band() {
+  for (int64_t p0 = pA; p0 < pB; p0 += kBatch) {
+    const int64_t np = std::min(kBatch, pB - p0);
+    // K split: enough workgroups to fill the chip when there are few tile pairs
+    const KSplit ks = k_split(bed->pitch, std::max<int64_t>(1, 2048 / np), 64, 256);
+    const bool fused = (kernel = small_band_kernel(ks.splits)) == kLdSixFused;
+    if (!fused) {
+      J.d_stats.ensure((size_t)std::min(kBatch, J.npairs) * 6 * TB * TB);
+      BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
+    }
+    tm.begin();
+#define BSN_LAUNCH(KERNEL, STATS, ATOMIC) \
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)np, (unsigned)ks.splits), dim3(256), 0, bed->stream, bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask.p, ks.bytes, STATS, ATOMIC, bo)
+    if (!fused) BSN_LAUNCH((k_pair_stats<false, false>), J.d_stats.p, 1);
+    else if (J.contig) BSN_LAUNCH((k_pair_stats<true, true>), (int32_t *)nullptr, 0);
+    else BSN_LAUNCH((k_pair_stats<true, false>), (int32_t *)nullptr, 0);
+#undef BSN_LAUNCH
+    tm.end();
+    if (!fused) fill_band(p0, np);
+  }
+}
+
 // runs the statistics + band fill in batches; mode / aux as in pair_value
 // Columns [c0, c1) of the band (c0 a multiple of 128; the whole band by default) go to J.d_band, whose first column
 // is then c0.  `accumulate`: add to the statistics of the previous block instead of starting them.
-static void band_run(BandJob &J, int mode, const double *d_thr, const double *d_v1, const double *d_v2,
+// Which kernel: plan_band (ld_plan.hpp; the table is in DESIGN.md, 3.6).  The three switches are read on every call.
+static void band_run(BandJob &J, LdMode mode, const double *d_thr, const double *d_v1, const double *d_v2,
                      double nrows, int64_t c0 = 0, int64_t c1 = -1, bool accumulate = false) {
   bsn_bed *bed = J.bed;
   if (c1 < 0 || c1 > J.m) c1 = J.m;
   if (c0 % TR != 0 || c1 - c0 > J.chunk_cols) fail("internal: LD band block [%lld, %lld)", (long long)c0, (long long)c1);
-  const int64_t batch = 4096;  // 4096 x 6 x 64 x 64 x 4 B = 403 MB of int32 statistics (two-stage paths only)
-  const bool xy_only = J.complete || mode == 2;  // FBM clumping (mode 2) reads the cross product only (src/clumping.cpp:66-73)
+  if (bed->bits == 8 && mode == LdMode::clump_bed) fail("internal: the bed clumping formula does not apply to a byte image");
+  if (bed->bits == 8 && bed->pitch > 6 * kSliceBytes) fail("windowed LD on a dosage FBM supports at most %lld samples", (long long)(6 * kSliceBytes));
+  BandFacts f;
+  f.bits = bed->bits, f.pitch = bed->pitch, f.n = bed->n, f.mode = mode;
+  f.complete = J.complete, f.contig = J.contig, f.all_rows = J.all_rows, f.have_cnn = J.d_cnn.p != nullptr, f.npairs_b = J.npairs_b;
+  f.i8 = getenv("BSN_LD_I8") != nullptr, f.lut = getenv("BSN_LD_LUT") != nullptr, f.no_quad = getenv("BSN_LD_NO_QUAD") != nullptr;
+  const BandPlan plan = plan_band(f);
   // the tile pairs whose row variants (the j0 side) lie in the block: a contiguous run of both pair lists
   const int64_t pA = J.pair_start[(size_t)(c0 / TB)], pB = J.pair_start[(size_t)((c1 + TB - 1) / TB)];
   const int64_t qA = J.pairb_start[(size_t)(c0 / TR)], qB = J.pairb_start[(size_t)((c1 + TR - 1) / TR)];
-  LdStats ls;
-  if (accumulate) ls = g_ld_stats;
-  ls.tile_pairs += (double)(pB - pA);
+  const bool blocks = plan.path == LdPath::shared_decode;   // blocks of 128 x 32 = the area of a 64 x 64 tile pair
+  BandRun R{J, bed, plan, BandOut{J.m, J.W, J.d_lo.p, d_thr, d_v1, d_v2, nrows, J.band_at(c0), (int)mode},
+            blocks ? qA : pA, blocks ? qB : pB, LaunchTimer(bed->stream), plan.kernel};
+  switch (plan.path) {
+    case LdPath::byte_na: R.byte_na(); break;
+    case LdPath::byte_xy: R.byte_xy(); break;
+    case LdPath::shared_decode: R.shared_decode(); break;
+    case LdPath::xy: R.xy(); break;
+    case LdPath::small_band: R.small_band(); break;
+  }
+  LdStats ls = accumulate ? g_ld_stats : LdStats();
+  ls.tile_pairs += (double)(R.pB - R.pA);
   for (int64_t j0 = c0; j0 < c1; j0++) ls.pairs += (double)(j0 - J.lo[(size_t)j0]);
-  hipEvent_t e0, e1;
-  BSN_HIP(hipEventCreate(&e0));
-  BSN_HIP(hipEventCreate(&e1));
-  float ms_total = accumulate ? (float)g_ld_stats.stats_ms : 0.f;
-  double *const band = J.band_at(c0);
-  BandOut bo{J.m, J.W, J.d_lo.p, d_thr, d_v1, d_v2, nrows, band, mode};
-  if (bed->bits == 8) {
-    if (mode == 3) fail("internal: the bed clumping formula does not apply to a byte image");
-    const int64_t slice_bytes = 131072;  // samples per int32 accumulator slice
-    const int nslice = (int)((bed->pitch + slice_bytes - 1) / slice_bytes);
-    if (nslice > 6) fail("windowed LD on a dosage FBM supports at most %lld samples", (long long)(6 * slice_bytes));
-    if (!J.complete && mode != 2) {
-      // missing values among the selected samples: the six pairwise-complete sums (eight int8 products)
-      const int64_t batch8 = 512;   // 512 x 8 x 64 x 64 x 8 B = 134 MB of int64 statistics
-      J.d_stats64.ensure((size_t)std::min(batch8, J.npairs) * 8 * TB * TB);
-      for (int64_t p0 = pA; p0 < pB; p0 += batch8) {
-        const int64_t np = std::min(batch8, pB - p0);
-        // enough workgroups to fill the chip; a split never crosses a 131 072-sample slice
-        int64_t ks = std::max<int64_t>(nslice, std::min<int64_t>(std::max<int64_t>(1, 4096 / (np * 4)), bed->pitch / 256));
-        int64_t kb = round_up((bed->pitch + ks - 1) / ks, 64);
-        if (kb > slice_bytes) kb = slice_bytes;
-        ks = (bed->pitch + kb - 1) / kb;
-        BSN_HIP(hipMemsetAsync(J.d_stats64.p, 0, (size_t)np * 8 * TB * TB * 8, bed->stream));
-        BSN_HIP(hipEventRecord(e0, bed->stream));
-        hipLaunchKernelGGL(k_pair_stats8, dim3((unsigned)np, (unsigned)ks, 4), dim3(64), 0, bed->stream, bed->d_img,
-                           bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, kb, J.d_stats64.p);
-        BSN_HIP(hipGetLastError());
-        BSN_HIP(hipEventRecord(e1, bed->stream));
-        hipLaunchKernelGGL(k_band_fill8na, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats64.p,
-                           J.d_pairs.p + p0, (int)np, J.m, J.d_lo.p, J.W, d_thr, mode, nrows, band);
-        BSN_HIP(hipGetLastError());
-        BSN_HIP(hipEventSynchronize(e1));
-        float ms = 0;
-        BSN_HIP(hipEventElapsedTime(&ms, e0, e1));
-        ms_total += ms;
-        ls.launches += 1;
-      }
-      ls.kernel = 3;   // byte image, eight products
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      ls.stats_ms = ms_total;
-      g_ld_stats = ls;
-      return;
-    }
-    J.d_stats.ensure((size_t)std::min(batch, J.npairs) * 6 * TB * TB);
-    for (int64_t p0 = pA; p0 < pB; p0 += batch) {
-      const int64_t np = std::min(batch, pB - p0);
-      // K splits never straddle a slice: one slice -> any 64-byte-aligned split of the row; several ->
-      // a power-of-two number of splits per 131 072-byte slice
-      const int64_t sl = std::min<int64_t>(slice_bytes, bed->pitch);
-      const int64_t want = std::max<int64_t>(1, 8192 / (np * nslice));
-      int sps;
-      int64_t kb;
-      if (nslice == 1) {
-        sps = (int)std::min<int64_t>(want, sl / 256);
-        if (sps < 1) sps = 1;
-        kb = round_up((sl + sps - 1) / sps, 64);
-        sps = (int)((sl + kb - 1) / kb);
-      } else {
-        sps = 1;
-        while (sps * 2 <= want && sps < 512) sps *= 2;
-        kb = sl / sps;
-      }
-      BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
-      BSN_HIP(hipEventRecord(e0, bed->stream));
-      hipLaunchKernelGGL(k_pair_xy8, dim3((unsigned)np, (unsigned)(sps * nslice)), dim3(64), 0, bed->stream,
-                         bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, kb, sps, J.d_stats.p);
-      BSN_HIP(hipGetLastError());
-      BSN_HIP(hipEventRecord(e1, bed->stream));
-      hipLaunchKernelGGL(k_band_fill8, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats.p, nslice,
-                         J.d_pairs.p + p0, (int)np, J.m, J.d_lo.p, J.W, d_thr, mode, d_v1, d_v2, nrows, band,
-                         J.d_cx.p, J.d_cxx.p, bed->v_step, bed->v_off, J.complete ? (const double *)nullptr : J.d_nna.p);
-      BSN_HIP(hipGetLastError());
-      BSN_HIP(hipEventSynchronize(e1));
-      float ms = 0;
-      BSN_HIP(hipEventElapsedTime(&ms, e0, e1));
-      ms_total += ms;
-      ls.launches += 1;
-    }
-    ls.kernel = 2;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    ls.stats_ms = ms_total;
-    g_ld_stats = ls;
-    return;
-  }
-  if (!xy_only && J.contig && J.use_mask && J.npairs_b >= 1024 && !abl_getenv("BSN_LD_NO_SHARED_DECODE")) {
-    // enough blocks to fill the chip without a K split: the kernel that shares the column operand's decode.
-    // (round 6, second session) ONE launch for the whole run: the fused epilogue needs no scratch, every block walks the same
-    // sample range (equal work), and a launch of 4 096 blocks on 768 resident workgroups ended with a round that was a third
-    // full — 13 such tails at C5 (BSN_LD_BATCH=<n> in the profiling build: blocks per launch, for the A/B)
-    int64_t fbatch = std::max<int64_t>(qB - qA, 1);
-    if (const char *e = abl_getenv("BSN_LD_BATCH")) fbatch = std::max<int64_t>(1, atoll(e));
-    for (int64_t p0 = qA; p0 < qB; p0 += fbatch) {
-      const int64_t np = std::min(fbatch, qB - p0);
-      BSN_HIP(hipEventRecord(e0, bed->stream));
-      // the FP4 matrix pipe while the sums stay exact in fp32 (at most 4 n < 2^24); BSN_LD_I8=1: the int8 kernel
-      static const bool i8_only = getenv("BSN_LD_I8") != nullptr;
-      const bool f4 = bed->pitch * 4 <= 4194303 && !i8_only;
-      // planes without look-ups while 9 n < 2^24 (BSN_LD_LUT=1: the look-up kernel, for the A/B)
-      static const bool lut_only = getenv("BSN_LD_LUT") != nullptr;
-      const bool raw = f4 && bed->pitch * 4 <= 1864135 && !lut_only && J.d_cnn.p != nullptr;
-      ls.kernel = f4 ? (mode == 3 ? 9 : 6) : 4;
-      if (raw) {
-        BandOut br = bo;
-        // every sample selected: no keep-mask (the pad samples are code 0 and add nothing to the raw products)
-        const bool nomask = J.all_rows && !abl_getenv("BSN_LD_RAW_MASK");
-        int prio = 2;   // (profiling build: BSN_LD_RAW_PRIO=0..3)
-        if (const char *e = abl_getenv("BSN_LD_RAW_PRIO")) prio = atoi(e);
-        (void)prio;
-        br.cx = J.d_cx.p, br.cxx = J.d_cxx.p, br.cnn = J.d_cnn.p, br.npos = nomask ? (double)bed->n : (double)(bed->pitch * 4);
-        ls.kernel = mode == 3 ? 11 : 10;
-#define BSN_LAUNCH_RAW(SQ_, MASK_, PRIO_)                                                                                      \
-  hipLaunchKernelGGL((k_pair_stats_f4<SQ_, true, MASK_, PRIO_>), dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, \
-                     bed->pitch, J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, br)
-#ifdef BSN_ABLATION
-#define BSN_LAUNCH_RAW_P(SQ_, MASK_)                  \
-  do {                                                \
-    if (prio == 0) BSN_LAUNCH_RAW(SQ_, MASK_, 0);     \
-    else if (prio == 1) BSN_LAUNCH_RAW(SQ_, MASK_, 1); \
-    else if (prio == 3) BSN_LAUNCH_RAW(SQ_, MASK_, 3); \
-    else BSN_LAUNCH_RAW(SQ_, MASK_, 2);               \
-  } while (0)
-#else
-#define BSN_LAUNCH_RAW_P(SQ_, MASK_) BSN_LAUNCH_RAW(SQ_, MASK_, 2)
-#endif
-        if (mode == 3) {
-          if (nomask) BSN_LAUNCH_RAW_P(false, false);
-          else BSN_LAUNCH_RAW_P(false, true);
-        } else {
-          if (nomask) BSN_LAUNCH_RAW_P(true, false);
-          else BSN_LAUNCH_RAW_P(true, true);
-        }
-#undef BSN_LAUNCH_RAW_P
-#undef BSN_LAUNCH_RAW
-      } else if (abl_getenv("BSN_LD_NOPRIO")) {   // (profiling build: the look-up / int8 kernels without the priority, for the A/B)
-        if (f4 && mode == 3)
-          hipLaunchKernelGGL(k_pair_stats_f4<false>, dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-        else if (f4)
-          hipLaunchKernelGGL(k_pair_stats_f4<true>, dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-        else
-          hipLaunchKernelGGL(k_pair_stats_b<0>, dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-      } else if (f4 && mode == 3)   // the bed clumping formula reads four of the six sums
-        hipLaunchKernelGGL((k_pair_stats_f4<false, false, true, 2>), dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                           J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-      else if (f4)
-        hipLaunchKernelGGL((k_pair_stats_f4<true, false, true, 2>), dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                           J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-      else   // (the int8 kernel without the priority: with it the compiler needs 174 registers — two waves per SIMD — and it is 11 % slower)
-        hipLaunchKernelGGL(k_pair_stats_b<0>, dim3((unsigned)np), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                           J.d_cols.p, J.d_pairs_b.p + p0, J.d_mask.p, bo);
-      BSN_HIP(hipGetLastError());
-      BSN_HIP(hipEventRecord(e1, bed->stream));
-      BSN_HIP(hipEventSynchronize(e1));
-      float ms = 0;
-      BSN_HIP(hipEventElapsedTime(&ms, e0, e1));
-      ms_total += ms;
-      ls.launches += 1;
-    }
-    ls.tile_pairs += (double)(qB - qA) - (double)(pB - pA);   // blocks of 128 x 32 = the area of a 64 x 64 tile pair
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    ls.stats_ms = ms_total;
-    g_ld_stats = ls;
-    return;
-  }
-  // (round 6) nothing in this loop waits for the device: the 2 x 2 blocks of tile pairs of ALL batches are grouped and uploaded
-  // once, every batch has its own pair of events, and the host reads them after the last launch (a batch used to end with an
-  // event wait and its own grouping + upload; measured at a million variants, same box: no difference — the band-fill kernel
-  // of a batch covered the host's preparation of the next — kept because it is the simpler order of events)
-  const bool xy_f4_all = xy_only && bed->bits == 2 && bed->n <= 4194303 && !getenv("BSN_LD_I8");
-  const bool quad_all = xy_f4_all && !getenv("BSN_LD_NO_QUAD");
-  std::vector<QuadXY> quads;
-  std::vector<int64_t> quad_off;
-  if (quad_all) {
-    std::unordered_map<uint64_t, int> at;
-    const int mt = (int)((J.m + TB - 1) / TB);
-    for (int64_t p0 = pA; p0 < pB; p0 += batch) {
-      const int64_t np = std::min(batch, pB - p0);
-      quad_off.push_back((int64_t)quads.size());
-      if (np < 64) continue;
-      at.clear();
-      const int64_t base = (int64_t)quads.size();
-      for (int64_t p = p0; p < p0 + np; p++) {
-        const int I = J.pairs_host[(size_t)p].x, Jt = J.pairs_host[(size_t)p].y;
-        const uint64_t key = ((uint64_t)(uint32_t)(I >> 1) << 32) | (uint32_t)(Jt >> 1);
-        auto it = at.find(key);
-        if (it == at.end()) {
-          QuadXY qd;
-          qd.t[0] = (I >> 1) * 2;
-          qd.t[1] = std::min(qd.t[0] + 1, mt - 1);
-          qd.t[2] = (Jt >> 1) * 2;
-          qd.t[3] = std::min(qd.t[2] + 1, mt - 1);
-          qd.p[0] = qd.p[1] = qd.p[2] = qd.p[3] = -1;
-          it = at.emplace(key, (int)((int64_t)quads.size() - base)).first;
-          quads.push_back(qd);
-        }
-        quads[(size_t)(base + it->second)].p[(I & 1) * 2 + (Jt & 1)] = (int)(p - p0);
-      }
-    }
-    quad_off.push_back((int64_t)quads.size());
-    if (!quads.empty()) {
-      copy_h2d(bed, J.d_quads.ensure(quads.size()), quads.data(), quads.size() * sizeof(QuadXY));
-      BSN_HIP(hipStreamSynchronize(bed->stream));   // (quads is a host vector)
-    }
-  }
-  std::vector<hipEvent_t> evs;
-  int64_t ib = 0;
-  for (int64_t p0 = pA; p0 < pB; p0 += batch, ib++) {
-    const int64_t np = std::min(batch, pB - p0);
-    hipEvent_t b0 = nullptr, b1 = nullptr;
-    BSN_HIP(hipEventCreate(&b0));
-    BSN_HIP(hipEventCreate(&b1));
-    evs.push_back(b0);
-    evs.push_back(b1);
-    // K split: enough workgroups to fill the chip when there are few tile pairs
-    int ksplit = (int)std::min<int64_t>(std::max<int64_t>(1, 2048 / np), bed->pitch / 256);
-    if (ksplit < 1) ksplit = 1;
-    int64_t kbytes = round_up((bed->pitch + ksplit - 1) / ksplit, 64);
-    ksplit = (int)((bed->pitch + kbytes - 1) / kbytes);
-    const bool fused = !xy_only && ksplit == 1 && !abl_getenv("BSN_LD_NOFUSE");   // (A/B switch: K split + k_band_fill)
-    if (!fused) {
-      J.d_stats.ensure((size_t)std::min(batch, J.npairs) * 6 * TB * TB);
-      if (ksplit > 1 || xy_only) BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
-    }
-    BSN_HIP(hipEventRecord(b0, bed->stream));
-    if (xy_only) {
-      // one wave per workgroup here: four times the K splits of the 4-wave kernel
-      int ks4 = (int)std::min<int64_t>(std::max<int64_t>(4, 8192 / np), bed->pitch / 256);
-      if (ks4 < 1) ks4 = 1;
-      int64_t kb4 = round_up((bed->pitch + ks4 - 1) / ks4, 128);   // (k_pair_xy_f4 walks whole cache lines)
-      ks4 = (int)((bed->pitch + kb4 - 1) / kb4);
-      // (round 6) on the FP4 matrix pipe while its fp32 sums are exact: 4 n < 2^24
-      const bool xy_f4 = bed->n <= 4194303 && !getenv("BSN_LD_I8");
-      // 2 x 2 blocks of tile pairs per workgroup (k_quad_xy_f4) once there are enough of them to fill the chip
-      const bool quad = quad_all && np >= 64;
-      if (quad) {
-        const int64_t nq = quad_off[(size_t)ib + 1] - quad_off[(size_t)ib];
-        const QuadXY *d_q = J.d_quads.p + quad_off[(size_t)ib];
-        int ksq = (int)std::min<int64_t>(std::max<int64_t>(1, 4096 / nq), bed->pitch / 1024);
-        if (ksq < 1) ksq = 1;
-        int64_t kbq = round_up((bed->pitch + ksq - 1) / ksq, 128);
-        ksq = (int)((bed->pitch + kbq - 1) / kbq);
-        if (J.all_rows && abl_getenv("BSN_LD_QUAD_PRIO"))
-          hipLaunchKernelGGL((k_quad_xy_f4<false, 2>), dim3((unsigned)nq, (unsigned)ksq), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, d_q, J.d_mask.p, kbq, J.d_stats.p);
-        else if (J.all_rows)
-          hipLaunchKernelGGL(k_quad_xy_f4<false>, dim3((unsigned)nq, (unsigned)ksq), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, d_q, J.d_mask.p, kbq, J.d_stats.p);
-        else
-          hipLaunchKernelGGL(k_quad_xy_f4<true>, dim3((unsigned)nq, (unsigned)ksq), dim3(256), 0, bed->stream, bed->d_img, bed->pitch,
-                             J.d_cols.p, d_q, J.d_mask.p, kbq, J.d_stats.p);
-        ls.kernel = 8;
-      } else if (xy_f4 && J.all_rows)
-        hipLaunchKernelGGL(k_pair_xy_f4<false>, dim3((unsigned)np, (unsigned)ks4), dim3(64), 0, bed->stream, bed->d_img,
-                           bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask.p, kb4, J.d_stats.p);
-      else if (xy_f4)
-        hipLaunchKernelGGL(k_pair_xy_f4<true>, dim3((unsigned)np, (unsigned)ks4), dim3(64), 0, bed->stream, bed->d_img,
-                           bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask.p, kb4, J.d_stats.p);
-      else
-        hipLaunchKernelGGL(k_pair_xy64, dim3((unsigned)np, (unsigned)ks4), dim3(64), 0, bed->stream, bed->d_img,
-                           bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask.p, kb4, J.d_stats.p);
-      if (!quad) ls.kernel = xy_f4 ? 7 : 2;
-    } else if (fused) {
-      if (J.contig)
-        hipLaunchKernelGGL((k_pair_stats<true, true, true>), dim3((unsigned)np, 1), dim3(256), 0, bed->stream,
-                           bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0,
-                           J.use_mask ? J.d_mask.p : nullptr, kbytes, (int32_t *)nullptr, 0, bo);
-      else
-        hipLaunchKernelGGL((k_pair_stats<true, true>), dim3((unsigned)np, 1), dim3(256), 0, bed->stream,
-                           bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0,
-                           J.use_mask ? J.d_mask.p : nullptr, kbytes, (int32_t *)nullptr, 0, bo);
-      ls.kernel = 0;
-    } else {
-      hipLaunchKernelGGL((k_pair_stats<true, false>), dim3((unsigned)np, (unsigned)ksplit), dim3(256), 0, bed->stream,
-                         bed->d_img, bed->pitch, J.d_cols.p, J.d_pairs.p + p0,
-                         J.use_mask ? J.d_mask.p : nullptr, kbytes, J.d_stats.p, ksplit > 1 ? 1 : 0, bo);
-      ls.kernel = 1;
-    }
-    BSN_HIP(hipGetLastError());
-    BSN_HIP(hipEventRecord(b1, bed->stream));
-    if (!fused) {
-      hipLaunchKernelGGL(k_band_fill, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats.p,
-                         J.d_pairs.p + p0, (int)np, J.m, J.d_lo.p, J.W, d_thr, mode, d_v1, d_v2, nrows,
-                         band, J.complete ? J.d_cx.p : (const double *)nullptr,
-                         J.complete ? J.d_cxx.p : (const double *)nullptr);
-      BSN_HIP(hipGetLastError());
-    }
-    ls.launches += 1;
-  }
-  if (!evs.empty()) BSN_HIP(hipStreamSynchronize(bed->stream));
-  for (size_t t = 0; t + 1 < evs.size(); t += 2) {
-    float ms = 0;
-    BSN_HIP(hipEventElapsedTime(&ms, evs[t], evs[t + 1]));
-    ms_total += ms;
-  }
-  for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  ls.stats_ms = ms_total;
+  ls.launches += R.tm.launches();
+  ls.stats_ms += R.tm.total_ms();
+  ls.kernel = R.kernel;
   g_ld_stats = ls;
 }
 
@@ -1799,7 +1717,78 @@ struct bsn_cor {
 
 static void cormat_resident(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const int64_t *ind_col_in, int64_t m,
                             double size, const double *thr, const double *pos, int fill_diag, int32_t *p_out,
-                            int64_t *nnz_out, bsn_cor **out);
+                            int64_t *nnz_out, bsn_cor **out) {
+  std::unique_ptr<bsn_cor> C(new bsn_cor());
+  BandJob &J = C->job;
+  const RowView rv = row_view(bed_in, ind_row_in, n, ind_col_in, m);
+  bsn_bed *bed = rv.bed;
+  const int64_t *ind_row = rv.ind_row, *ind_col = rv.ind_col;
+  C->owned = rv.owned;
+  band_stats(J, bed, ind_row, n, ind_col, m, pos, size, false, true, 12.0);   // @i + @x: 12 bytes per kept pair
+  copy_h2d(bed, J.d_thr.ensure((size_t)n), thr, (size_t)n * 8);
+  DevBuf<int32_t> d_cnt;
+  DevBuf<int64_t> d_off;
+  DevBuf<int> d_nan;
+  BSN_HIP(hipMemsetAsync(d_nan.ensure(1), 0, sizeof(int), bed->stream));
+  std::vector<int32_t> cnt;
+  std::vector<int64_t> off;
+  int64_t nnz = 0;
+  p_out[0] = 0;
+  // blocks of band columns in ascending order (one block when the band fits): statistics -> r -> count -> compact
+  for (int64_t c0 = 0; c0 < m; c0 += J.chunk_cols) {
+    const int64_t c1 = std::min(m, c0 + J.chunk_cols), mc = c1 - c0;
+    band_run(J, LdMode::cor, J.d_thr.p, nullptr, nullptr, (double)n, c0, c1, c0 > 0);
+    hipLaunchKernelGGL(k_cor_count, dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, bed->stream, J.band_at(c0),
+                       J.d_lo.p, J.W, c0, c1, fill_diag, d_cnt.ensure((size_t)mc));
+    BSN_HIP(hipGetLastError());
+    cnt.resize((size_t)mc);
+    copy_d2h(bed, cnt.data(), d_cnt.p, (size_t)mc * 4);
+    BSN_HIP(hipStreamSynchronize(bed->stream));
+    off.resize((size_t)mc);
+    int64_t nz = 0;
+    for (int64_t j = 0; j < mc; j++) {
+      off[(size_t)j] = nz;
+      nz += cnt[(size_t)j];
+      if (nnz + nz > 0x7fffffffLL) fail("more than 2^31 - 1 non-zero correlations");
+      p_out[c0 + j + 1] = (int32_t)(nnz + nz);
+    }
+    std::unique_ptr<bsn_cor::Piece> P(new bsn_cor::Piece());
+    P->nnz = nz;
+    P->d_i.ensure((size_t)std::max<int64_t>(nz, 1));
+    P->d_x.ensure((size_t)std::max<int64_t>(nz, 1));
+    copy_h2d(bed, d_off.ensure((size_t)mc), off.data(), (size_t)mc * 8);
+    hipLaunchKernelGGL(k_cor_fill, dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, bed->stream, J.band_at(c0),
+                       J.d_lo.p, J.W, c0, c1, fill_diag, d_off.p, P->d_i.p, P->d_x.p, d_nan.p);
+    BSN_HIP(hipGetLastError());
+    BSN_HIP(hipStreamSynchronize(bed->stream));   // `off` is reused by the next block
+    C->pieces.push_back(std::move(P));
+    nnz += nz;
+  }
+  C->nnz = nnz;
+  // (through the handle's pinned staging buffer: a copy into pageable memory leaves every later stream
+  // synchronisation of the process ~4 ms late, bsn_internal.hpp)
+  copy_d2h(bed, &C->has_nan, d_nan.p, sizeof(int));
+  BSN_HIP(hipStreamSynchronize(bed->stream));
+  J.d_band.release();
+  J.d_stats.release();
+  *nnz_out = nnz;
+  *out = C.release();
+}
+
+// The walk over the selection that every out-of-core entry opens with: ind.col inside the file, 'pos' sorted.  Returns whether
+// ind.col is in increasing file order; with `need_increasing` (a message) anything else fails with it.
+static bool check_selection(const bsn_bed *bed, const int64_t *ind_col, int64_t m, const double *pos, const char *need_increasing) {
+  bool increasing = true;
+  for (int64_t t = 0, prev = 0; t < m; t++) {
+    const int64_t c = ind_col ? ind_col[t] : t;
+    if (c < 0 || c >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)c, (long long)bed->m);
+    if (t > 0 && c <= prev && need_increasing) fail("%s", need_increasing);
+    increasing = increasing && (t == 0 || c > prev);
+    if (t > 0 && pos[t] < pos[t - 1]) fail("'pos' is not sorted.");
+    prev = c;
+  }
+  return increasing;
+}
 
 // (round 5) snp_cor / bed_cor on an OUT-OF-CORE handle: corMat pairs every variant with the EARLIER variants of its
 // window (src/corr.cpp:52-53), so a run of target variants needs a halo to the left only.  Each run is uploaded with
@@ -1811,12 +1800,7 @@ static void cormat_streamed(bsn_bed *bed, const int64_t *ind_row, int64_t n, con
                             int64_t *nnz_out, bsn_cor **out) {
   if (m <= 0 || n <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
   auto col = [&](int64_t t) -> int64_t { return ind_col ? ind_col[t] : t; };
-  for (int64_t t = 0; t < m; t++) {
-    if (col(t) < 0 || col(t) >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)col(t), (long long)bed->m);
-    if (t > 0 && col(t) <= col(t - 1))
-      fail("snp_cor on an out-of-core handle (it streams its file) needs 'ind.col' in increasing file order");
-    if (t > 0 && pos[t] < pos[t - 1]) fail("'pos' is not sorted.");
-  }
+  check_selection(bed, ind_col, m, pos, "snp_cor on an out-of-core handle (it streams its file) needs 'ind.col' in increasing file order");
   const int64_t cap = bed->slab_cols;
   bsn_bed *img = slab_image(bed);
   std::unique_ptr<bsn_cor> C(new bsn_cor());
@@ -1890,72 +1874,6 @@ int bsn_cormat(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const int6
   });
 }
 
-}  // extern "C"
-
-static void cormat_resident(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const int64_t *ind_col_in, int64_t m,
-                            double size, const double *thr, const double *pos, int fill_diag, int32_t *p_out,
-                            int64_t *nnz_out, bsn_cor **out) {
-  {
-    std::unique_ptr<bsn_cor> C(new bsn_cor());
-    BandJob &J = C->job;
-    const RowView rv = row_view(bed_in, ind_row_in, n, ind_col_in, m);
-    bsn_bed *bed = rv.bed;
-    const int64_t *ind_row = rv.ind_row, *ind_col = rv.ind_col;
-    C->owned = rv.owned;
-    band_stats(J, bed, ind_row, n, ind_col, m, pos, size, false, true, 12.0);   // @i + @x: 12 bytes per kept pair
-    copy_h2d(bed, J.d_thr.ensure((size_t)n), thr, (size_t)n * 8);
-    DevBuf<int32_t> d_cnt;
-    DevBuf<int64_t> d_off;
-    DevBuf<int> d_nan;
-    BSN_HIP(hipMemsetAsync(d_nan.ensure(1), 0, sizeof(int), bed->stream));
-    std::vector<int32_t> cnt;
-    std::vector<int64_t> off;
-    int64_t nnz = 0;
-    p_out[0] = 0;
-    // blocks of band columns in ascending order (one block when the band fits): statistics -> r -> count -> compact
-    for (int64_t c0 = 0; c0 < m; c0 += J.chunk_cols) {
-      const int64_t c1 = std::min(m, c0 + J.chunk_cols), mc = c1 - c0;
-      band_run(J, 0, J.d_thr.p, nullptr, nullptr, (double)n, c0, c1, c0 > 0);
-      hipLaunchKernelGGL(k_cor_count, dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, bed->stream, J.band_at(c0),
-                         J.d_lo.p, J.W, c0, c1, fill_diag, d_cnt.ensure((size_t)mc));
-      BSN_HIP(hipGetLastError());
-      cnt.resize((size_t)mc);
-      copy_d2h(bed, cnt.data(), d_cnt.p, (size_t)mc * 4);
-      BSN_HIP(hipStreamSynchronize(bed->stream));
-      off.resize((size_t)mc);
-      int64_t nz = 0;
-      for (int64_t j = 0; j < mc; j++) {
-        off[(size_t)j] = nz;
-        nz += cnt[(size_t)j];
-        if (nnz + nz > 0x7fffffffLL) fail("more than 2^31 - 1 non-zero correlations");
-        p_out[c0 + j + 1] = (int32_t)(nnz + nz);
-      }
-      std::unique_ptr<bsn_cor::Piece> P(new bsn_cor::Piece());
-      P->nnz = nz;
-      P->d_i.ensure((size_t)std::max<int64_t>(nz, 1));
-      P->d_x.ensure((size_t)std::max<int64_t>(nz, 1));
-      copy_h2d(bed, d_off.ensure((size_t)mc), off.data(), (size_t)mc * 8);
-      hipLaunchKernelGGL(k_cor_fill, dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, bed->stream, J.band_at(c0),
-                         J.d_lo.p, J.W, c0, c1, fill_diag, d_off.p, P->d_i.p, P->d_x.p, d_nan.p);
-      BSN_HIP(hipGetLastError());
-      BSN_HIP(hipStreamSynchronize(bed->stream));   // `off` is reused by the next block
-      C->pieces.push_back(std::move(P));
-      nnz += nz;
-    }
-    C->nnz = nnz;
-    // (through the handle's pinned staging buffer: a copy into pageable memory leaves every later stream
-    // synchronisation of the process ~4 ms late, bsn_internal.hpp)
-    copy_d2h(bed, &C->has_nan, d_nan.p, sizeof(int));
-    BSN_HIP(hipStreamSynchronize(bed->stream));
-    J.d_band.release();
-    J.d_stats.release();
-    *nnz_out = nnz;
-    *out = C.release();
-  }
-}
-
-extern "C" {
-
 int bsn_ld_last_stats(double *out) {
   return guarded([&] {
     out[0] = g_ld_stats.pairs;
@@ -1996,7 +1914,26 @@ int bsn_cormat_free(bsn_cor *c) {
 }
 
 static void ld_scores_resident(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const int64_t *ind_col_in, int64_t m,
-                               double size, const double *pos, double *out);
+                               double size, const double *pos, double *out) {
+  const RowView rv = row_view(bed_in, ind_row_in, n, ind_col_in, m);
+  bsn_bed *bed = rv.bed;
+  const int64_t *ind_row = rv.ind_row, *ind_col = rv.ind_col;
+  BandJob J;
+  band_stats(J, bed, ind_row, n, ind_col, m, pos, size, false, true);
+  DevBuf<double> d_ld;
+  d_ld.ensure((size_t)m);
+  // blocks of band columns in ascending order (one block when the band fits): r2, then every variant the block's
+  // columns reach takes its terms — the running sums go through the same additions as over the whole band
+  for (int64_t c0 = 0; c0 < m; c0 += J.chunk_cols) {
+    const int64_t c1 = std::min(m, c0 + J.chunk_cols), jlo = J.lo[(size_t)c0];
+    band_run(J, LdMode::r2, nullptr, nullptr, nullptr, (double)n, c0, c1, c0 > 0);
+    hipLaunchKernelGGL(k_ld_sum, dim3((unsigned)((c1 - jlo + 255) / 256)), dim3(256), 0, bed->stream, J.band_at(c0),
+                       J.d_lo.p, J.W, m, jlo, c0, c1, d_ld.p);
+    BSN_HIP(hipGetLastError());
+  }
+  copy_d2h(bed, out, d_ld.p, (size_t)m * 8);
+  BSN_HIP(hipStreamSynchronize(bed->stream));
+}
 
 // (round 5) LD scores on an OUT-OF-CORE handle.  The score of a variant only needs the variants inside its window,
 // so the selection is cut into runs of target variants; each run is uploaded together with its halo (the window of
@@ -2006,12 +1943,7 @@ static void ld_scores_streamed(bsn_bed *bed, const int64_t *ind_row, int64_t n, 
                                double size, const double *pos, double *out) {
   if (m <= 0 || n <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
   auto col = [&](int64_t t) -> int64_t { return ind_col ? ind_col[t] : t; };
-  for (int64_t t = 0; t < m; t++) {
-    if (col(t) < 0 || col(t) >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)col(t), (long long)bed->m);
-    if (t > 0 && col(t) <= col(t - 1))
-      fail("LD scores on an out-of-core handle (it streams its file) need 'ind.col' in increasing file order");
-    if (t > 0 && pos[t] < pos[t - 1]) fail("'pos' is not sorted.");
-  }
+  check_selection(bed, ind_col, m, pos, "LD scores on an out-of-core handle (it streams its file) need 'ind.col' in increasing file order");
   const int64_t cap = bed->slab_cols;
   bsn_bed *img = slab_image(bed);
   std::vector<int64_t> loc;
@@ -2055,30 +1987,6 @@ int bsn_ld_scores(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const i
     }
     ld_scores_resident(bed_in, ind_row_in, n, ind_col_in, m, size, pos, out);
   });
-}
-
-static void ld_scores_resident(bsn_bed *bed_in, const int64_t *ind_row_in, int64_t n, const int64_t *ind_col_in, int64_t m,
-                               double size, const double *pos, double *out) {
-  {
-    const RowView rv = row_view(bed_in, ind_row_in, n, ind_col_in, m);
-    bsn_bed *bed = rv.bed;
-    const int64_t *ind_row = rv.ind_row, *ind_col = rv.ind_col;
-    BandJob J;
-    band_stats(J, bed, ind_row, n, ind_col, m, pos, size, false, true);
-    DevBuf<double> d_ld;
-    d_ld.ensure((size_t)m);
-    // blocks of band columns in ascending order (one block when the band fits): r2, then every variant the block's
-    // columns reach takes its terms — the running sums go through the same additions as over the whole band
-    for (int64_t c0 = 0; c0 < m; c0 += J.chunk_cols) {
-      const int64_t c1 = std::min(m, c0 + J.chunk_cols), jlo = J.lo[(size_t)c0];
-      band_run(J, 1, nullptr, nullptr, nullptr, (double)n, c0, c1, c0 > 0);
-      hipLaunchKernelGGL(k_ld_sum, dim3((unsigned)((c1 - jlo + 255) / 256)), dim3(256), 0, bed->stream, J.band_at(c0),
-                         J.d_lo.p, J.W, m, jlo, c0, c1, d_ld.p);
-      BSN_HIP(hipGetLastError());
-    }
-    copy_d2h(bed, out, d_ld.p, (size_t)m * 8);
-    BSN_HIP(hipStreamSynchronize(bed->stream));
-  }
 }
 
 // ---- greedy clumping inside one chromosome --------------------------------------------------
@@ -2151,7 +2059,7 @@ static int64_t clump_bits(bsn_bed *bed, const int64_t *ind_row, int64_t n, const
   band_stats(J, bed, ind_row, n, ind_col, m, pos, size, true);
   copy_h2d(bed, J.d_v1.ensure((size_t)m), aux1, (size_t)m * 8);
   copy_h2d(bed, J.d_v2.ensure((size_t)m), aux2, (size_t)m * 8);
-  band_run(J, mode == 0 ? 2 : 3, nullptr, J.d_v1.p, J.d_v2.p, (double)n);
+  band_run(J, mode == 0 ? LdMode::clump_fbm : LdMode::clump_bed, nullptr, J.d_v1.p, J.d_v2.p, (double)n);
   const int64_t Wq = (J.W + 63) / 64;
   bitsL.assign(uthr.size(), {});
   bitsU.assign(uthr.size(), {});
@@ -2188,12 +2096,7 @@ static int64_t clump_bits_streamed(bsn_bed *bed, const int64_t *ind_row, int64_t
                                    const std::vector<double> &uthr, std::vector<std::vector<u64>> &bitsL,
                                    std::vector<std::vector<u64>> &bitsU) {
   auto col = [&](int64_t t) -> int64_t { return ind_col ? ind_col[t] : t; };
-  bool increasing = true;
-  for (int64_t t = 0; t < m; t++) {
-    if (col(t) < 0 || col(t) >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)col(t), (long long)bed->m);
-    if (t > 0 && col(t) <= col(t - 1)) increasing = false;
-    if (t > 0 && pos[t] < pos[t - 1]) fail("'pos' is not sorted.");
-  }
+  const bool increasing = check_selection(bed, ind_col, m, pos, nullptr);
   std::vector<int64_t> nL, nU;
   window_counts(pos, m, size, nL, nU);
   int64_t Wg = 1;
@@ -2410,33 +2313,23 @@ static void clumping_grid(bsn_bed *bed, const int64_t *ind_row, int64_t n, const
   }
 }
 
-int bsn_clumping_chr(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
-                     int64_t m, int mode, const double *aux1, const double *aux2,
-                     const int32_t *ordInd, const int32_t *rankInd, const double *pos, double size,
-                     double thr, int32_t *keep) {
-  return guarded([&] {
-    if (bed->streamed()) {   // (round 6) out of core: the band run by run on the slab image, the sweep on the host
-      clumping_grid(bed, ind_row, n, ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, 1, &size, &thr, keep);
-      return;
-    }
-    const RowView rv = row_view(bed, ind_row, n, ind_col, m);
-    clumping_grid(rv.bed, rv.ind_row, n, rv.ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, 1, &size, &thr, keep);
-  });
-}
-
 int bsn_clumping_chr_cached(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
                             int64_t m, int mode, const double *aux1, const double *aux2,
                             const int32_t *ordInd, const int32_t *rankInd, const double *pos,
                             int64_t n_grid, const double *sizes, const double *thrs, int32_t *keep) {
   return guarded([&] {
-    if (bed->streamed()) {
-      clumping_grid(bed, ind_row, n, ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, n_grid, sizes, thrs, keep);
-      return;
-    }
-    const RowView rv = row_view(bed, ind_row, n, ind_col, m);
-    clumping_grid(rv.bed, rv.ind_row, n, rv.ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, n_grid, sizes, thrs,
-                  keep);
+    // (round 6) out of core: the band run by run on the slab image, the sweep on the host (row lists with repeats: clump_bits_streamed)
+    const RowView rv = bed->streamed() ? RowView{bed, ind_row, ind_col, nullptr} : row_view(bed, ind_row, n, ind_col, m);
+    clumping_grid(rv.bed, rv.ind_row, n, rv.ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, n_grid, sizes, thrs, keep);
   });
+}
+
+int bsn_clumping_chr(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                     int64_t m, int mode, const double *aux1, const double *aux2,
+                     const int32_t *ordInd, const int32_t *rankInd, const double *pos, double size,
+                     double thr, int32_t *keep) {
+  // a grid of one point
+  return bsn_clumping_chr_cached(bed, ind_row, n, ind_col, m, mode, aux1, aux2, ordInd, rankInd, pos, 1, &size, &thr, keep);
 }
 
 }  // extern "C"

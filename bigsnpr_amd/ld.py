@@ -476,6 +476,7 @@ def last_stats():
     """figures of the last LD call of this process (bsn_ld_last_stats): bench.py --workload ld"""
     out = np.zeros(5)
     check(_lib.load().bsn_ld_last_stats(ptr(out, f64p)))
+    # indexed by LdKernel (bigsnpr_amd/csrc/ld_plan.hpp); bench.py and the tests read the strings: never renumber
     names = ("k_pair_stats<6 products, fused fp64 epilogue>", "k_pair_stats<6 products, K split> + k_band_fill",
              "k_pair_xy64 (cross product only: no missing values) + k_band_fill",
              "k_pair_stats8 (dosage bytes with missing values: 8 products) + k_band_fill8na",

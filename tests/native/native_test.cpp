@@ -2,11 +2,13 @@
 // (bigsnpr_amd/csrc/svd_driver.hpp, dense_small.hpp) on CPU with a dense host backend so
 // that the driver logic — including the column-sharded multi-rank path with an all-reduce
 // hook — can be tested without a GPU (gloo, world_size 2).  Not part of the product.
+// Also the kernel choice of the windowed-LD band (ld_plan.hpp), which is plain C++ for the same reason.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
+#include "ld_plan.hpp"
 #include "orth_small.hpp"
 #include "svd_driver.hpp"
 
@@ -343,5 +345,26 @@ void nt_svd_host(const double *A, int64_t n, int64_t m_local, int64_t m_total, i
   // below what the rounded products resolve)
   info[7] = (r.exhausted && r.exhausted_resid > 1e-9 ? 1 : 0) | (r.below_resolution > 0 ? 2 : 0);
   *resid = r.max_rel_resid;
+}
+
+// ---- ld_plan.hpp (tests/test_ld_plan_cpu.py) ----
+// facts: bits, pitch, n, mode, complete, contig, all_rows, have_cnn, npairs_b, i8, lut, no_quad
+static BandPlan ld_plan_of(const int64_t *f) {
+  BandFacts b;
+  b.bits = (int)f[0], b.pitch = f[1], b.n = f[2], b.mode = (LdMode)f[3];
+  b.complete = f[4] != 0, b.contig = f[5] != 0, b.all_rows = f[6] != 0, b.have_cnn = f[7] != 0, b.npairs_b = f[8];
+  b.i8 = f[9] != 0, b.lut = f[10] != 0, b.no_quad = f[11] != 0;
+  return plan_band(b);
+}
+// out: path (0 byte_na, 1 byte_xy, 2 shared_decode, 3 xy, 4 small_band), kernel, f4, raw, nomask, quad_all
+void nt_ld_plan(const int64_t *facts, int32_t *out) {
+  const BandPlan p = ld_plan_of(facts);
+  out[0] = (int32_t)p.path, out[1] = (int32_t)p.kernel, out[2] = p.f4, out[3] = p.raw, out[4] = p.nomask, out[5] = p.quad_all;
+}
+int nt_ld_xy_kernel(const int64_t *facts, int64_t np) { return (int)xy_kernel(ld_plan_of(facts), np); }
+int nt_ld_small_band_kernel(int ksplit) { return (int)small_band_kernel(ksplit); }
+void nt_ld_k_split(int64_t pitch, int64_t want, int64_t align, int64_t min_bytes, int64_t *out) {
+  const KSplit k = k_split(pitch, want, align, min_bytes);
+  out[0] = k.splits, out[1] = k.bytes;
 }
 }

@@ -126,7 +126,8 @@ def test_ld_on_complete_data_uses_one_product_and_is_identical(ba, orc):
 
 def test_cross_product_kernel_in_blocks_of_four_tile_pairs(ba, orc, monkeypatch):
     """round 6: k_quad_xy_f4 — four tile pairs per workgroup, their tiles brought once through LDS — against the
-    one-pair-per-wave kernel (BSN_LD_NO_QUAD=1: bit-identical band), the six-product kernels and the oracle: band widths
+    one-pair-per-wave kernel (BSN_LD_NO_QUAD=1: bit-identical band), the int8 kernel k_pair_xy64 that every image of more than
+    4 194 303 samples takes (BSN_LD_I8=1: bit-identical band), the six-product kernels and the oracle: band widths
     from under one tile to many, an odd number of tiles, row subsets (the keep-mask applied by the loading wave), a
     variant list that is not contiguous, clumping on an FBM"""
     from bigsnpr_amd import ld as ldm
@@ -146,6 +147,11 @@ def test_cross_product_kernel_in_blocks_of_four_tile_pairs(ba, orc, monkeypatch)
         assert "k_pair_xy_f4" in ldm.last_stats()["kernel"]
         monkeypatch.delenv("BSN_LD_NO_QUAD")
         np.testing.assert_array_equal(quad, single)
+        monkeypatch.setenv("BSN_LD_I8", "1")
+        i8 = ba.bed_ld_scores(gb, rows, cols, size=size, infos_pos=pos)
+        assert "k_pair_xy64" in ldm.last_stats()["kernel"]
+        monkeypatch.delenv("BSN_LD_I8")
+        np.testing.assert_array_equal(quad, i8)
         monkeypatch.setenv("BSN_FORCE_NA_PLANE", "1")
         np.testing.assert_array_equal(quad, ba.bed_ld_scores(gb, rows, cols, size=size, infos_pos=pos))
         monkeypatch.delenv("BSN_FORCE_NA_PLANE")
@@ -154,8 +160,13 @@ def test_cross_product_kernel_in_blocks_of_four_tile_pairs(ba, orc, monkeypatch)
     monkeypatch.setenv("BSN_LD_NO_QUAD", "1")
     c2 = ba.bed_cor(gb, ir, None, size=0.1, infos_pos=np.arange(m, dtype=float), thr_r2=0.01)
     monkeypatch.delenv("BSN_LD_NO_QUAD")
-    for a, b in ((c1.p, c2.p), (c1.i, c2.i), (c1.x, c2.x)):
+    monkeypatch.setenv("BSN_LD_I8", "1")
+    c3 = ba.bed_cor(gb, ir, None, size=0.1, infos_pos=np.arange(m, dtype=float), thr_r2=0.01)
+    assert "k_pair_xy64" in ldm.last_stats()["kernel"]
+    monkeypatch.delenv("BSN_LD_I8")
+    for a, b, c in ((c1.p, c2.p, c3.p), (c1.i, c2.i, c3.i), (c1.x, c2.x, c3.x)):
         np.testing.assert_array_equal(a, b)
+        np.testing.assert_array_equal(a, c)
     Go = orc.fbm_from_bed(ob)
     G = ba.FBM_code256(Go.bytes)
     chr_ = np.repeat([1, 2, 3], [900, 900, 450])

@@ -339,7 +339,8 @@ def test_raw_plane_kernel_equals_the_look_up_kernel_bit_for_bit(ba, orc, monkeyp
     products and the per-variant totals (x = c - 3 M, x^2 = c + 2 H - 5 M, present = 1 - M): integer arithmetic, so
     every band entry is the one the look-up kernel (BSN_LD_LUT=1) writes — scores, @p / @i / @x and clumping indices
     bit for bit; row subsets (dropped samples are ORed to missing and counted in the totals' way), an increasing column
-    subset, heavy and light missingness, ragged sizes; and against the oracle."""
+    subset, heavy and light missingness, ragged sizes; and against the oracle.  The int8 kernel k_pair_stats_b (BSN_LD_I8=1:
+    what every image of more than 4 194 303 samples takes) is the third party: the same integers, the same bits."""
     from bigsnpr_amd import ld as ldm
     rng = np.random.default_rng(41)
     for n, m, na16 in ((420, 12032, 2000), (1003, 9000, 655), (259, 10250, 20000), (64, 8200, 100)):
@@ -350,10 +351,10 @@ def test_raw_plane_kernel_equals_the_look_up_kernel_bit_for_bit(ba, orc, monkeyp
         ir = np.sort(rng.choice(n, n - n // 5, replace=False))
         ic = np.sort(rng.choice(m, m - 300, replace=False))
         got = {}
-        for tag in ("raw", "lut"):
-            if tag == "lut":
-                monkeypatch.setenv("BSN_LD_LUT", "1")
-            # (the switch is read once per process: the A/B runs in children)
+        for tag in ("raw", "lut", "i8"):
+            if tag != "raw":
+                monkeypatch.setenv({"lut": "BSN_LD_LUT", "i8": "BSN_LD_I8"}[tag], "1")
+            # (one child per setting: no call of one setting precedes a call of another)
             code = (
                 "import numpy as np, sys, pickle, bigsnpr_amd as ba\n"
                 "from bigsnpr_amd import ld as ldm\n"
@@ -376,13 +377,58 @@ def test_raw_plane_kernel_equals_the_look_up_kernel_bit_for_bit(ba, orc, monkeyp
                 assert r.returncode == 0, r.stderr[-2000:]
                 got[tag] = pickle.load(open(fout, "rb"))
             monkeypatch.delenv("BSN_LD_LUT", raising=False)
+            monkeypatch.delenv("BSN_LD_I8", raising=False)
         assert "RAW" in got["raw"]["k_ld"] and "RAW" in got["raw"]["k_cl"], (got["raw"]["k_ld"], got["raw"]["k_cl"])
         assert "RAW" not in got["lut"]["k_ld"] and "k_pair_stats_f4" in got["lut"]["k_ld"] and "RAW" not in got["lut"]["k_cl"]
-        for key in ("ld", "ld_sub", "clump", "clump_sub"):
-            np.testing.assert_array_equal(got["raw"][key], got["lut"][key], err_msg="%s, n=%d m=%d" % (key, n, m))
-        for key in ("cor", "cor_sub"):
-            for a, b in zip(got["raw"][key], got["lut"][key]):
-                np.testing.assert_array_equal(a, b, err_msg="%s, n=%d m=%d" % (key, n, m))
+        assert "k_pair_stats_b" in got["i8"]["k_ld"] and "k_pair_stats_b" in got["i8"]["k_cl"], (got["i8"]["k_ld"], got["i8"]["k_cl"])
+        for other in ("lut", "i8"):
+            for key in ("ld", "ld_sub", "clump", "clump_sub"):
+                np.testing.assert_array_equal(got["raw"][key], got[other][key], err_msg="%s %s, n=%d m=%d" % (other, key, n, m))
+            for key in ("cor", "cor_sub"):
+                for a, b in zip(got["raw"][key], got[other][key]):
+                    np.testing.assert_array_equal(a, b, err_msg="%s %s, n=%d m=%d" % (other, key, n, m))
         if n <= 420:      # (the oracle's scalar loops: seconds at these sizes)
             np.testing.assert_allclose(got["raw"]["ld"], orc.ld_scores(ob, size=500, infos_pos=pos), rtol=1e-12)
             np.testing.assert_array_equal(got["raw"]["clump"], orc.bed_clumping(ob, chrom, pos, thr_r2=0.02, size=500))
+
+
+def test_ld_switches_are_read_on_every_call(ba, orc, monkeypatch):
+    """BSN_LD_LUT and BSN_LD_I8 set or unset after the first LD call of a process take effect on the next call, as
+    BSN_LD_NO_QUAD always did (band_run reads the three on every call): raw planes, look-up planes, int8, raw planes again
+    on one handle in one process — the kernel changes, the scores do not"""
+    from bigsnpr_amd import ld as ldm
+    n, m = 300, 12032                                                 # 94 x 17 blocks of 128 x 32: the shared-decode path
+    ob = orc.fake_bed(n, m, seed=12, na16=1500)
+    gb = ba.bed.from_payload(ob.payload, n, m)
+    pos = np.arange(m, dtype=np.float64)
+    first = ba.bed_ld_scores(gb, size=0.4, infos_pos=pos)
+    assert "RAW" in ldm.last_stats()["kernel"]
+    monkeypatch.setenv("BSN_LD_LUT", "1")
+    lut = ba.bed_ld_scores(gb, size=0.4, infos_pos=pos)
+    k = ldm.last_stats()["kernel"]
+    assert "k_pair_stats_f4" in k and "RAW" not in k, k
+    monkeypatch.setenv("BSN_LD_I8", "1")
+    i8 = ba.bed_ld_scores(gb, size=0.4, infos_pos=pos)
+    assert "k_pair_stats_b" in ldm.last_stats()["kernel"]
+    monkeypatch.delenv("BSN_LD_LUT")
+    monkeypatch.delenv("BSN_LD_I8")
+    again = ba.bed_ld_scores(gb, size=0.4, infos_pos=pos)
+    assert "RAW" in ldm.last_stats()["kernel"]
+    for other in (lut, i8, again):
+        np.testing.assert_array_equal(first, other)
+
+
+def test_small_band_takes_the_tile_pair_kernel_fused_or_with_a_k_split(ba, orc):
+    """a band of fewer than 1 024 blocks of 128 x 32 stays on k_pair_stats (64 x 64 tile pairs): with its fused fp64 epilogue
+    when a batch needs no K split (a variant's samples fill less than two 256-byte pieces), through the statistics buffer
+    and k_band_fill when the few tile pairs are split over the samples to fill the chip; both against the oracle"""
+    from bigsnpr_amd import ld as ldm
+    for n, want in ((500, "fused fp64 epilogue"), (2600, "K split")):
+        m = 900
+        ob = orc.fake_bed(n, m, seed=n, na16=2000)
+        gb = ba.bed.from_payload(ob.payload, n, m)
+        pos = np.arange(m, dtype=np.float64)
+        ld = ba.bed_ld_scores(gb, size=0.05, infos_pos=pos)
+        k = ldm.last_stats()["kernel"]
+        assert k.startswith("k_pair_stats<") and want in k, k
+        np.testing.assert_allclose(ld, orc.ld_scores(ob, size=0.05, infos_pos=pos), rtol=1e-12)

@@ -1,6 +1,6 @@
 """The CPU-side native code under AddressSanitizer + UndefinedBehaviorSanitizer (VERDICT r3 #7c):
 oracle/bsn_oracle.c (the C restatement every parity test leans on) and tests/native (the backend-independent SVD
-driver, orth_small.hpp, dense_small.hpp: the SAME sources the product instantiates with the HIP backend) are built
+driver, orth_small.hpp, dense_small.hpp, ld_plan.hpp: the SAME sources the product instantiates with the HIP backend) are built
 once with -fsanitize=address,undefined and the oracle's golden tests plus the driver tests run on those builds in a
 child interpreter with the sanitizer runtimes preloaded.  Any report aborts the child (halt_on_error / abort_on_error)."""
 import os
@@ -29,7 +29,7 @@ def test_oracle_and_driver_under_asan_ubsan():
     # its own there (bed == FBM clumping on three window units) stays out: the same clumping code runs in the PLINK one
     jobs = [base + ["tests/test_oracle_golden.py", "--deselect",
                     "tests/test_oracle_golden.py::test_clumping_bed_equals_fbm_and_unit_invariance"],
-            base + ["tests/test_svd_driver_cpu.py"]]
+            base + ["tests/test_svd_driver_cpu.py", "tests/test_ld_plan_cpu.py"]]
     procs = [subprocess.Popen(j, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for j in jobs]
     for p in procs:
         out, _ = p.communicate(timeout=1500)
