@@ -520,7 +520,7 @@ void slab_upload_range(bsn_bed *b, int64_t j0, int64_t cnt) {
     fail("internal: variants %lld .. %lld into a slab image of %lld", (long long)j0, (long long)(j0 + cnt), (long long)b->slab_cols);
   img->m = cnt;
   img->na_cnt.clear();
-  img->counts_cache.clear();
+  img->forget_counts();
   image_from_file(img, b->fd_file, 3 + j0 * b->n_byte, b->n_byte, (FileStage *)b->slab_stage);
 }
 int64_t slab_upload(bsn_bed *b, int64_t sl, int64_t *j0_out) {
@@ -578,10 +578,12 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
     });
     return;
   }
-  // the counts of this row selection as an earlier call left them (BSN_NO_COUNTS_CACHE=1: always count)
+  // the counts as an earlier call left them (BSN_NO_COUNTS_CACHE=1: always count).  All samples in file order: the
+  // handle's device-resident counts, which the solves feed and read too (bsn_bed::stats_cache); any other row
+  // selection: the host copy of the last one
   auto &cc = bed->counts_cache;
   const bool use_cache = n > 0 && m > 0 && !getenv("BSN_NO_COUNTS_CACHE");
-  bool rows_all = use_cache && n == bed->n;
+  bool rows_all = n == bed->n;
   for (int64_t i = 0; rows_all && ind_row && i < n; i++) rows_all = ind_row[i] == i;
   std::vector<int64_t> lead;         // (a NULL list with n < the handle's samples: the leading n)
   const int64_t *rows = ind_row;
@@ -590,9 +592,8 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
     for (int64_t i = 0; i < n; i++) lead[(size_t)i] = i;
     rows = lead.data();
   }
-  const bool same_rows = use_cache && (int64_t)cc.cnt.size() == 4 * bed->m &&
-                         (rows_all ? cc.rows_all
-                                   : (!cc.rows_all && (int64_t)cc.rows.size() == n && std::memcmp(cc.rows.data(), rows, (size_t)n * 8) == 0));
+  const bool same_rows = use_cache && !rows_all && (int64_t)cc.cnt.size() == 4 * bed->m && (int64_t)cc.rows.size() == n &&
+                         std::memcmp(cc.rows.data(), rows, (size_t)n * 8) == 0;
   if (same_rows) {
     bool known = true;
     for (int64_t j = 0; known && j < m; j++) {
@@ -608,21 +609,82 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
   fill_op(&op, bed, ind_row, n, ind_col, m, nullptr, nullptr, true);
   DevBuf<int32_t> d_counts;
   d_counts.ensure((size_t)4 * m);
+  const bool device_cache = op.rows_identity && stats_cache_enabled(bed);
+  const StatsCols sel{op.cols_contig ? nullptr : ind_col, op.cols_contig ? nullptr : op.d_cols.p, op.col0, m};
+  if (device_cache && use_cache && stats_cache_known(bed, sel)) {
+    stats_cache_load(bed, sel, d_counts.p, bed->stream);
+    copy_d2h(bed, res, d_counts.p, (size_t)4 * m * 4);
+    return;
+  }
   counts_device(&op, ind_row, n, d_counts.p);
+  if (device_cache) stats_cache_store(bed, sel, d_counts.p, bed->stream);   // (the download below synchronises)
   copy_d2h(bed, res, d_counts.p, (size_t)4 * m * 4);
   if (op.rows_identity) {  // remember which variants are complete
     if ((int64_t)bed->na_cnt.size() != bed->m) bed->na_cnt.assign((size_t)bed->m, -1);
     for (int64_t j = 0; j < m; j++) bed->na_cnt[(size_t)(ind_col ? ind_col[j] : j)] = res[4 * j + 3];
   }
-  if (use_cache) {
+  if (use_cache && !rows_all) {
     if (!same_rows) {
       cc.clear();
-      cc.rows_all = rows_all;
-      if (!rows_all) cc.rows.assign(rows, rows + n);
+      cc.rows.assign(rows, rows + n);
       cc.cnt.assign((size_t)4 * bed->m, -1);
     }
     for (int64_t j = 0; j < m; j++) std::memcpy(&cc.cnt[(size_t)4 * (ind_col ? ind_col[j] : j)], res + 4 * j, 16);
   }
+}
+
+// ---- the handle's device-resident code counts over all samples (bsn_bed::stats_cache) ---------------------------------
+// to_cache: cache[variant of j] = counts[j]; else counts[j] = cache[variant of j].  One int4 per variant.
+__global__ void k_stats_cache_copy(int32_t *cache, int32_t *counts, const int32_t *cols, int64_t col0, int64_t m, int to_cache) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const int64_t c = cols ? (int64_t)cols[j] : col0 + j;
+  if (to_cache) *(int4 *)(cache + 4 * c) = *(const int4 *)(counts + 4 * j);
+  else *(int4 *)(counts + 4 * j) = *(const int4 *)(cache + 4 * c);
+}
+
+bool stats_cache_enabled(const bsn_bed *b) {
+  return b->bits == 2 && !b->generic && b->d_img != nullptr && !getenv("BSN_NO_STATS_CACHE");
+}
+
+static void stats_cols_check(const bsn_bed *b, const StatsCols &c) {
+  if (c.m <= 0 || (c.ind_col ? c.d_cols == nullptr : (c.col0 < 0 || c.col0 + c.m > b->m)))
+    fail("internal: selection of variants for the handle's code counts");
+}
+
+bool stats_cache_known(const bsn_bed *b, const StatsCols &c) {
+  const auto &sc = b->stats_cache;
+  stats_cols_check(b, c);
+  if ((int64_t)sc.known.size() != b->m) return false;
+  if (sc.n_known == b->m) return true;
+  for (int64_t j = 0; j < c.m; j++)
+    if (!sc.known[(size_t)(c.ind_col ? c.ind_col[j] : c.col0 + j)]) return false;
+  return true;
+}
+
+void stats_cache_store(bsn_bed *b, const StatsCols &c, const int32_t *d_counts, hipStream_t st) {
+  auto &sc = b->stats_cache;
+  stats_cols_check(b, c);
+  hipLaunchKernelGGL(k_stats_cache_copy, dim3((unsigned)((c.m + 255) / 256)), dim3(256), 0, st,
+                     sc.d_cnt.ensure((size_t)4 * b->m), const_cast<int32_t *>(d_counts), c.d_cols, c.col0, c.m, 1);
+  BSN_HIP(hipGetLastError());
+  if ((int64_t)sc.known.size() != b->m) {
+    sc.known.assign((size_t)b->m, 0);
+    sc.n_known = 0;
+  }
+  for (int64_t j = 0; j < c.m; j++) {
+    uint8_t &k = sc.known[(size_t)(c.ind_col ? c.ind_col[j] : c.col0 + j)];
+    sc.n_known += k == 0;
+    k = 1;
+  }
+}
+
+void stats_cache_load(bsn_bed *b, const StatsCols &c, int32_t *d_counts, hipStream_t st) {
+  stats_cols_check(b, c);
+  if (!stats_cache_known(b, c)) fail("internal: code counts asked of the handle's cache before they were written");
+  hipLaunchKernelGGL(k_stats_cache_copy, dim3((unsigned)((c.m + 255) / 256)), dim3(256), 0, st, b->stats_cache.d_cnt.p,
+                     d_counts, c.d_cols, c.col0, c.m, 0);
+  BSN_HIP(hipGetLastError());
 }
 
 // ---- multLinReg on the device ----------------------------------------------------------------
@@ -1005,6 +1067,7 @@ int bsn_bed_release_workspace(bsn_bed *bed) {
       bed->sub_rows.clear();
       bed->last_solve_on_sub = false;
     }
+    bed->stats_cache.release();   // the code counts over all samples (16 B per variant): counted again when next needed
     if (bed->slab_img) {   // out-of-core handle: the resident slab image and its page-locked staging buffers
       bed_free(bed->slab_img);
       bed->slab_img = nullptr;

@@ -290,16 +290,44 @@ struct bsn_bed {
   // code counts per variant as the last count entries returned them, for ONE row selection (round 6: snp_autoSVD asks for the
   // column statistics of the same rows three times — snp_MAF, snp_clumping, the scaling function: R/autoSVD.R:103-127 — and
   // each is a pass over the whole image).  cnt[4 j] < 0: not known.  Dropped wherever na_cnt is (the image changed).
+  // That selection is never "all samples in file order": those counts live in stats_cache below.
   struct CountsCache {
-    bool rows_all = false;
-    std::vector<int64_t> rows;      // the selection when it is not all rows in file order
+    std::vector<int64_t> rows;      // the selection
     std::vector<int32_t> cnt;       // 4 per variant of the handle
     void clear() {
-      rows_all = false;
       rows.clear();
       cnt.clear();
     }
   } counts_cache;
+  // Code counts per variant over ALL samples in file order, resident on the device (int32[4 m]: 16 MB at a million
+  // variants).  Written by whichever launch counts with those rows — the first full crossproduct pass of a solve with
+  // bed_scaleBinom's scaling (svd.hip), the column counts (api.hip counts_host) — and read by every later one: a solve
+  // whose variants are all known derives centre / scale from it and streams the image with the plain kernels from its
+  // first launch on; snp_MAF / snp_clumping / bed_counts answer from it.  `known` is the host's record of which
+  // variants have been written, updated where the writer synchronises anyway.  A solve over a list of variants (gather
+  // lists, or the compacted copy `sub`) uses the cache of THIS handle, indexed by the handle's variants.  Void wherever
+  // counts_cache is (forget_counts); BSN_NO_STATS_CACHE=1: neither read nor written.
+  struct StatsCache {
+    bsn::DevBuf<int32_t> d_cnt;     // 4 per variant of the handle
+    std::vector<uint8_t> known;     // m flags (empty: nothing known)
+    int64_t n_known = 0;
+    bsn::DevBuf<int32_t> d_cols;    // the variant list of the compacted copy `sub` on the device, valid while cols_key == sub_key
+    uint64_t cols_key = 0;
+    void clear() {                  // (the allocation stays for the next counts)
+      known.clear();
+      n_known = 0;
+    }
+    void release() {
+      clear();
+      d_cnt.release();
+      d_cols.release();
+      cols_key = 0;
+    }
+  } stats_cache;
+  void forget_counts() {            // new bytes in the image: what earlier counts remembered is void
+    counts_cache.clear();
+    stats_cache.clear();
+  }
   // Share of the K-steps of the two streaming products that carry NO missing code (round 5, matvec.hip op_na_blocks):
   // sampled once per image by a small kernel queued on the handle's stream, picked up from pinned memory by a later
   // launch (no synchronisation).  state 0 = not measured, 1 = queued, 2 = known.  [0] crossproduct (16 variants x
@@ -377,6 +405,19 @@ void counts_all_rows(bsn_bed *b, const int32_t *d_cols, int64_t col0, int64_t m,
 // host result, 4 x m (counts of 0, 1, 2, NA) for arbitrary row / column selections (api.hip)
 void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
                  int32_t *res);
+// api.hip: the handle's device-resident code counts over all samples (bsn_bed::stats_cache).  A selection of the handle's
+// variants as both sides see it: the host list (nullptr: the run col0 .. col0 + m - 1) and the same list on the device.
+struct StatsCols {
+  const int64_t *ind_col;
+  const int32_t *d_cols;
+  int64_t col0, m;
+};
+bool stats_cache_enabled(const bsn_bed *b);                      // a resident 2-bit image and no BSN_NO_STATS_CACHE
+bool stats_cache_known(const bsn_bed *b, const StatsCols &c);    // every selected variant has its counts in the cache
+// d_counts (4 x m, in the order of the selection) -> the cache / the cache -> d_counts, queued on `st`.  store also
+// updates the host record: the caller synchronises `st` before it returns (both callers download results right after).
+void stats_cache_store(bsn_bed *b, const StatsCols &c, const int32_t *d_counts, hipStream_t st);
+void stats_cache_load(bsn_bed *b, const StatsCols &c, int32_t *d_counts, hipStream_t st);
 void read_dense(bsn_bed *b, const int32_t *d_rows, int64_t n, const int32_t *d_cols, int64_t m,
                 const double *d_center, const double *d_scale, int32_t na_val, int32_t *d_out_i,
                 double *d_out_d);

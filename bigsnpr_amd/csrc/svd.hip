@@ -1286,6 +1286,78 @@ static void binom_scale_host(const std::vector<int32_t> &cnt, int64_t n, int64_t
   *n_bad = bad;
 }
 
+// What a counting pass leaves behind (matvec.hip, finish_fused_stats: k_binom_scale + k_stats_summary), for counts that
+// come from the handle's cache instead (bsn_bed::stats_cache): centre / scale of bed_scaleBinom — the same operations in
+// the same order, so the same bits — and out[0] = number of missing genotypes, out[1] = variants with > 50 % missing
+// (integer atomics; cleared by the caller).  The per-variant missing counts are on the handle already (na_cnt).
+#pragma clang fp contract(off)
+__global__ __launch_bounds__(256) void k_scale_from_counts(const int32_t *counts, int64_t m, int64_t n, double *center,
+                                                           double *scale, unsigned long long *out) {
+  long long s = 0, bad = 0;
+  for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < m; j += (int64_t)gridDim.x * 256) {
+    const int4 c = *(const int4 *)(counts + 4 * j);
+    const double sumX = (double)(c.y + 2 * c.z);
+    const double nona = (double)(c.x + c.y + c.z);
+    const double af = sumX / (2.0 * nona);
+    center[j] = 2.0 * af;
+    scale[j] = sqrt(2.0 * af * (1.0 - af));
+    s += c.w;
+    if (2 * ((int64_t)c.x + c.y + c.z) < n) bad++;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_down(s, off);
+    bad += __shfl_down(bad, off);
+  }
+  __shared__ long long sw[4], sb[4];
+  if ((threadIdx.x & 63) == 0) {
+    sw[threadIdx.x >> 6] = s;
+    sb[threadIdx.x >> 6] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    s = sw[0] + sw[1] + sw[2] + sw[3];
+    bad = sb[0] + sb[1] + sb[2] + sb[3];
+    if (s) atomicAdd(&out[0], (unsigned long long)s);
+    if (bad) atomicAdd(&out[1], (unsigned long long)bad);
+  }
+}
+#pragma clang fp contract(on)
+
+// The scaling statistics of a solve whose variants all have their counts in the owner's cache: queued on the solve's
+// stream before its first launch, so no pass has to count.  The two totals come back through the operator's pinned
+// words like those of a counting pass and are read where the solve synchronises at its end.
+static void stats_from_cache(bsn_op *op, bsn_bed *owner, const StatsCols &sel) {
+  bsn_bed *b = op->bed;
+  int32_t *cnt = op->d_counts.ensure((size_t)4 * op->m + 8);
+  stats_cache_load(owner, sel, cnt, b->stream);
+  if (!op->h_na_total) BSN_HIP(hipHostMalloc((void **)&op->h_na_total, 2 * sizeof(long long), hipHostMallocDefault));
+  op->h_na_total[0] = -1;
+  op->h_na_total[1] = -1;
+  unsigned long long *d_tot = (unsigned long long *)(cnt + 4 * op->m);   // (the spare words behind the counts)
+  BSN_HIP(hipMemsetAsync(d_tot, 0, 16, b->stream));
+  int gx = (int)((op->m + 1023) / 1024);
+  if (gx > 1024) gx = 1024;
+  hipLaunchKernelGGL(k_scale_from_counts, dim3(gx), dim3(256), 0, b->stream, cnt, op->m, op->n, op->d_center.p,
+                     op->d_scale.p, d_tot);
+  BSN_HIP(hipGetLastError());
+  BSN_HIP(hipMemcpyAsync(op->h_na_total, d_tot, 16, hipMemcpyDeviceToHost, b->stream));
+}
+
+// the variants of the compacted copy as indices of the owner, on the device (kept while the copy answers to the same list)
+static const int32_t *owner_cols_device(bsn_bed *owner, bsn_bed *sub, const int64_t *cols, int64_t m) {
+  auto &sc = owner->stats_cache;
+  if (sc.cols_key == 0 || sc.cols_key != owner->sub_key || (int64_t)sc.d_cols.n < m) {
+    std::vector<int32_t> c32((size_t)m);
+    for (int64_t j = 0; j < m; j++) {
+      if (cols[j] < 0 || cols[j] >= owner->m) fail("internal: variant %lld of %lld in a compacted solve", (long long)cols[j], (long long)owner->m);
+      c32[(size_t)j] = (int32_t)cols[j];
+    }
+    copy_h2d(sub, sc.d_cols.ensure((size_t)m), c32.data(), (size_t)m * 4);
+    sc.cols_key = owner->sub_key;
+  }
+  return sc.d_cols.p;
+}
+
 // A solve over a list of variants that is not a contiguous range runs on a compacted copy of the selection
 // (bsn_bed::sub, bsn_internal.hpp).  Returns the copy, or nullptr when the solve should go through the gather lists:
 // contiguous columns, a small selection (BSN_COMPACT_MIN_BYTES, default 256 MB of 2-bit payload: below that a solve
@@ -1353,6 +1425,7 @@ static bsn_bed *compacted_view(bsn_bed *bed, const int64_t *ind_row, int64_t n, 
   }
   bed->sub = fresh;
   bed->sub_key = key;
+  bed->stats_cache.cols_key = 0;   // (the device copy of the previous list)
   bed->sub_cols.assign(ind_col, ind_col + m);
   if (keep_rows) bed->sub_rows.assign(ind_row, ind_row + n);
   else bed->sub_rows.clear();
@@ -1396,6 +1469,13 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     bool compacted = false;
     double t_compact = 0.0;
     bed->last_solve_on_sub = false;
+    // the handle's device-resident code counts (bsn_bed::stats_cache) serve, and are fed by, a solve over all samples of
+    // a resident 2-bit image; on the compacted copy too, through the caller's handle and the caller's variant list
+    bsn_bed *const owner = bed;
+    const int64_t *const owner_cols = ind_col;
+    bool rows_all = !ooc && n == bed->n;
+    for (int64_t i = 0; rows_all && ind_row && i < n; i++) rows_all = ind_row[i] == i;
+    const bool use_stats_cache = o->binom_scaling && rows_all && stats_cache_enabled(owner);
     if (bsn_bed *sub = compacted_view(bed, ind_row, n, ind_col, m)) {
       bed->last_solve_on_sub = true;
       if (ind_row == nullptr && n != bed->n) fail("internal: row count of a compacted solve");
@@ -1415,15 +1495,33 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     bsn_op *op = lend.op.get();
     op->passes = 0;
     op->prof_kind_override = -1;
+    for (const void *&pk : op->prof_kernel) pk = nullptr;   // (bsn_bed_streaming_kernels names the launches of THIS solve)
     op->stats_pending = false;
     op->na_poll = false;
     op->no_na = false;
     if (!bed->svd_ws) bed->svd_ws = std::make_shared<SvdWorkspace>();
     int32_t n_bad = 0;
-    bool fused = false;
+    bool fused = false, served = false;
+    StatsCols sel{nullptr, nullptr, 0, m};
     if (o->binom_scaling) {
       fill_op(op, bed, ind_row, n, ind_col, m, nullptr, nullptr, true, ooc);
-      if (op->rows_identity) {
+      if (use_stats_cache) {
+        if (compacted) sel = StatsCols{owner_cols, owner_cols_device(owner, bed, owner_cols, m), 0, m};
+        else if (!op->cols_contig) sel = StatsCols{ind_col, op->d_cols.p, 0, m};
+        else sel.col0 = op->col0;
+        served = op->rows_identity && stats_cache_known(owner, sel);
+      }
+      if (served) {
+        // every variant's counts are on the handle: centre / scale before the first launch, no pass counts, and whether
+        // the missing-value plane is needed is known from the start
+        fused = true;
+        stats_from_cache(op, owner, sel);
+        if (compacted && !getenv("BSN_FORCE_NA_PLANE")) {   // (fill_op looked at the copy's record; the owner's is the one that is known)
+          bool all0 = (int64_t)owner->na_cnt.size() == owner->m;
+          for (int64_t j = 0; all0 && j < m; j++) all0 = owner->na_cnt[(size_t)owner_cols[j]] == 0;
+          op->no_na = all0;
+        }
+      } else if (op->rows_identity) {
         // the counts ride along the first crossproduct pass; until they are known the general kernels run
         op->stats_pending = true;
         op->no_na = false;
@@ -1464,7 +1562,7 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     bk.timing = getenv("BSN_TIMING") != nullptr;
     bk.speculate = getenv("BSN_NO_SPECULATION") == nullptr;
     bk.no_fused = getenv("BSN_NO_FUSED_STEP") != nullptr;
-    bk.fused_stats = fused;
+    bk.fused_stats = fused && !served;
     bk.warm_den = o->warm_denominator >= 2 ? o->warm_denominator : 16;
     int64_t dim = bk.n < bk.m_total ? bk.n : bk.m_total;
     if (o->k > dim) fail("'k' is larger than the dimensions of the matrix.");
@@ -1629,7 +1727,7 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     BSN_HIP(hipEventSynchronize(bed->ev1));
     float ms = 0;
     BSN_HIP(hipEventElapsedTime(&ms, bed->ev0, bed->ev1));
-    if (fused) {
+    if (fused && !served) {
       // by-products of the counting pass: the scaling actually used, the > 50 % missing count of
       // bed_colstats (src/bed-fun.cpp:40-41) and the per-variant completeness of the handle.  They
       // come back through the workspace's pinned staging buffer: blocking copies into pageable memory
@@ -1639,6 +1737,10 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
       const int64_t chunk = 1 << 21;  // int32 per staged piece (8 MB)
       int32_t *hp = (int32_t *)ws.pinned((size_t)chunk / 2);
       if ((int64_t)bed->na_cnt.size() != bed->m) bed->na_cnt.assign((size_t)bed->m, -1);
+      // ... and the counts themselves, into the handle's cache for the next solve (the downloads below synchronise)
+      const bool feed = use_stats_cache && !op->stats_pending && op->m == m && (int64_t)op->d_counts.n >= 4 * m;
+      if (feed) stats_cache_store(owner, sel, op->d_counts.p, bed->stream);
+      if (feed && compacted && (int64_t)owner->na_cnt.size() != owner->m) owner->na_cnt.assign((size_t)owner->m, -1);
       for (int64_t j0 = 0; j0 < m; j0 += chunk) {
         const int64_t cnt = std::min<int64_t>(chunk, m - j0);
         BSN_HIP(hipMemcpyAsync(hp, op->d_na.p + j0, (size_t)cnt * 4, hipMemcpyDeviceToHost, bed->stream));
@@ -1648,7 +1750,11 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
         } else {
           std::memcpy(&bed->na_cnt[(size_t)j0], hp, (size_t)cnt * 4);
         }
+        if (feed && compacted)
+          for (int64_t j = 0; j < cnt; j++) owner->na_cnt[(size_t)owner_cols[j0 + j]] = hp[j];
       }
+    }
+    if (fused) {
       if (op->h_na_total && op->h_na_total[1] >= 0) n_bad += (int32_t)op->h_na_total[1];
       if (o->center_out) copy_d2h(bed, o->center_out, op->d_center.p, (size_t)m * 8);
       if (o->scale_out) copy_d2h(bed, o->scale_out, op->d_scale.p, (size_t)m * 8);
