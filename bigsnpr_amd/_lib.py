@@ -15,6 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libbigsnpr_hip.so")
 u8p = C.POINTER(C.c_uint8)
 i32p = C.POINTER(C.c_int32)
 i64p = C.POINTER(C.c_int64)
+u64p = C.POINTER(C.c_uint64)
 f64p = C.POINTER(C.c_double)
 vp = C.c_void_p
 i64 = C.c_int64
@@ -134,6 +135,10 @@ SIGNATURES = {
     "bsn_sfbm_free": (C.c_int, [vp]),
     "bsn_lassosum2": (C.c_int, [vp, f64p, i64, f64p, f64p, f64p, i64, i64p, C.c_double, C.c_int32, C.c_double,
                                 f64p, i32p, f64p]),
+    "bsn_ldpred2_gibbs": (C.c_int, [vp, f64p, f64p, i64, i64p, f64p, f64p, i32p, u64p, i64, C.c_int, C.c_int, C.c_uint64,
+                                    f64p, f64p]),
+    "bsn_ldpred2_gibbs_sampling": (C.c_int, [vp, f64p, f64p, i64, i64p, C.c_double, C.c_double, C.c_int32, C.c_uint64,
+                                             C.c_int, C.c_int, C.c_uint64, f64p, f64p]),
     "bsn_sfbm_prodvec": (C.c_int, [vp, f64p, i64p, i64, f64p]),
     "bsn_sfbm_ld_scores": (C.c_int, [vp, i64p, i64, f64p]),
     "bsn_sfbm_solve_sym": (C.c_int, [vp, f64p, f64p, i64p, i64, C.c_double, C.c_int32, f64p, i32p, f64p]),

@@ -25,6 +25,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "bsn_internal.hpp"
+#include "gibbs_step.hpp"
 
 struct bsn_sfbm {
   int64_t m2 = 0, nnz = 0;
@@ -214,6 +215,185 @@ __global__ __launch_bounds__(64) void k_lassosum2(const int64_t *__restrict__ P,
     num_iter[g] = k + 1;
     ticks[g] = wall_clock64() - t0;
   }
+}
+
+// ---- LDpred2-grid's Gibbs sampler (src/ldpred2.cpp:9-69, src/ldpred2-sampling.cpp:9-59) ---------------------------------
+// One workgroup of four waves per chain; its dotprods [m2], curr_beta [m] and avg_beta [m] are in HBM.  The structure is
+// k_lassosum2's: 64 coordinates are decided against the current dotprods, a coordinate whose diff is exactly 0 changes
+// nothing that others read, so every coordinate up to the first with diff != 0 is decided as the sequential loop decides
+// it; that one commits, its column is added to dotprods, and the decision resumes behind it.  All four waves decide (the
+// same values in the same operations, so they agree without a hand-off; wave 0 alone stores curr_beta, avg_beta and the
+// samples), all 256 threads add the column.  Two barriers per decision: one behind the additions, before dotprods is read
+// again, and one behind those reads, before a wave that has decided starts adding (the second finds the waves together).
+// gap is added in j order, avg_beta[j] touches only j, rows are distinct within a column: every element of dotprods
+// receives its additions in the reference's order.  U and Z of a coordinate come from its counter alone (gibbs_step.hpp).
+//
+// WINDOW: the rows of dotprods that the chain can still touch, [lo[b], hi[b]] of block b (gibbs_envelope), live in LDS as
+// a ring of `ring_rows` doubles (row r at r mod ring_rows).  When the block changes, the rows below the new lo go back to
+// the chain's HBM vector and the rows up to the new hi come from it; reads and read-modify-writes of a move are LDS
+// operations.  The same additions reach the same elements in the same order: the two paths give the same bits.
+constexpr int kGibbsThreads = 256;
+constexpr int kGibbsAxpy = 8;   // entries per thread and round of a column update (2 048 per round)
+
+struct GibbsArgs {
+  const int64_t *P;
+  const int32_t *I;
+  const double *X;
+  int64_t m2, m;
+  const double *beta_hat, *n_vec;
+  const int64_t *ind_sub;
+  const double *h2, *p;
+  const int32_t *sparse;
+  const uint64_t *stream;
+  const int32_t *order;     // the chain of each workgroup of the call, large p first
+  const int32_t *blo, *bhi;   // WINDOW: the envelope per block of 64 positions
+  int32_t ring_rows;
+  int64_t g0;
+  double gap0;
+  int burn_in, num_iter;
+  uint64_t seed;
+  double *dots, *curs, *avgs;
+  double *out;   // grid: beta [m x G]; sampling: sample_beta [m x num_iter] of the one chain, zeroed
+  uint64_t *ticks;
+};
+
+template <bool WINDOW, bool SAMPLING>
+__global__ __launch_bounds__(kGibbsThreads) void k_ldpred2_gibbs(const GibbsArgs a) {
+  extern __shared__ double ring[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const bool writer = tid < 64;
+  const int64_t m = a.m;
+  const int64_t g = a.order[a.g0 + blockIdx.x];
+  double *dot = a.dots + (int64_t)blockIdx.x * a.m2;   // no __restrict__: threads read what other threads stored
+  double *cur = a.curs + (int64_t)blockIdx.x * m;
+  double *avg = a.avgs + (int64_t)blockIdx.x * m;
+  const double p = a.p[g];
+  const bool sparse = a.sparse[g] != 0;
+  const uint64_t stream = a.stream[g];
+  const double h2_per_var = a.h2[g] / (m * p);
+  const double inv_odd_p = (1 - p) / p;
+  const int32_t W = a.ring_rows;
+  const uint64_t t0 = wall_clock64();
+  bool diverged = false;
+  for (int k = -a.burn_in; k < a.num_iter && !diverged; k++) {
+    double gap = 0;
+    int32_t wlo = 0, whi = -1, wbase = 0;   // WINDOW: rows wlo .. whi of dot are in the ring; wbase = wlo rounded down to W
+    if (WINDOW) {
+      wlo = a.blo[0];
+      whi = wlo - 1;
+    }
+    int64_t b = 0;
+    for (int64_t j0 = 0; j0 < m; j0 += 64, b++) {
+      if (WINDOW) {
+        const int32_t nlo = a.blo[b], nhi = a.bhi[b];
+        if (nlo > wlo || nhi > whi) {
+          const int32_t out_end = nlo < whi + 1 ? nlo : whi + 1;    // rows wlo .. out_end - 1 leave
+          for (int32_t r = wlo + tid; r < out_end; r += kGibbsThreads) dot[r] = ring[r % W];
+          if (out_end > wlo) __syncthreads();   // a row that enters may take the place of one that leaves
+          const int32_t in_from = nlo > whi + 1 ? nlo : whi + 1;    // rows in_from .. nhi enter
+          for (int32_t r = in_from + tid; r <= nhi; r += kGibbsThreads) ring[r % W] = dot[r];
+          wlo = nlo;
+          whi = nhi;
+          __syncthreads();
+        }
+        wbase = wlo / W * W;
+      }
+      const int64_t j = j0 + lane;
+      const bool in = j < m;
+      int64_t j2 = 0, pa = 0, pb = 0;   // the column and its extent: loaded here, ahead of the decision
+      int32_t at = 0;                   // WINDOW: where dot[j2] is in the ring
+      double bh = 0, cb = 0;
+      gibbs::Coord c = {};
+      if (in) {
+        j2 = a.ind_sub ? a.ind_sub[j] : j;
+        pa = a.P[j2];
+        pb = a.P[j2 + 1];
+        bh = a.beta_hat[j];
+        cb = cur[j];
+        c = gibbs::coord(a.n_vec[j], h2_per_var, inv_odd_p, gibbs::draw(a.seed, stream, (uint32_t)(k + a.burn_in), (uint32_t)j));
+        if (WINDOW) {
+          at = (int32_t)j2 - wbase;
+          if (at >= W) at -= W;
+        }
+      }
+      int from = 0;   // lanes below `from` are decided
+      for (;;) {
+        const bool act = in && lane >= from;
+        gibbs::Step s = {};
+        double dj = 0, sh = 0;
+        if (act) dj = WINDOW ? ring[at] : dot[j2];
+        // every wave holds its values before any wave, having decided, adds a column: the waves must decide alike
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (act) {
+          s = gibbs::step<SAMPLING>(bh, dj, cb, c, p, sparse);
+          sh = s.beta - cb;
+        }
+        const uint64_t moves = __ballot(act && sh != 0);
+        const int f = moves ? __ffsll((unsigned long long)moves) - 1 : 64;   // the first coordinate that changes state
+        const bool decided = act && lane <= f;
+        if (!SAMPLING) {
+          uint64_t nz = __ballot(decided && s.nonzero);
+          const double sq = s.beta * s.beta;
+          while (nz) {
+            const int l = __ffsll((unsigned long long)nz) - 1;
+            gap += lane_value(sq, l);
+            nz &= nz - 1;
+          }
+        }
+        if (writer && decided && s.drawn && k >= 0) {
+          if (SAMPLING) a.out[j + (int64_t)k * m] = s.beta;
+          else avg[j] += s.mean;
+        }
+        if (f == 64) break;
+        const double shift = lane_value(sh, f);
+        if (lane == f) {
+          cb = s.beta;
+          if (writer) cur[j] = s.beta;
+        }
+        const int64_t e1 = lane_index(pb, f);
+        for (int64_t eb = lane_index(pa, f) + tid; eb < e1; eb += kGibbsThreads * kGibbsAxpy) {
+          int32_t r[kGibbsAxpy];
+          double xv[kGibbsAxpy], dv[kGibbsAxpy];
+#pragma unroll
+          for (int u = 0; u < kGibbsAxpy; u++) {
+            const int64_t e = eb + kGibbsThreads * u;
+            r[u] = e < e1 ? a.I[e] : 0;
+            xv[u] = e < e1 ? a.X[e] : 0.0;
+          }
+          if (WINDOW) {
+#pragma unroll
+            for (int u = 0; u < kGibbsAxpy; u++)
+              if (eb + kGibbsThreads * u < e1) {
+                int32_t q = r[u] - wbase;
+                if (q >= W) q -= W;
+                ring[q] = ring[q] + xv[u] * shift;
+              }
+          } else {
+#pragma unroll
+            for (int u = 0; u < kGibbsAxpy; u++)
+              if (eb + kGibbsThreads * u < e1) dv[u] = dot[r[u]];
+#pragma unroll
+            for (int u = 0; u < kGibbsAxpy; u++)
+              if (eb + kGibbsThreads * u < e1) dot[r[u]] = dv[u] + xv[u] * shift;
+          }
+        }
+        __syncthreads();   // the additions above, before any thread reads dotprods again
+        from = f + 1;
+        if (from >= 64) break;
+      }
+    }
+    if (WINDOW) {
+      for (int32_t r = wlo + tid; r <= whi; r += kGibbsThreads) dot[r] = ring[r % W];
+      __syncthreads();
+    }
+    if (!SAMPLING && gap > a.gap0) diverged = true;
+  }
+  if (!SAMPLING) {
+    __syncthreads();   // wave 0's avg_beta, before every thread reads it
+    for (int64_t j = tid; j < m; j += kGibbsThreads) a.out[g * m + j] = diverged ? __builtin_nan("") : avg[j] / a.num_iter;
+  }
+  if (tid == 0) a.ticks[g] = wall_clock64() - t0;
 }
 
 #pragma clang fp contract(on)
@@ -565,6 +745,103 @@ double host_total(const double *d_part, int n) {
   return t;
 }
 
+// Both Gibbs entries: G chains of the grid (sample_out NULL), or one chain's samples.  The checks come before any device work.
+void run_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
+               const double *h2, const double *p, const int32_t *sparse, const uint64_t *stream, int64_t G, int burn_in,
+               int num_iter, uint64_t seed, double *beta_out, double *sample_out, double *seconds_out, const char *what) {
+  if (!s) fail("%s: NULL 'corr'", what);
+  if (m < 0 || G < 0 || G > 0x7fffffffLL || (m > 0 && (!beta_hat || !n_vec)) || (G > 0 && (!h2 || !p || !sparse)) ||
+      (m > 0 && G > 0 && !(sample_out ? sample_out : beta_out)))
+    fail("%s: arguments", what);
+  check_ind_sub(s, ind_sub, m, true, what);
+  for (int64_t g = 0; g < G; g++) {
+    if (!(h2[g] > 0)) fail("'h2' should have only positive values.");
+    if (!(p[g] > 0 && p[g] <= 1)) fail("'p' should be in (0, 1].");
+  }
+  if (burn_in < 0) fail("'burn_in' should not be negative.");
+  if (num_iter < 1) fail("'num_iter' should be at least 1.");
+  if (G == 0 || m == 0) return;
+  require_gpu();
+  const bool sampling = sample_out != nullptr;
+  const double gap0 = lassosum2_gap0(beta_hat, m);   // 2 * inner_product(beta_hat, beta_hat), src/ldpred2.cpp:29-30
+  // the path: the LDS window when the visiting order ascends and the envelope fits (BSN_GIBBS_NO_WINDOW=1: never)
+  const gibbs::Envelope env = gibbs::gibbs_envelope(s->lo.data(), s->hi.data(), ind_sub, m);
+  const bool window = gibbs::gibbs_window_fits(env) && getenv("BSN_GIBBS_NO_WINDOW") == nullptr;
+  const int32_t ring_rows = window ? (int32_t)round_up(env.rows, 64) : 0;
+  // large p first (R/LDpred2.R:94): the longest chains start first when there are more chains than the device takes at once
+  std::vector<int32_t> order((size_t)G);
+  for (int64_t g = 0; g < G; g++) order[(size_t)g] = (int32_t)g;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    if (p[a] != p[b]) return p[a] > p[b];
+    if ((sparse[a] != 0) != (sparse[b] != 0)) return sparse[a] == 0;
+    return h2[a] > h2[b];
+  });
+  std::vector<uint64_t> st((size_t)G);
+  for (int64_t g = 0; g < G; g++) st[(size_t)g] = stream ? stream[g] : (uint64_t)g;
+  // as many chains per launch as the free memory holds (dotprods + curr_beta + avg_beta of each, 3/4 of what is free
+  // once the result and the per-call vectors, which stay for the whole call, are taken off)
+  size_t free_b = 0, total_b = 0;
+  BSN_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t n_out = (size_t)m * (size_t)(sampling ? num_iter : G);
+  const int64_t per_g = (s->m2 + 2 * m) * 8;
+  const int64_t fixed_b = (int64_t)n_out * 8 + m * 24 + G * 48 + (int64_t)(env.lo.size() + env.hi.size()) * 4;
+  const int64_t batch = std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g);
+  if (batch < 1)
+    fail("%s: the result (%lld B) and the state of one chain (%lld B) do not fit the free device memory", what,
+         (long long)fixed_b, (long long)per_g);
+  int clock_khz = 0, dev = 0;
+  BSN_HIP(hipGetDevice(&dev));
+  BSN_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
+  DevBuf<double> d_bh, d_nv, d_h2, d_p, d_dots, d_curs, d_avgs, d_out;
+  DevBuf<int64_t> d_ind;
+  DevBuf<int32_t> d_sparse, d_order, d_blo, d_bhi;
+  DevBuf<uint64_t> d_stream, d_ticks;
+  BSN_HIP(hipMemcpy(d_bh.ensure((size_t)m), beta_hat, (size_t)m * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_nv.ensure((size_t)m), n_vec, (size_t)m * 8, hipMemcpyHostToDevice));
+  if (ind_sub) BSN_HIP(hipMemcpy(d_ind.ensure((size_t)m), ind_sub, (size_t)m * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_h2.ensure((size_t)G), h2, (size_t)G * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_p.ensure((size_t)G), p, (size_t)G * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_sparse.ensure((size_t)G), sparse, (size_t)G * 4, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_order.ensure((size_t)G), order.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_stream.ensure((size_t)G), st.data(), (size_t)G * 8, hipMemcpyHostToDevice));
+  if (window) {
+    BSN_HIP(hipMemcpy(d_blo.ensure(env.lo.size()), env.lo.data(), env.lo.size() * 4, hipMemcpyHostToDevice));
+    BSN_HIP(hipMemcpy(d_bhi.ensure(env.hi.size()), env.hi.data(), env.hi.size() * 4, hipMemcpyHostToDevice));
+  }
+  d_out.ensure(n_out);
+  if (sampling) BSN_HIP(hipMemsetAsync(d_out.p, 0, n_out * 8, nullptr));   // sample_beta starts as zeros
+  d_dots.ensure((size_t)(batch * s->m2));
+  d_curs.ensure((size_t)(batch * m));
+  d_avgs.ensure((size_t)(batch * m));
+  d_ticks.ensure((size_t)G);
+  GibbsArgs a;
+  a.P = s->p.p, a.I = s->i.p, a.X = s->x.p, a.m2 = s->m2, a.m = m;
+  a.beta_hat = d_bh.p, a.n_vec = d_nv.p, a.ind_sub = ind_sub ? d_ind.p : nullptr;
+  a.h2 = d_h2.p, a.p = d_p.p, a.sparse = d_sparse.p, a.stream = d_stream.p, a.order = d_order.p;
+  a.blo = d_blo.p, a.bhi = d_bhi.p, a.ring_rows = ring_rows;
+  a.gap0 = gap0, a.burn_in = burn_in, a.num_iter = num_iter, a.seed = seed;
+  a.dots = d_dots.p, a.curs = d_curs.p, a.avgs = d_avgs.p, a.out = d_out.p, a.ticks = d_ticks.p;
+  const size_t lds = (size_t)ring_rows * 8;
+  auto kernel = window ? (sampling ? k_ldpred2_gibbs<true, true> : k_ldpred2_gibbs<true, false>)
+                       : (sampling ? k_ldpred2_gibbs<false, true> : k_ldpred2_gibbs<false, false>);
+  if (window) BSN_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int64_t g0 = 0; g0 < G; g0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, G - g0);
+    BSN_HIP(hipMemsetAsync(d_dots.p, 0, (size_t)(nb * s->m2) * 8, nullptr));
+    BSN_HIP(hipMemsetAsync(d_curs.p, 0, (size_t)(nb * m) * 8, nullptr));
+    BSN_HIP(hipMemsetAsync(d_avgs.p, 0, (size_t)(nb * m) * 8, nullptr));
+    a.g0 = g0;
+    kernel<<<(unsigned)nb, kGibbsThreads, lds>>>(a);
+    BSN_HIP(hipGetLastError());
+  }
+  BSN_HIP(hipMemcpy(sampling ? sample_out : beta_out, d_out.p, n_out * 8, hipMemcpyDeviceToHost));
+  if (seconds_out) {
+    std::vector<uint64_t> t((size_t)G);
+    BSN_HIP(hipMemcpy(t.data(), d_ticks.p, (size_t)G * 8, hipMemcpyDeviceToHost));
+    for (int64_t g = 0; g < G; g++) seconds_out[g] = clock_khz > 0 ? (double)t[(size_t)g] / (clock_khz * 1e3) : NAN;
+  }
+}
+
 }  // namespace
 }  // namespace bsn
 
@@ -739,6 +1016,25 @@ int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const do
       BSN_HIP(hipMemcpy(t.data(), d_ticks.p, (size_t)G * 8, hipMemcpyDeviceToHost));
       for (int64_t g = 0; g < G; g++) time_out[g] = clock_khz > 0 ? (double)t[(size_t)g] / (clock_khz * 1e3) : NAN;
     }
+  });
+}
+
+int bsn_ldpred2_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
+                      const double *h2, const double *p, const int32_t *sparse, const uint64_t *stream, int64_t G, int burn_in,
+                      int num_iter, uint64_t seed, double *beta_out, double *seconds_out) {
+  return guarded([&] {
+    run_gibbs(s, beta_hat, n_vec, m, ind_sub, h2, p, sparse, stream, G, burn_in, num_iter, seed, beta_out, nullptr, seconds_out,
+              "bsn_ldpred2_gibbs");
+  });
+}
+
+int bsn_ldpred2_gibbs_sampling(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
+                               double h2, double p, int32_t sparse, uint64_t stream, int burn_in, int num_iter, uint64_t seed,
+                               double *sample_out, double *seconds_out) {
+  return guarded([&] {
+    if (!sample_out && m > 0) fail("bsn_ldpred2_gibbs_sampling: arguments");
+    run_gibbs(s, beta_hat, n_vec, m, ind_sub, &h2, &p, &sparse, &stream, 1, burn_in, num_iter, seed, nullptr, sample_out,
+              seconds_out, "bsn_ldpred2_gibbs_sampling");
   });
 }
 

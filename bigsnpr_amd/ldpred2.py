@@ -1,16 +1,18 @@
-"""LD scores, LD score regression and LDpred2-inf over the resident SFBM — host mirror of R/ldsc.R, R/LDpred2.R:27-42 and of
-bigsparser's sp_prodVec / sp_solve_sym.
+"""LD scores, LD score regression, LDpred2-inf and LDpred2-grid over the resident SFBM — host mirror of R/ldsc.R,
+R/LDpred2.R:27-140 and of bigsparser's sp_prodVec / sp_solve_sym.
 
-The sparse products run on the device (bsn_sfbm_prodvec, bsn_sfbm_ld_scores, bsn_sfbm_solve_sym); the regression itself
-works on vectors of length M and is numpy on the host, as it is R in the reference.  Indices are 0-based.  Every device
-sum has a fixed order: two calls on the same inputs return the same bits."""
+The sparse products run on the device (bsn_sfbm_prodvec, bsn_sfbm_ld_scores, bsn_sfbm_solve_sym), and so do the Gibbs
+chains of snp_ldpred2_grid (bsn_ldpred2_gibbs); the regression itself works on vectors of length M and is numpy on the
+host, as it is R in the reference.  Indices are 0-based.  Every device sum has a fixed order: two calls on the same
+inputs (and, for the sampler, the same seed) return the same bits."""
 import ctypes as C
+import os
 from statistics import NormalDist
 
 import numpy as np
 
 from . import _lib
-from ._lib import as_f64, check, f64p, i64p, ptr
+from ._lib import as_f64, check, f64p, i32p, i64p, ptr, u64p
 from .bed import ERROR_DIM
 from .lassosum2 import SFBM, _col, _ncol, as_SFBM
 
@@ -289,3 +291,97 @@ def snp_ldpred2_inf(corr, df_beta, h2):
     beta_hat = beta / scale
     beta_inf = sp_solve_sym(corr, beta_hat, add_to_diag=m2 / (float(h2) * N))
     return np.asarray(beta_inf) * scale
+
+
+# ---- R/LDpred2.R:73-140 --------------------------------------------------------------------------------------------------
+
+class LDpred2Grid(np.ndarray):
+    """beta_grid (m x number of chains; m x num_iter with return_sampling_betas).  `.seed` is the key the random numbers
+    of the call came from (the same seed gives the same bits), `.grid_param` holds p, h2, sparse, stream and `time`,
+    each chain's seconds on the device clock (all chains of a call run at the same time)."""
+    seed = None
+    grid_param = None
+
+    def __array_finalize__(self, obj):
+        if obj is not None:
+            self.seed = getattr(obj, "seed", None)
+            self.grid_param = getattr(obj, "grid_param", None)
+
+
+def _grid_col(grid_param, name, dtype):
+    try:
+        has = name in grid_param
+    except TypeError:
+        has = False
+    if not has:
+        raise ValueError("'grid_param' should have element '%s'." % name)
+    return np.ascontiguousarray(np.ravel(np.asarray(grid_param[name])), dtype=dtype)
+
+
+def snp_ldpred2_grid(corr, df_beta, grid_param, burn_in=50, num_iter=100, ncores=1, return_sampling_betas=False,
+                     ind_corr=None, seed=None):
+    """R/LDpred2.R:73-140: one Gibbs chain per row of grid_param (a mapping or DataFrame with p, h2, sparse), all of them
+    in one library call over the resident matrix.  corr: an SFBM or anything as_SFBM takes (converted for this call
+    only).  Returns an LDpred2Grid: m x nrow(grid_param), NaN columns where the reference returns NA; with
+    return_sampling_betas (one row of grid_param only) m x num_iter, the effects after each sweep past burn-in.
+
+    The random numbers.  R's generator cannot be reproduced; U and Z of (chain, sweep, position in ind_corr) come from
+    a counter-based generator keyed by `seed`.  seed=None draws a fresh seed, so two calls differ, as in the reference
+    without set.seed; the seed used is kept on the result.  A chain's stream id is its row in grid_param unless
+    grid_param has an element 'stream': a chain's result depends on (seed, stream, its own parameters) alone, not on
+    the other rows or their order.  ncores is accepted for the reference's signature."""
+    # the reference's checks, in its order, before any device work
+    beta, beta_se, n_eff = _sumstats(df_beta)
+    pp, h2 = (_grid_col(grid_param, n, np.float64) for n in ("p", "h2"))
+    sparse = _grid_col(grid_param, "sparse", bool).astype(np.int32)
+    ind = _subset(corr, ind_corr, beta.size, "ind.corr", repeats_ok=True)
+    if not np.all(beta_se > 0):
+        raise ValueError("'df_beta$beta_se' should have only positive values.")
+    if not np.all(h2 > 0):
+        raise ValueError("'grid_param$h2' should have only positive values.")
+    if not (int(ncores) == ncores and ncores >= 1):
+        raise ValueError("'ncores' should be an integer >= 1.")
+    if not (beta.size == beta_se.size == n_eff.size) or not (pp.size == h2.size == sparse.size):
+        raise ValueError(ERROR_LENGTH)
+    G = pp.size
+    if return_sampling_betas and G != 1:
+        raise ValueError("Only one set of parameters is allowed when using 'return_sampling_betas'.")
+    if ind is not None and np.unique(ind).size != ind.size:
+        raise ValueError("'ind.corr' should not have repeated indices.")
+    has_stream = False
+    try:
+        has_stream = "stream" in grid_param
+    except TypeError:
+        pass
+    stream = _grid_col(grid_param, "stream", np.uint64) if has_stream else np.arange(G, dtype=np.uint64)
+    if stream.size != G:
+        raise ValueError(ERROR_LENGTH)
+    burn_in, num_iter = int(burn_in), int(num_iter)
+    if burn_in < 0:
+        raise ValueError("'burn_in' should not be negative.")
+    if num_iter < 1:
+        raise ValueError("'num_iter' should be at least 1.")
+    seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
+
+    N = n_eff
+    scale = np.sqrt(N * beta_se ** 2 + beta ** 2)
+    beta_hat = as_f64(beta / scale)
+    N = as_f64(N)
+    m = beta_hat.size
+    secs = np.zeros(G)
+    L = _lib.load()
+    with _Resident(corr) as sf:
+        if return_sampling_betas:
+            out = np.empty((m, num_iter), dtype=np.float64, order="F")
+            check(L.bsn_ldpred2_gibbs_sampling(sf.handle, ptr(beta_hat, f64p), ptr(N, f64p), m, ptr(ind, i64p), float(h2[0]),
+                                               float(pp[0]), int(sparse[0]), int(stream[0]), burn_in, num_iter, seed,
+                                               out.ctypes.data_as(f64p), secs.ctypes.data_as(f64p)))
+        else:
+            out = np.empty((m, G), dtype=np.float64, order="F")
+            check(L.bsn_ldpred2_gibbs(sf.handle, ptr(beta_hat, f64p), ptr(N, f64p), m, ptr(ind, i64p), ptr(h2, f64p),
+                                      ptr(pp, f64p), ptr(sparse, i32p), ptr(stream, u64p), G, burn_in, num_iter, seed,
+                                      out.ctypes.data_as(f64p), secs.ctypes.data_as(f64p)))
+    res = (out * scale[:, None]).view(LDpred2Grid)      # sweep(beta_gibbs, 1, scale, '*')
+    res.seed = seed
+    res.grid_param = {"p": pp, "h2": h2, "sparse": sparse.astype(bool), "stream": stream, "time": secs}
+    return res

@@ -503,6 +503,21 @@ int bsn_sfbm_free(bsn_sfbm *s);
 int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const double *pf, const double *lambda,
                   const double *delta, int64_t G, const int64_t *ind_sub, double dfmax, int32_t maxiter, double tol,
                   double *beta_out, int32_t *num_iter_out, double *time_out);
+/* LDpred2-grid's Gibbs sampler: ldpred2_gibbs_one (src/ldpred2.cpp:9-69) for G chains per call, and
+ * ldpred2_gibbs_one_sampling (src/ldpred2-sampling.cpp:9-59) for one.  Chain g uses h2[g], p[g] (0 < p <= 1), sparse[g]
+ * and the random numbers of stream[g] (NULL: g): U and Z of sweep k, position j come from a counter-based generator
+ * keyed by `seed` at the counter (j, k + burn_in, stream[g]) and from nothing else, so a chain's result depends on
+ * neither its place in the call nor the other chains.  ind_sub [m] as above, without repeats.  beta_out [m * G] is
+ * column-major, avg_beta / num_iter, all NaN where the reference returns NA (gap > gap0 after a sweep); sample_out
+ * [m * num_iter] holds curr_beta after each sweep past burn-in.  seconds_out (may be NULL): each chain's seconds on the
+ * device clock.  Every floating-point operation is the reference's, in its order; only the generator differs from R's.
+ * Arguments are checked before any device work. */
+int bsn_ldpred2_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
+                      const double *h2, const double *p, const int32_t *sparse, const uint64_t *stream, int64_t G, int burn_in,
+                      int num_iter, uint64_t seed, double *beta_out, double *seconds_out);
+int bsn_ldpred2_gibbs_sampling(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
+                               double h2, double p, int32_t sparse, uint64_t stream, int burn_in, int num_iter, uint64_t seed,
+                               double *sample_out, double *seconds_out);
 
 /* ---- products with the resident matrix: bigsparser's sp_prodVec and sp_solve_sym, ld_scores_sfbm ------------------------
  * ind_sub [m] (0-based columns of `corr`, any order; NULL: all of them, m = m2) means "as if run on corr[ind_sub, ind_sub]".
