@@ -13,7 +13,7 @@ y_exact being formed here in rational arithmetic (fractions) on a sample of the 
 exact zero of the scattered vector: they add nothing and round nothing.  Against scipy's own fp64 product, which obeys the
 same bound, the bound doubles.  The LD scores obey it with x^2 in the place of |a| |x|."""
 import os
-from fractions import Fraction
+import sys
 
 import numpy as np
 import pytest
@@ -22,8 +22,9 @@ pytestmark = pytest.mark.gpu
 
 sparse = pytest.importorskip("scipy.sparse")
 
-U = 2.0 ** -53
-UQ = Fraction(1, 2 ** 53)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+from sfbm_inputs import check_exact, check_residual, check_scipy  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -91,39 +92,6 @@ def scipy_matrices():
     wide = sparse.csc_matrix(np.corrcoef(rng.normal(size=(300, 150)), rowvar=False))     # every column long (150 entries)
     return {"irregular": irregular, "empty_columns": empty, "one_by_one": sparse.csc_matrix(np.array([[0.75]])),
             "dense_columns": wide}
-
-
-def exact_column(A, j, x, square=False):
-    """(sum, sum of absolute values, number of terms) of column j's terms a_ij x_i (a_ij^2 when `square`), in rationals"""
-    lo, hi = A.indptr[j], A.indptr[j + 1]
-    s, sa = Fraction(0), Fraction(0)
-    for r, a in zip(A.indices[lo:hi], A.data[lo:hi]):
-        t = Fraction(float(a)) * (Fraction(float(a)) if square else Fraction(float(x[r])))
-        s += t
-        sa += abs(t)
-    return s, sa, int(hi - lo)
-
-
-def check_exact(A, x, y, cols, square=False):
-    """the bound of the module docstring, in rationals, for the listed columns of A (x: the vector seen by those columns)"""
-    worst = 0.0
-    for j in cols:
-        s, sa, L = exact_column(A, j, x, square)
-        err, bound = abs(Fraction(float(y[j])) - s), (L + 1) * UQ * sa
-        if sa:
-            worst = max(worst, float(err / (UQ * sa)) / (L + 1))
-        assert err <= bound, (j, L, float(err), float(bound))
-    return worst
-
-
-def check_scipy(A, x, y, square=False):
-    """twice the bound, against scipy's fp64 product, for every column"""
-    L = np.diff(A.indptr)
-    if square:
-        ref = mag = np.asarray(A.multiply(A).sum(axis=0)).ravel()
-    else:
-        ref, mag = A.T @ x, abs(A).T @ np.abs(x)
-    assert np.all(np.abs(y - ref) <= 2 * (L + 1) * U * mag), np.max(np.abs(y - ref) / np.maximum(mag, 1e-300))
 
 
 def sample_cols(m, k, seed):
@@ -239,19 +207,10 @@ def test_sp_colSumsSq_sym_equals_colsums_of_squares(ba):
 def check_solve(M, b, d, sol, tol):
     """the three assertions on a solve of (A + diag(d)) x = b, A the full matrix of M"""
     A = full_of(M)
-    n = b.size
     x = np.asarray(sol)
     assert sol.iters >= 1 and sol.relres <= tol
-    # 1. the residual recomputed here in fp64.  Both this and the device's t = (A + D) x obey the product bound with one term
-    # more (the diagonal shift): e_j = (L_j + 2) u (|A + D| |x|)_j each; b - t adds u |r_j| each, and a norm of n terms
-    # (n + 2) u relative.  So | ||r_host|| - ||r_gpu|| | <= 2 ||e + u |r| || + (n + 2) u (||r_host|| + ||r_gpu||).
-    Md = sparse.csc_matrix(A + sparse.diags(d))
-    r = b - Md @ x
-    relres_host = np.linalg.norm(r) / np.linalg.norm(b)
-    e = (np.diff(A.indptr) + 2) * U * (abs(Md) @ np.abs(x)) + U * np.abs(r)
-    slack = 2 * np.linalg.norm(e) / np.linalg.norm(b) + (n + 2) * U * (relres_host + sol.relres)
-    print("iters %d, relres device %.3e host %.3e (allowed difference %.3e)" % (sol.iters, sol.relres, relres_host, slack))
-    assert abs(relres_host - sol.relres) <= slack
+    # 1. the residual recomputed here in fp64 against the device's, with the slack derived at check_residual
+    Md, relres_host = check_residual(A, b, d, sol)
     # 2. against the dense solve: x - x_dense = (A + D)^-1 (r_dense - r_gpu)
     dense = Md.toarray()
     x_dense = np.linalg.solve(dense, b)

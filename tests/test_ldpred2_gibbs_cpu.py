@@ -12,7 +12,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 import ldpred2_ref as ref  # noqa: E402
+from sfbm_inputs import banded_corr  # noqa: E402
 from scipy import sparse  # noqa: E402
 
 
@@ -82,17 +84,6 @@ def test_exp_log_qnorm_against_libm():
 
 
 # ---- the C statement against the transliteration -------------------------------------------------------------------------------
-
-def banded_corr(m2, band, seed, n=60):
-    rng = np.random.default_rng(seed)
-    X = rng.binomial(2, rng.uniform(0.1, 0.5, m2), size=(n, m2)).astype(float)
-    R = np.corrcoef(X, rowvar=False)
-    R[np.isnan(R)] = 0
-    jj, ii = np.meshgrid(np.arange(m2), np.arange(m2))
-    R[np.abs(ii - jj) > band] = 0
-    np.fill_diagonal(R, 1.0)
-    return sparse.csc_matrix(R)
-
 
 def sumstats(A, seed, causal=0.2, N=2000):
     rng = np.random.default_rng(seed)
