@@ -115,6 +115,7 @@ SIGNATURES = {
     "bsn_op_prod": (C.c_int, [vp, vp, i64, C.c_int, vp, i64]),
     "bsn_op_cprod": (C.c_int, [vp, vp, i64, C.c_int, vp, i64]),
     "bsn_op_sync": (C.c_int, [vp]),
+    "bsn_op_last_kernel": (C.c_int, [vp, C.c_char_p, i64]),
     "bsn_bed_randomsvd": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, C.POINTER(SvdOptions),
                                     f64p, f64p, f64p, C.POINTER(SvdInfo)]),
     "bsn_bed_tcrossprod": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p]),

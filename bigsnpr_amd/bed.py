@@ -413,6 +413,12 @@ class ScaledOp:
     def sync(self):
         check(_lib.load().bsn_op_sync(self._h))
 
+    def last_kernel(self):
+        """name of the streaming kernel the last prod launched (bsn_op_last_kernel)"""
+        buf = C.create_string_buffer(1024)
+        check(_lib.load().bsn_op_last_kernel(self._h, buf, 1024))
+        return buf.value.decode()
+
     def close(self):
         if self._h is not None:
             _lib.load().bsn_op_destroy(self._h)

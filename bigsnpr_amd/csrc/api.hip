@@ -1033,6 +1033,24 @@ int bsn_bed_streaming_kernels(bsn_bed *bed, char *buf, int64_t len) {
   });
 }
 
+// Name (as bsn_bed_streaming_kernels gives it) of the streaming kernel the last bsn_op_prod on this operator launched.
+int bsn_op_last_kernel(bsn_op *op, char *buf, int64_t len) {
+  return guarded([&] {
+    if (!buf || len < 1) fail("bsn_op_last_kernel: no buffer");
+    buf[0] = 0;
+    if (!op->last_kernel) return;
+    const char *mangled = hipKernelNameRefByPtr(op->last_kernel, op->bed->stream);
+    if (!mangled) return;
+    int status = 1;
+    char *dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+    std::string name = (status == 0 && dem) ? dem : mangled;
+    free(dem);
+    const size_t par = name.find('(');
+    if (par != std::string::npos) name.resize(par);
+    snprintf(buf, (size_t)len, "%s", name.c_str());
+  });
+}
+
 int bsn_bed_sample_major(bsn_bed *bed, int *built) {
   return guarded([&] {
     BSN_HIP(hipSetDevice(bed->device));

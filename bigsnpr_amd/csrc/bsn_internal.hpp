@@ -187,6 +187,7 @@ struct bsn_op {
   std::vector<int> ev_kind;
   std::vector<char> ev_more;   // 1: a further piece of the previous launch (prof_begin)
   const void *prof_kernel[kProfKinds] = {};  // host stub of the last kernel launched under each kind
+  const void *last_kernel = nullptr;         // ... and of the last product launch, profiled or not (bsn_op_last_kernel)
   ~bsn_op() {
     for (auto e : ev_begin) (void)hipEventDestroy(e);
     for (auto e : ev_end) (void)hipEventDestroy(e);

@@ -23,11 +23,13 @@
 #include <cstdlib>
 
 #include "bsn_internal.hpp"
+#include "prodt_sparse.hpp"
 #include <type_traits>
 
 namespace bsn {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v8i __attribute__((ext_vector_type(8)));
 
 // Every launch of a streaming kernel notes WHICH instantiation it was: prof_end files it under the launch's kind and
 // bsn_bed_streaming_kernels reports the names, so that a committed counter record (profiles/pmc_traffic.json) can be
@@ -149,6 +151,10 @@ __global__ void k_absmax(const double *X, int64_t ldx, int64_t len, const double
 // Layout: q[(k/16) * (nplanes*ncol) + plane*ncol + col][16 B], col = v*S + s.
 // PERM = 1 (cprod operand): sample e of the 16 is stored at byte (e%4)*4 + e/4, the
 // order in which k_cprod's decode emits them;  PERM = 0 (prod operand): natural.
+// PERM = 2 (operand of k_prodT's sparse form, prodt_sparse.hpp; mode 1 only): natural order, the two planes
+// byte-interleaved as (A_e, B_e) — row 0 of the pair holds variants 0..7, row 1 variants 8..15 — and the second plane
+// holds B itself, not B - 3 A: a missing genotype selects the B slot alone, and 3 A + (B - 3 A) = B.  The sums and the
+// scale are those of the other orders (k_absmax keeps the |b - 3 a| term), so qscale and sum2 do not change.
 // The values are read coalesced and handed over through LDS (row stride 17 against bank
 // conflicts); the digit bytes are packed in registers (S and PERM are compile-time).
 template <int S, int PERM>
@@ -236,8 +242,8 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
       shi2 += B >> 24; slo2 += B & 0xFFFFFF;
       // scaled product: the genotype plane is the raw code (3 for a missing value), so the
       // missing-value plane carries c w - 3 w, in exact integers: 3 A + (B - 3 A) - B == 0
-      if (raw3 & 1) B -= 3 * A;
-      const int pos = PERM ? ((e & 3) * 4 + (e >> 2)) : e;
+      if ((raw3 & 1) && PERM != 2) B -= 3 * A;
+      const int pos = PERM == 1 ? ((e & 3) * 4 + (e >> 2)) : e;
 #ifdef BSN_ABLATION
       // BSN_DIGITS=2 (timing only: the finalize kernels read balanced base-256 digits): sign x 7-bit magnitude chunks
       const bool sm = (raw3 >> 8) == 2;
@@ -255,8 +261,14 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
 #endif
         A = (A - da) >> 8;
         B = (B - db) >> 8;
-        pk[0][s][pos >> 2] |= (uint32_t)(uint8_t)da << (8 * (pos & 3));
-        pk[1][s][pos >> 2] |= (uint32_t)(uint8_t)db << (8 * (pos & 3));
+        if constexpr (PERM == 2) {
+          const int r = prodt_sparse_row(e), ba = prodt_sparse_byte(e, 0), bb = prodt_sparse_byte(e, 1);
+          pk[r][s][ba >> 2] |= (uint32_t)(uint8_t)da << (8 * (ba & 3));
+          pk[r][s][bb >> 2] |= (uint32_t)(uint8_t)db << (8 * (bb & 3));
+        } else {
+          pk[0][s][pos >> 2] |= (uint32_t)(uint8_t)da << (8 * (pos & 3));
+          pk[1][s][pos >> 2] |= (uint32_t)(uint8_t)db << (8 * (pos & 3));
+        }
       }
     }
     for (int p = 0; p < nplanes; p++)
@@ -836,7 +848,13 @@ __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, i
 // exact int64 like k_prod's): 782 workgroups of 512 samples alone would fill 3.05 rounds of 256 CUs.
 // The copy is CHUNK-MAJOR (bsn_bed::d_smaj): byte of the operator's first variant in a sample row (col0 / 4, a multiple of 16).
 // NASKIP: as in k_cprod — the missing-value plane of a K-step (16 samples x 64 variants) only when it has a missing code.
-template <int NB, bool HASQ, int TILES = 2, int WAVES = 16, int TAG = 0, int SGB = 3, bool NASKIP = false>
+// SPARSE (prodt_sparse.hpp): both planes in ONE v_smfmac_i32_16x16x128_i8 per tile and column block.  Of a genotype's
+// code term and missing term at most one is non-zero, so with the digit rows interleaved as (A_e, B_e) (k_quant, PERM = 2)
+// the 16 variants of a decoded dword are 16 compressed values over 32 dense K: half the matrix instructions, the same
+// integer per sample (3 A + (B - 3 A) = B) -> bit-identical.  The LDS panel has the same bytes, rows and addressing.
+// (Reading the digit operands one K-step ahead with three column blocks as well, now that 4 + 1 operand registers
+// replace 8, measured level in the skeleton of tools/ubench/smfmac_parts.hip — 26.5 ms either way — and is not built.)
+template <int NB, bool HASQ, int TILES = 2, int WAVES = 16, int TAG = 0, int SGB = 3, bool NASKIP = false, bool SPARSE = false>
 __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict__ simg, int64_t rows_t, int64_t chunk0,
                                                       int nchunks, int cps,
                                                       const int8_t *__restrict__ wq, int32_t *__restrict__ acc_out,
@@ -910,13 +928,22 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (SGB & 2) __builtin_amdgcn_s_setprio(2);
     constexpr int NP = HASQ ? 2 : 1;
+    static_assert(!SPARSE || (HASQ && !NASKIP), "the sparse form replaces the two planes of the plain pass");
     constexpr bool PFB = NB <= 2;   // (as in k_cprod: no second register copy of the digit operands with three column blocks)
     uint4 bv[NP][NB], bn[PFB ? NP : 1][PFB ? NB : 1];
+    // 16-byte row of the panel that register p of the lane's digit operand takes in K-step kb (= it * 16 + d).  Dense: row p
+    // (the plane) of the lane group's own block of 16 variants.  Sparse: the instruction's B operand holds dense K
+    // 64 p + 16 g .. + 15 in register half p of lane group g, and its A operand of lane group ga the compressed values of
+    // dense K 32 ga .. 32 ga + 31 (tools/ubench/smfmac_parts.hip) — so half p is row (g & 1), variants 8 (g & 1) .. + 7 with
+    // their (A_e, B_e) pairs, of the block that lane group 2 p + (g >> 1) decodes.
+    auto xrow = [&](const int kb, const int p) -> int {
+      return SPARSE ? (kb + (2 * p + (g >> 1)) * 4) * 2 + (g & 1) : (kb + g * 4) * 2 + p;
+    };
 #pragma unroll
     for (int p = 0; p < NP; p++)
 #pragma unroll
       for (int nb = 0; nb < NB; nb++) {
-        bv[p][nb] = xs[SET][((g * 4) * 2 + p) * NCOL + nb * 16 + c];
+        bv[p][nb] = xs[SET][xrow(0, p) * NCOL + nb * 16 + c];
         if constexpr (PFB) bn[p][nb] = bv[p][nb];
       }
 #pragma unroll
@@ -928,19 +955,31 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
 #pragma unroll
             for (int p = 0; p < NP; p++)
 #pragma unroll
-              for (int nb = 0; nb < NB; nb++) bv[p][nb] = xs[SET][((it * 16 + g * 4 + d) * 2 + p) * NCOL + nb * 16 + c];
+              for (int nb = 0; nb < NB; nb++) bv[p][nb] = xs[SET][xrow(it * 16 + d, p) * NCOL + nb * 16 + c];
           }
         } else if (it * 4 + d + 1 < LD * 4) {
           const int itn = (it * 4 + d + 1) / 4, dn = (it * 4 + d + 1) % 4;
 #pragma unroll
           for (int p = 0; p < NP; p++)
 #pragma unroll
-            for (int nb = 0; nb < NB; nb++) bn[p][nb] = xs[SET][((itn * 16 + g * 4 + dn) * 2 + p) * NCOL + nb * 16 + c];
+            for (int nb = 0; nb < NB; nb++) bn[p][nb] = xs[SET][xrow(itn * 16 + dn, p) * NCOL + nb * 16 + c];
         }
 #pragma unroll
         for (int t = 0; t < TILES; t++) {
           const uint32_t w = d == 0 ? ga[SET][t][it].x : d == 1 ? ga[SET][t][it].y
                              : d == 2 ? ga[SET][t][it].z : ga[SET][t][it].w;
+          if constexpr (SPARSE) {
+            uint32_t av[4], idx;
+            prodt_sparse_decode(w, av, idx);
+            const v4i a = {(int)av[0], (int)av[1], (int)av[2], (int)av[3]};
+#pragma unroll
+            for (int nb = 0; nb < NB; nb++) {
+              const v8i b = {(int)bv[0][nb].x, (int)bv[0][nb].y, (int)bv[0][nb].z, (int)bv[0][nb].w,
+                             (int)bv[1][nb].x, (int)bv[1][nb].y, (int)bv[1][nb].z, (int)bv[1][nb].w};
+              acc[t][nb] = __builtin_amdgcn_smfmac_i32_16x16x128_i8(a, b, acc[t][nb], (int)idx, 0, 0);
+            }
+            continue;
+          }
           const uint32_t s0 = w & 0x03030303u, s1 = (w >> 2) & 0x03030303u, s2 = (w >> 4) & 0x03030303u,
                          s3 = (w >> 6) & 0x03030303u;
           const v4i a0 = {(int)s0, (int)s1, (int)s2, (int)s3};
@@ -977,9 +1016,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
       for (int it = 0; it < LD; it++) ga[SET][t][it] = gload(t, ch2, it * 64);
     if constexpr (SGB & 1) {
       // the explicit MFMA / decode pipeline of k_cprod (0x008 MFMA, 0x002 VALU, 0x100 DS read, 0x020 VMEM read)
-      constexpr int VSTEP = TILES * (7 + (HASQ ? 4 : 0)), MSTEP = TILES * NP * NB;
+      // (sparse: 18 VALU — prodt_sparse_decode as compiled — against NB matrix instructions per tile)
+      constexpr int VSTEP = TILES * (SPARSE ? 18 : 7 + (HASQ ? 4 : 0)), MSTEP = TILES * (SPARSE ? NB : NP * NB);
       __builtin_amdgcn_sched_group_barrier(0x100, NP * NB, 0);
-      __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, SPARSE ? 9 : 7, 0);
       auto slots = [&](auto self, auto IC) {
         constexpr int i = decltype(IC)::value;
         if constexpr (i < MSTEP) {
@@ -1351,6 +1391,7 @@ static void quantise(bsn_op *op, const double *d_X, int64_t ldx, int64_t len, in
   if (const char *dg = getenv("BSN_DIGITS")) raw3 |= atoi(dg) << 8;
 #endif
   if (bytes) permute = 0;  // the byte image holds the samples of a 16-block in natural order
+  if (permute == 2 && !(mode == 1 && (raw3 & 1))) fail("internal: the interleaved digit rows are the scaled product's");
   // meta: kMetaVecs records, then the slice maxima of k_absmax (kMetaVecs x 256 x 2 doubles)
   double *part = (double *)(meta + kMetaVecs);
   int gx = 0;
@@ -1372,7 +1413,10 @@ static void quantise(bsn_op *op, const double *d_X, int64_t ldx, int64_t len, in
   const dim3 qgrid((unsigned)((nblk + 63) / 64), nvec);
 #define BSN_QUANT(SV)                                                                                  \
   case SV:                                                                                             \
-    if (permute)                                                                                       \
+    if (permute == 2)                                                                                  \
+      hipLaunchKernelGGL((k_quant<SV, 2>), qgrid, dim3(64), 0, st, d_X, ldx, len, len_pad, qc, qsc, mode, \
+                         ncol, meta, q, vstep, voff, raw3, part, gx);                                  \
+    else if (permute)                                                                                  \
       hipLaunchKernelGGL((k_quant<SV, 1>), qgrid, dim3(64), 0, st, d_X, ldx, len, len_pad, qc, qsc, mode, \
                          ncol, meta, q, vstep, voff, raw3, part, gx);                                  \
     else                                                                                               \
@@ -1978,15 +2022,27 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
   if (!smaj) ky = (int)((m_pad + mc - 1) / mc);
   // complete variants: the missing-value plane is all zero, skip its look-ups and MFMAs
   const bool has_q = lutQ != 0u && !(op->no_na && lutQ == kLutNA);
+  // k_prodT<3> with the missing-value plane runs in its sparse form (one matrix instruction for both planes,
+  // prodt_sparse.hpp: 27.8 against 29.5 ms per pass at 400K x 1M); with two column blocks the 18-instruction decode
+  // outweighs the two matrix instructions it saves per tile (23.3 against 22.4 ms, profiles/sparse_prod_ab.txt) and the
+  // dense kernel stays.  BSN_NO_SPARSE_PROD=1: the dense two-plane kernel (A/B switch, bit-identical; read on every call)
+  // Its per-slice sums differ from the dense kernel's by carries between the digit slices, and k_prod_final adds the
+  // slices in fp64: the same Y needs that sum exact — below 2^53 for the largest panel the scale admits (codes up to 3,
+  // integers below 2^(8S-1), m_pad variants).  True for every 24-bit panel; the 56-bit panels of a wide solve keep the dense kernel.
+  const bool sparse_ok = smaj && has_q && getenv("BSN_NO_SPARSE_PROD") == nullptr &&
+                         ldexp(3.0 * (double)m_pad, 8 * S - 1) < 9007199254740992.0;
   for (int v0 = 0; v0 < nvec; v0 += vmax) {
     int nv = nvec - v0 < vmax ? nvec - v0 : vmax;
     int NB = pick_nb(nv * S), ncol = 16 * NB;
+    // (where the host rule takes the kernels that skip the plane of K-steps without a missing code, they stay: nearly
+    // complete data, 1e-4 missing, 186.5 ms per solve on them against 198.7 on the sparse form)
+    const bool sparse = sparse_ok && NB == 3 && !op->na_skip_p;
     int8_t *q = op->d_q.ensure((size_t)(npad > m_pad ? npad : m_pad) * kMaxCols * 2);
     size_t acc_need = (size_t)ky * npad * ncol;
     if (acc_need < (size_t)2 * op->m * kMaxCols) acc_need = (size_t)2 * op->m * kMaxCols;
     int32_t *acc = op->d_acc.ensure(acc_need);
-    // (k_prodT decodes like k_cprod: its digit rows take the crossproduct's byte order)
-    quantise(op, d_X + (int64_t)v0 * ldx, ldx, op->m, m_pad, nv, mode, S, ncol, smaj && NB >= 2 ? 1 : 0, 0, meta, q,
+    // (k_prodT decodes like k_cprod: its digit rows take the crossproduct's byte order; the sparse form its own)
+    quantise(op, d_X + (int64_t)v0 * ldx, ldx, op->m, m_pad, nv, mode, S, ncol, smaj && NB >= 2 ? (sparse ? 2 : 1) : 0, 0, meta, q,
              d_W2 ? d_W2 + (int64_t)v0 * ldx : nullptr);
     dim3 grid((unsigned)wgx, (unsigned)ky);
     prof_begin(op, NB == 3 ? 5 : 1);
@@ -2011,9 +2067,14 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
 #define BSN_PRODT_SKIP(NBV, GRID, BS, STRIDE, OFF)                                                                   \
   BSN_KLAUNCH((k_prodT<NBV, true, 2, 16, 0, 0, true>), GRID, dim3(1024), 0, b->stream, b->d_smaj, b->rows_smaj,       \
               op->col0 / 512, nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF)
+#define BSN_PRODT_SPARSE(TAGV, GRID, BS, STRIDE, OFF)                                                                \
+  BSN_KLAUNCH((k_prodT<3, true, 2, 16, TAGV, 3, false, true>), GRID, dim3(1024), 0, b->stream, b->d_smaj,  \
+              b->rows_smaj, op->col0 / 512, nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF)
 #define BSN_PRODT(HASQV, TAGV, GRID, BS, STRIDE, OFF)                                                                \
   do {                                                                                                               \
-    if (HASQV && op->na_skip_p) {   /* the missing-value plane only where a K-step has a missing code */             \
+    if (HASQV && sparse) {   /* (three column blocks) */                                                             \
+      BSN_PRODT_SPARSE(TAGV, GRID, BS, STRIDE, OFF);                                                                 \
+    } else if (HASQV && op->na_skip_p) {   /* the missing-value plane only where a K-step has a missing code */      \
       if (NB == 2) BSN_PRODT_SKIP(2, GRID, BS, STRIDE, OFF);                                                         \
       else BSN_PRODT_SKIP(3, GRID, BS, STRIDE, OFF);                                                                 \
     } else if (NB == 2) BSN_PRODT_(2, HASQV, TAGV, GRID, BS, STRIDE, OFF);                                           \
@@ -2048,6 +2109,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
       if (has_q) { if (warm) BSN_PRODT(true, 1, grid, 0, 0, 0); else BSN_PRODT(true, 0, grid, 0, 0, 0); }
       else { if (warm) BSN_PRODT(false, 1, grid, 0, 0, 0); else BSN_PRODT(false, 0, grid, 0, 0, 0); }
 #undef BSN_PRODT
+#undef BSN_PRODT_SPARSE
 #undef BSN_PRODT_SKIP
 #undef BSN_PRODT3
 #undef BSN_PRODT_
@@ -2080,6 +2142,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
       else launch_prod<2, false>(op, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
     }
     prof_end(op);
+    op->last_kernel = g_last_kernel;
     op->passes++;
     if (NB == 1)
       hipLaunchKernelGGL((k_prod_final<16>), dim3((unsigned)((op->n + 255) / 256)), dim3(256), 0, b->stream,

@@ -357,6 +357,8 @@ int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int
  * last bsn_bed_randomsvd on this handle launched, one "kind=name" line per kind (cprod, prod, cprod_stats, warm).
  * bench.py matches them against profiles/pmc_traffic.json before it quotes that record's HBM traffic. */
 int bsn_bed_streaming_kernels(bsn_bed *bed, char *buf, int64_t len);
+/* ... and the name of the streaming kernel the last bsn_op_prod of an operator launched (empty before the first). */
+int bsn_op_last_kernel(bsn_op *op, char *buf, int64_t len);
 /* Streaming layout.  The passes of bsn_bed_randomsvd / bsn_bed_prodvec / bsn_bed_cprodvec over a 64-aligned
  * contiguous range of variants run faster (about 8 %) on a second copy of the 2-bit image stored in tiles of
  * 64 variants x 1024 samples (16 KB): every load of a wavefront then lands in one contiguous run instead of 16 -
