@@ -140,6 +140,9 @@ SIGNATURES = {
                                     f64p, f64p]),
     "bsn_ldpred2_gibbs_sampling": (C.c_int, [vp, f64p, f64p, i64, i64p, C.c_double, C.c_double, C.c_int32, C.c_uint64,
                                              C.c_int, C.c_int, C.c_uint64, f64p, f64p]),
+    "bsn_ldpred2_auto": (C.c_int, [vp, f64p, f64p, f64p, i64, i64p, f64p, u64p, i64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                   C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, C.c_uint64, f64p, f64p, f64p, f64p, f64p, f64p, f64p, f64p]),
     "bsn_sfbm_prodvec": (C.c_int, [vp, f64p, i64p, i64, f64p]),
     "bsn_sfbm_ld_scores": (C.c_int, [vp, i64p, i64, f64p]),
     "bsn_sfbm_solve_sym": (C.c_int, [vp, f64p, f64p, i64p, i64, C.c_double, C.c_int32, f64p, i32p, f64p]),

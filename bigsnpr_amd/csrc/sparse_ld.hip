@@ -25,6 +25,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "bsn_internal.hpp"
+#include "gibbs_auto.hpp"
 #include "gibbs_step.hpp"
 
 struct bsn_sfbm {
@@ -235,6 +236,60 @@ __global__ __launch_bounds__(64) void k_lassosum2(const int64_t *__restrict__ P,
 constexpr int kGibbsThreads = 256;
 constexpr int kGibbsAxpy = 8;   // entries per thread and round of a column update (2 048 per round)
 
+// WINDOW: rows wlo .. whi of the chain's dotprods are in the ring.  Before a block with the envelope [nlo, nhi] is worked
+// on, the rows below nlo go back to HBM and the rows up to nhi come from it.
+__device__ __forceinline__ void ring_advance(double *dot, double *ring, int32_t W, int32_t nlo, int32_t nhi, int32_t &wlo,
+                                             int32_t &whi, int tid) {
+  if (nlo > wlo || nhi > whi) {
+    const int32_t out_end = nlo < whi + 1 ? nlo : whi + 1;    // rows wlo .. out_end - 1 leave
+    for (int32_t r = wlo + tid; r < out_end; r += kGibbsThreads) dot[r] = ring[r % W];
+    if (out_end > wlo) __syncthreads();   // a row that enters may take the place of one that leaves
+    const int32_t in_from = nlo > whi + 1 ? nlo : whi + 1;    // rows in_from .. nhi enter
+    for (int32_t r = in_from + tid; r <= nhi; r += kGibbsThreads) ring[r % W] = dot[r];
+    wlo = nlo;
+    whi = nhi;
+    __syncthreads();
+  }
+}
+
+// the end of a sweep: what is left in the ring goes back to HBM
+__device__ __forceinline__ void ring_flush(double *dot, const double *ring, int32_t W, int32_t wlo, int32_t whi, int tid) {
+  for (int32_t r = wlo + tid; r <= whi; r += kGibbsThreads) dot[r] = ring[r % W];
+  __syncthreads();
+}
+
+// dotprods += shift * (stored entries e0 .. e1 - 1 of one column), by all threads of the workgroup: each row once
+template <bool WINDOW>
+__device__ __forceinline__ void add_column(const int32_t *__restrict__ I, const double *__restrict__ X, int64_t e0, int64_t e1,
+                                           double shift, double *dot, double *ring, int32_t wbase, int32_t W, int tid) {
+  for (int64_t eb = e0 + tid; eb < e1; eb += kGibbsThreads * kGibbsAxpy) {
+    int32_t r[kGibbsAxpy];
+    double xv[kGibbsAxpy], dv[kGibbsAxpy];
+#pragma unroll
+    for (int u = 0; u < kGibbsAxpy; u++) {
+      const int64_t e = eb + kGibbsThreads * u;
+      r[u] = e < e1 ? I[e] : 0;
+      xv[u] = e < e1 ? X[e] : 0.0;
+    }
+    if (WINDOW) {
+#pragma unroll
+      for (int u = 0; u < kGibbsAxpy; u++)
+        if (eb + kGibbsThreads * u < e1) {
+          int32_t q = r[u] - wbase;
+          if (q >= W) q -= W;
+          ring[q] = ring[q] + xv[u] * shift;
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < kGibbsAxpy; u++)
+        if (eb + kGibbsThreads * u < e1) dv[u] = dot[r[u]];
+#pragma unroll
+      for (int u = 0; u < kGibbsAxpy; u++)
+        if (eb + kGibbsThreads * u < e1) dot[r[u]] = dv[u] + xv[u] * shift;
+    }
+  }
+}
+
 struct GibbsArgs {
   const int64_t *P;
   const int32_t *I;
@@ -285,17 +340,7 @@ __global__ __launch_bounds__(kGibbsThreads) void k_ldpred2_gibbs(const GibbsArgs
     int64_t b = 0;
     for (int64_t j0 = 0; j0 < m; j0 += 64, b++) {
       if (WINDOW) {
-        const int32_t nlo = a.blo[b], nhi = a.bhi[b];
-        if (nlo > wlo || nhi > whi) {
-          const int32_t out_end = nlo < whi + 1 ? nlo : whi + 1;    // rows wlo .. out_end - 1 leave
-          for (int32_t r = wlo + tid; r < out_end; r += kGibbsThreads) dot[r] = ring[r % W];
-          if (out_end > wlo) __syncthreads();   // a row that enters may take the place of one that leaves
-          const int32_t in_from = nlo > whi + 1 ? nlo : whi + 1;    // rows in_from .. nhi enter
-          for (int32_t r = in_from + tid; r <= nhi; r += kGibbsThreads) ring[r % W] = dot[r];
-          wlo = nlo;
-          whi = nhi;
-          __syncthreads();
-        }
+        ring_advance(dot, ring, W, a.blo[b], a.bhi[b], wlo, whi, tid);
         wbase = wlo / W * W;
       }
       const int64_t j = j0 + lane;
@@ -351,47 +396,226 @@ __global__ __launch_bounds__(kGibbsThreads) void k_ldpred2_gibbs(const GibbsArgs
           cb = s.beta;
           if (writer) cur[j] = s.beta;
         }
-        const int64_t e1 = lane_index(pb, f);
-        for (int64_t eb = lane_index(pa, f) + tid; eb < e1; eb += kGibbsThreads * kGibbsAxpy) {
-          int32_t r[kGibbsAxpy];
-          double xv[kGibbsAxpy], dv[kGibbsAxpy];
-#pragma unroll
-          for (int u = 0; u < kGibbsAxpy; u++) {
-            const int64_t e = eb + kGibbsThreads * u;
-            r[u] = e < e1 ? a.I[e] : 0;
-            xv[u] = e < e1 ? a.X[e] : 0.0;
-          }
-          if (WINDOW) {
-#pragma unroll
-            for (int u = 0; u < kGibbsAxpy; u++)
-              if (eb + kGibbsThreads * u < e1) {
-                int32_t q = r[u] - wbase;
-                if (q >= W) q -= W;
-                ring[q] = ring[q] + xv[u] * shift;
-              }
-          } else {
-#pragma unroll
-            for (int u = 0; u < kGibbsAxpy; u++)
-              if (eb + kGibbsThreads * u < e1) dv[u] = dot[r[u]];
-#pragma unroll
-            for (int u = 0; u < kGibbsAxpy; u++)
-              if (eb + kGibbsThreads * u < e1) dot[r[u]] = dv[u] + xv[u] * shift;
-          }
-        }
+        add_column<WINDOW>(a.I, a.X, lane_index(pa, f), lane_index(pb, f), shift, dot, ring, wbase, W, tid);
         __syncthreads();   // the additions above, before any thread reads dotprods again
         from = f + 1;
         if (from >= 64) break;
       }
     }
-    if (WINDOW) {
-      for (int32_t r = wlo + tid; r <= whi; r += kGibbsThreads) dot[r] = ring[r % W];
-      __syncthreads();
-    }
+    if (WINDOW) ring_flush(dot, ring, W, wlo, whi, tid);
     if (!SAMPLING && gap > a.gap0) diverged = true;
   }
   if (!SAMPLING) {
     __syncthreads();   // wave 0's avg_beta, before every thread reads it
     for (int64_t j = tid; j < m; j += kGibbsThreads) a.out[g * m + j] = diverged ? __builtin_nan("") : avg[j] / a.num_iter;
+  }
+  if (tid == 0) a.ticks[g] = wall_clock64() - t0;
+}
+
+// ---- LDpred2-auto (src/ldpred2-auto.cpp:57-202) ------------------------------------------------------------------------------
+// k_ldpred2_gibbs's structure with the coordinate step of gibbs_auto.hpp: one workgroup per chain, 64 coordinates decided
+// at a time, the first whose diff is not 0 commits.  cur_h2_est receives a term from committing coordinates only, one per
+// decision, so it is added in j order; gap and ind_causal (wave 0 appends, in j order) take every decided causal
+// coordinate, the three accumulators every decided coordinate.  The epilogue of a sweep runs on all 256 threads: every
+// thread forms p (the same draws, the same operations), the threads stride over the bootstrap and over the sums of the
+// MLE, whose partial sums meet in the fixed tree of gibbs_auto.hpp (inside each wave by lane exchange, across the four
+// waves through twelve LDS doubles, kept twice so that one barrier per evaluation is enough).  The static LDS comes on
+// top of the ring: 128 KiB + 192 B of the CU's 160 KiB.
+struct AutoArgs {
+  const int64_t *P;
+  const int32_t *I;
+  const double *X;
+  int64_t m2, m;
+  const double *beta_hat, *n_vec, *log_var;
+  const int64_t *ind_sub;
+  const double *p_init;
+  const uint64_t *stream;
+  const int32_t *order;
+  const int32_t *blo, *bhi;
+  int32_t ring_rows;
+  int64_t g0;
+  double gap0, h2_init, shrink_corr, p_lo, p_hi, alpha_lo, alpha_hi, mean_ld;
+  int burn_in, num_iter, report_step, n_report, no_jump_sign, use_mle;
+  uint64_t seed;
+  double *dots, *curs, *avg_beta, *avg_postp, *avg_hat, *boot_a, *boot_b;   // per chain of the batch
+  int32_t *causal;
+  double *beta_est, *postp_est, *corr_est;   // [m x G]
+  double *sample_beta;                       // [m x n_report x G], zeroed
+  double *path_p, *path_h2, *path_alpha;     // [(burn_in + num_iter) x G]
+  uint64_t *ticks;
+};
+
+template <bool WINDOW>
+__global__ __launch_bounds__(kGibbsThreads) void k_ldpred2_auto(const AutoArgs a) {
+  extern __shared__ double ring[];
+  __shared__ double wsum[2][3][4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool writer = tid < 64;
+  const int64_t m = a.m;
+  const int64_t g = a.order[a.g0 + blockIdx.x];
+  double *dot = a.dots + (int64_t)blockIdx.x * a.m2;   // no __restrict__: threads read what other threads stored
+  double *cur = a.curs + (int64_t)blockIdx.x * m;
+  double *avg_beta = a.avg_beta + (int64_t)blockIdx.x * m;
+  double *avg_postp = a.avg_postp + (int64_t)blockIdx.x * m;
+  double *avg_hat = a.avg_hat + (int64_t)blockIdx.x * m;
+  double *ba = a.boot_a + (int64_t)blockIdx.x * m;
+  double *bb = a.boot_b + (int64_t)blockIdx.x * m;
+  int32_t *causal = a.causal + (int64_t)blockIdx.x * m;
+  const uint64_t stream = a.stream[g];
+  const bool use_mle = a.use_mle != 0, no_jump = a.no_jump_sign != 0;
+  const double shrink = a.shrink_corr;
+  const int32_t W = a.ring_rows;
+  const int tot = a.burn_in + a.num_iter;
+  const uint64_t t0 = wall_clock64();
+  double cur_h2 = 0;
+  double h2 = a.h2_init < gibbs::kAutoMinH2 ? gibbs::kAutoMinH2 : a.h2_init;
+  double p = gibbs::clamp_p(a.p_init[g], a.p_lo, a.p_hi);
+  double alpha1 = 0, sigma2 = h2 / (m * p);
+  int ind_report = 0, next_report = a.burn_in + a.report_step - 1;
+  int flip = 0;
+  bool diverged = false;
+  int k = 0;
+  for (; k < tot; k++) {
+    const double inv_odd_p = (1 - p) / p;
+    double gap = 0;
+    int32_t nbc = 0;   // entries of ind_causal
+    int32_t wlo = 0, whi = -1, wbase = 0;
+    if (WINDOW) {
+      wlo = a.blo[0];
+      whi = wlo - 1;
+    }
+    int64_t b = 0;
+    for (int64_t j0 = 0; j0 < m; j0 += 64, b++) {
+      if (WINDOW) {
+        ring_advance(dot, ring, W, a.blo[b], a.bhi[b], wlo, whi, tid);
+        wbase = wlo / W * W;
+      }
+      const int64_t j = j0 + lane;
+      const bool in = j < m;
+      int64_t j2 = 0, pa = 0, pb = 0;
+      int32_t at = 0;
+      double bh = 0, cb = 0;
+      gibbs::Coord c = {};
+      if (in) {
+        j2 = a.ind_sub ? a.ind_sub[j] : j;
+        pa = a.P[j2];
+        pb = a.P[j2 + 1];
+        bh = a.beta_hat[j];
+        cb = cur[j];
+        c = gibbs::coord_auto(a.n_vec[j], use_mle ? a.log_var[j] : 0.0, alpha1, sigma2, inv_odd_p, use_mle,
+                              gibbs::draw(a.seed, stream, (uint32_t)k, (uint32_t)j));
+        if (WINDOW) {
+          at = (int32_t)j2 - wbase;
+          if (at >= W) at -= W;
+        }
+      }
+      int from = 0;   // lanes below `from` are decided
+      for (;;) {
+        const bool act = in && lane >= from;
+        gibbs::StepAuto s = {};
+        double dj = 0;
+        if (act) dj = WINDOW ? ring[at] : dot[j2];
+        // every wave holds its values before any wave, having decided, adds a column: the waves must decide alike
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (act) s = gibbs::step_auto(bh, dj, cb, c, shrink, no_jump);
+        const uint64_t moves = __ballot(act && s.diff != 0);
+        const int f = moves ? __ffsll((unsigned long long)moves) - 1 : 64;   // the first coordinate that changes state
+        const bool decided = act && lane <= f;
+        const uint64_t cz = __ballot(decided && s.causal);
+        const double sq = s.beta * s.beta;
+        for (uint64_t nz = cz; nz; nz &= nz - 1) gap += lane_value(sq, __ffsll((unsigned long long)nz) - 1);
+        if (writer && decided) {
+          if (s.causal) causal[nbc + __popcll(cz & ((1ull << lane) - 1))] = (int32_t)j;
+          if (k >= a.burn_in) {
+            avg_postp[j] += s.postp;
+            avg_beta[j] += s.mean;
+            avg_hat[j] += s.shrunk;
+          }
+        }
+        nbc += __popcll(cz);
+        if (f == 64) break;
+        const double shift = lane_value(s.diff, f);
+        cur_h2 += lane_value(gibbs::h2_term(s), f);
+        if (lane == f) {
+          cb = s.beta;
+          if (writer) cur[j] = s.beta;
+        }
+        add_column<WINDOW>(a.I, a.X, lane_index(pa, f), lane_index(pb, f), shift, dot, ring, wbase, W, tid);
+        __syncthreads();   // the additions above, before any thread reads dotprods again
+        from = f + 1;
+        if (from >= 64) break;
+      }
+    }
+    if (WINDOW) ring_flush(dot, ring, W, wlo, whi, tid);
+    __syncthreads();   // wave 0's curr_beta and ind_causal, before every thread reads them
+    if (gap > a.gap0) {
+      diverged = true;
+      break;
+    }
+    p = gibbs::next_p(nbc, m, a.mean_ld, a.p_lo, a.p_hi, a.seed, stream, (uint32_t)k);
+    h2 = cur_h2 < gibbs::kAutoMinH2 ? gibbs::kAutoMinH2 : cur_h2;
+    if (use_mle) {
+      if (nbc > 0) {
+        for (int32_t kk = tid; kk < nbc; kk += kGibbsThreads) {
+          const int32_t jj = causal[gibbs::boot_index(nbc, a.seed, stream, (uint32_t)k, (uint32_t)kk)];
+          const double v = cur[jj];
+          ba[kk] = a.log_var[jj];
+          bb[kk] = v * v;
+        }
+        __syncthreads();
+        const gibbs::MlePar par = gibbs::mle_solve(
+            [&](double al) {
+              gibbs::MleSums t = gibbs::mle_partial(ba, bb, nbc, al, tid);
+              t.a = gibbs::tree_wave(t.a);
+              t.S = gibbs::tree_wave(t.S);
+              t.Sa = gibbs::tree_wave(t.Sa);
+              double(*w)[4] = wsum[flip];
+              flip ^= 1;
+              if (lane == 0) {
+                w[0][wave] = t.a;
+                w[1][wave] = t.S;
+                w[2][wave] = t.Sa;
+              }
+              __syncthreads();
+              t.a = gibbs::tree_four(w[0][0], w[0][1], w[0][2], w[0][3]);
+              t.S = gibbs::tree_four(w[1][0], w[1][1], w[1][2], w[1][3]);
+              t.Sa = gibbs::tree_four(w[2][0], w[2][1], w[2][2], w[2][3]);
+              return t;
+            },
+            nbc, a.alpha_lo, a.alpha_hi, sigma2);
+        alpha1 = par.alpha1;
+        sigma2 = par.sigma2;
+      }
+    } else {
+      sigma2 = h2 / (m * p);
+    }
+    if (tid == 0) {
+      a.path_p[g * tot + k] = p;
+      a.path_h2[g * tot + k] = h2;
+      a.path_alpha[g * tot + k] = use_mle ? alpha1 - 1 : __builtin_nan("");
+    }
+    if (k == next_report) {
+      double *col = a.sample_beta + (g * a.n_report + ind_report) * m;
+      for (int32_t kk = tid; kk < nbc; kk += kGibbsThreads) {
+        const int32_t jj = causal[kk];
+        col[jj] = cur[jj];
+      }
+      ind_report++;
+      next_report += a.report_step;
+    }
+    __syncthreads();   // the reads of curr_beta and ind_causal above, before wave 0 writes them in the next sweep
+  }
+  const double nan = __builtin_nan("");
+  for (int64_t j = tid; j < m; j += kGibbsThreads) {
+    a.beta_est[g * m + j] = diverged ? nan : avg_beta[j] / a.num_iter;
+    a.postp_est[g * m + j] = diverged ? nan : avg_postp[j] / a.num_iter;
+    a.corr_est[g * m + j] = diverged ? nan : avg_hat[j] / a.num_iter;
+  }
+  for (int kk = k + tid; kk < tot; kk += kGibbsThreads) {   // the sweeps a diverged chain did not finish
+    a.path_p[g * tot + kk] = nan;
+    a.path_h2[g * tot + kk] = nan;
+    a.path_alpha[g * tot + kk] = nan;
   }
   if (tid == 0) a.ticks[g] = wall_clock64() - t0;
 }
@@ -842,6 +1066,126 @@ void run_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, i
   }
 }
 
+// bsn_ldpred2_auto: G chains of LDpred2-auto, batched as run_gibbs batches its chains.  The checks come before any device work.
+void run_auto(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, const double *log_var, int64_t m,
+              const int64_t *ind_sub, const double *p_init, const uint64_t *stream, int64_t G, double h2_init, int burn_in,
+              int num_iter, int report_step, int no_jump_sign, double shrink_corr, int use_mle, double p_lo, double p_hi,
+              double alpha_lo, double alpha_hi, double mean_ld, uint64_t seed, double *beta_est, double *postp_est,
+              double *corr_est, double *sample_beta, double *path_p, double *path_h2, double *path_alpha, double *seconds_out) {
+  const char *what = "bsn_ldpred2_auto";
+  if (!s) fail("%s: NULL 'corr'", what);
+  if (m < 0 || G < 0 || G > 0x7fffffffLL || (m > 0 && (!beta_hat || !n_vec || (use_mle && !log_var))) || (G > 0 && !p_init) ||
+      (m > 0 && G > 0 && (!beta_est || !postp_est || !corr_est)) || (G > 0 && (!path_p || !path_h2 || !path_alpha)))
+    fail("%s: arguments", what);
+  check_ind_sub(s, ind_sub, m, true, what);
+  if (!(h2_init > 0)) fail("'h2_init' should have only positive values.");
+  if (burn_in < 0) fail("'burn_in' should not be negative.");
+  if (num_iter < 1) fail("'num_iter' should be at least 1.");
+  if (report_step < 1) fail("'report_step' should be at least 1.");
+  if ((int64_t)burn_in + num_iter >= (1LL << gibbs::kAutoSweepBits))
+    fail("'burn_in + num_iter' should be below 2^30: the two top bits of a counter's sweep word tell its purpose.");
+  if (!(p_lo > 0 && p_lo <= p_hi && p_hi <= 1)) fail("'p_bounds' should be ordered and in (0, 1].");
+  if (!(alpha_lo <= alpha_hi)) fail("'alpha_bounds' should be ordered.");
+  if (!(shrink_corr == shrink_corr)) fail("'shrink_corr' should not be missing.");
+  if (!(mean_ld > 0)) fail("'mean_ld' should have only positive values.");
+  for (int64_t g = 0; g < G; g++)
+    if (!(p_init[g] == p_init[g])) fail("'vec_p_init' should not have missing values.");
+  if (report_step > num_iter) report_step = num_iter + 1;   // no column is reported either way
+  const int64_t n_report = num_iter / report_step;
+  if (m > 0 && G > 0 && n_report > 0 && !sample_beta) fail("%s: arguments", what);
+  if (G == 0) return;
+  const int64_t tot = (int64_t)burn_in + num_iter;
+  if (m == 0) {
+    for (int64_t t = 0; t < tot * G; t++) path_p[t] = path_h2[t] = path_alpha[t] = NAN;
+    return;
+  }
+  require_gpu();
+  const double gap0 = lassosum2_gap0(beta_hat, m);   // src/ldpred2-auto.cpp:96-97
+  // the path: run_gibbs's decision
+  const gibbs::Envelope env = gibbs::gibbs_envelope(s->lo.data(), s->hi.data(), ind_sub, m);
+  const bool window = gibbs::gibbs_window_fits(env) && getenv("BSN_GIBBS_NO_WINDOW") == nullptr;
+  const int32_t ring_rows = window ? (int32_t)round_up(env.rows, 64) : 0;
+  std::vector<int32_t> order((size_t)G);   // large p first (R/LDpred2.R:231)
+  for (int64_t g = 0; g < G; g++) order[(size_t)g] = (int32_t)g;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return p_init[x] > p_init[y]; });
+  std::vector<uint64_t> st((size_t)G);
+  for (int64_t g = 0; g < G; g++) st[(size_t)g] = stream ? stream[g] : (uint64_t)g;
+  // as many chains per launch as the free memory holds: dotprods, curr_beta, three accumulators, the bootstrap's two
+  // vectors and ind_causal of each, in 3/4 of what is free once the results and the per-call vectors are taken off
+  size_t free_b = 0, total_b = 0;
+  BSN_HIP(hipMemGetInfo(&free_b, &total_b));
+  const size_t n_est = (size_t)m * (size_t)G, n_smp = (size_t)(m * n_report) * (size_t)G, n_path = (size_t)(tot * G);
+  const int64_t per_g = (s->m2 + 6 * m) * 8 + m * 4;
+  const int64_t fixed_b = (int64_t)(3 * n_est + n_smp + 3 * n_path) * 8 + m * 32 + G * 32 +
+                          (int64_t)(env.lo.size() + env.hi.size()) * 4;
+  const int64_t batch = std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g);
+  if (batch < 1)
+    fail("%s: the results (%lld B) and the state of one chain (%lld B) do not fit the free device memory", what,
+         (long long)fixed_b, (long long)per_g);
+  int clock_khz = 0, dev = 0;
+  BSN_HIP(hipGetDevice(&dev));
+  BSN_HIP(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeWallClockRate, dev));
+  DevBuf<double> d_bh, d_nv, d_lv, d_p, d_dots, d_state, d_est, d_smp, d_path;
+  DevBuf<int64_t> d_ind;
+  DevBuf<int32_t> d_order, d_blo, d_bhi, d_causal;
+  DevBuf<uint64_t> d_stream, d_ticks;
+  BSN_HIP(hipMemcpy(d_bh.ensure((size_t)m), beta_hat, (size_t)m * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_nv.ensure((size_t)m), n_vec, (size_t)m * 8, hipMemcpyHostToDevice));
+  if (use_mle) BSN_HIP(hipMemcpy(d_lv.ensure((size_t)m), log_var, (size_t)m * 8, hipMemcpyHostToDevice));
+  if (ind_sub) BSN_HIP(hipMemcpy(d_ind.ensure((size_t)m), ind_sub, (size_t)m * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_p.ensure((size_t)G), p_init, (size_t)G * 8, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_order.ensure((size_t)G), order.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+  BSN_HIP(hipMemcpy(d_stream.ensure((size_t)G), st.data(), (size_t)G * 8, hipMemcpyHostToDevice));
+  if (window) {
+    BSN_HIP(hipMemcpy(d_blo.ensure(env.lo.size()), env.lo.data(), env.lo.size() * 4, hipMemcpyHostToDevice));
+    BSN_HIP(hipMemcpy(d_bhi.ensure(env.hi.size()), env.hi.data(), env.hi.size() * 4, hipMemcpyHostToDevice));
+  }
+  d_est.ensure(3 * n_est);
+  d_path.ensure(3 * n_path);
+  if (n_smp > 0) BSN_HIP(hipMemsetAsync(d_smp.ensure(n_smp), 0, n_smp * 8, nullptr));   // sample_beta starts as zeros
+  d_dots.ensure((size_t)(batch * s->m2));
+  d_state.ensure((size_t)(batch * m) * 6);   // curr_beta, avg_beta, avg_postp, avg_beta_hat, then the bootstrap's a and b
+  d_causal.ensure((size_t)(batch * m));
+  d_ticks.ensure((size_t)G);
+  AutoArgs a;
+  a.P = s->p.p, a.I = s->i.p, a.X = s->x.p, a.m2 = s->m2, a.m = m;
+  a.beta_hat = d_bh.p, a.n_vec = d_nv.p, a.log_var = use_mle ? d_lv.p : nullptr, a.ind_sub = ind_sub ? d_ind.p : nullptr;
+  a.p_init = d_p.p, a.stream = d_stream.p, a.order = d_order.p;
+  a.blo = d_blo.p, a.bhi = d_bhi.p, a.ring_rows = ring_rows;
+  a.gap0 = gap0, a.h2_init = h2_init, a.shrink_corr = shrink_corr, a.p_lo = p_lo, a.p_hi = p_hi;
+  a.alpha_lo = alpha_lo, a.alpha_hi = alpha_hi, a.mean_ld = mean_ld;
+  a.burn_in = burn_in, a.num_iter = num_iter, a.report_step = report_step, a.n_report = (int)n_report;
+  a.no_jump_sign = no_jump_sign, a.use_mle = use_mle, a.seed = seed;
+  const size_t bm = (size_t)(batch * m);
+  a.dots = d_dots.p, a.curs = d_state.p, a.avg_beta = d_state.p + bm, a.avg_postp = d_state.p + 2 * bm;
+  a.avg_hat = d_state.p + 3 * bm, a.boot_a = d_state.p + 4 * bm, a.boot_b = d_state.p + 5 * bm, a.causal = d_causal.p;
+  a.beta_est = d_est.p, a.postp_est = d_est.p + n_est, a.corr_est = d_est.p + 2 * n_est, a.sample_beta = d_smp.p;
+  a.path_p = d_path.p, a.path_h2 = d_path.p + n_path, a.path_alpha = d_path.p + 2 * n_path, a.ticks = d_ticks.p;
+  const size_t lds = (size_t)ring_rows * 8;
+  auto kernel = window ? k_ldpred2_auto<true> : k_ldpred2_auto<false>;
+  if (window) BSN_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  for (int64_t g0 = 0; g0 < G; g0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, G - g0);
+    BSN_HIP(hipMemsetAsync(d_dots.p, 0, (size_t)(nb * s->m2) * 8, nullptr));
+    BSN_HIP(hipMemsetAsync(d_state.p, 0, bm * 4 * 8, nullptr));   // curr_beta and the accumulators
+    a.g0 = g0;
+    kernel<<<(unsigned)nb, kGibbsThreads, lds>>>(a);
+    BSN_HIP(hipGetLastError());
+  }
+  BSN_HIP(hipMemcpy(beta_est, a.beta_est, n_est * 8, hipMemcpyDeviceToHost));
+  BSN_HIP(hipMemcpy(postp_est, a.postp_est, n_est * 8, hipMemcpyDeviceToHost));
+  BSN_HIP(hipMemcpy(corr_est, a.corr_est, n_est * 8, hipMemcpyDeviceToHost));
+  if (n_smp > 0) BSN_HIP(hipMemcpy(sample_beta, d_smp.p, n_smp * 8, hipMemcpyDeviceToHost));
+  BSN_HIP(hipMemcpy(path_p, a.path_p, n_path * 8, hipMemcpyDeviceToHost));
+  BSN_HIP(hipMemcpy(path_h2, a.path_h2, n_path * 8, hipMemcpyDeviceToHost));
+  BSN_HIP(hipMemcpy(path_alpha, a.path_alpha, n_path * 8, hipMemcpyDeviceToHost));
+  if (seconds_out) {
+    std::vector<uint64_t> t((size_t)G);
+    BSN_HIP(hipMemcpy(t.data(), d_ticks.p, (size_t)G * 8, hipMemcpyDeviceToHost));
+    for (int64_t g = 0; g < G; g++) seconds_out[g] = clock_khz > 0 ? (double)t[(size_t)g] / (clock_khz * 1e3) : NAN;
+  }
+}
+
 }  // namespace
 }  // namespace bsn
 
@@ -1035,6 +1379,19 @@ int bsn_ldpred2_gibbs_sampling(const bsn_sfbm *s, const double *beta_hat, const 
     if (!sample_out && m > 0) fail("bsn_ldpred2_gibbs_sampling: arguments");
     run_gibbs(s, beta_hat, n_vec, m, ind_sub, &h2, &p, &sparse, &stream, 1, burn_in, num_iter, seed, nullptr, sample_out,
               seconds_out, "bsn_ldpred2_gibbs_sampling");
+  });
+}
+
+int bsn_ldpred2_auto(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, const double *log_var, int64_t m,
+                     const int64_t *ind_sub, const double *p_init, const uint64_t *stream, int64_t G, double h2_init,
+                     int burn_in, int num_iter, int report_step, int no_jump_sign, double shrink_corr, int use_mle,
+                     double p_lo, double p_hi, double alpha_lo, double alpha_hi, double mean_ld, uint64_t seed,
+                     double *beta_est, double *postp_est, double *corr_est, double *sample_beta,
+                     double *path_p, double *path_h2, double *path_alpha, double *seconds_out) {
+  return guarded([&] {
+    run_auto(s, beta_hat, n_vec, log_var, m, ind_sub, p_init, stream, G, h2_init, burn_in, num_iter, report_step, no_jump_sign,
+             shrink_corr, use_mle, p_lo, p_hi, alpha_lo, alpha_hi, mean_ld, seed, beta_est, postp_est, corr_est, sample_beta,
+             path_p, path_h2, path_alpha, seconds_out);
   });
 }
 

@@ -385,3 +385,115 @@ def snp_ldpred2_grid(corr, df_beta, grid_param, burn_in=50, num_iter=100, ncores
     res.seed = seed
     res.grid_param = {"p": pp, "h2": h2, "sparse": sparse.astype(bool), "stream": stream, "time": secs}
     return res
+
+
+# ---- R/LDpred2.R:203-286 -------------------------------------------------------------------------------------------------
+
+def snp_ldpred2_auto(corr, df_beta, h2_init, vec_p_init=0.1, burn_in=500, num_iter=200, sparse=False, verbose=False,
+                     report_step=None, allow_jump_sign=True, shrink_corr=1, use_MLE=True, p_bounds=(1e-5, 1),
+                     alpha_bounds=(-1.5, 0.5), ind_corr=None, ncores=1, seed=None, stream=None):
+    """R/LDpred2.R:203-286: one LDpred2-auto chain per value of vec_p_init, all of them in one library call over the
+    resident matrix (bsn_ldpred2_auto).  corr: an SFBM or anything as_SFBM takes (converted for this call only).
+    Returns a list of dicts in the order of vec_p_init with the reference's elements — beta_est (scaled back), postp_est,
+    corr_est, sample_beta (dense m x (num_iter // report_step); report_step=None is the reference's num_iter + 1, no
+    column), path_p_est, path_h2_est, path_alpha_est, h2_est, p_est, alpha_est (means over the last num_iter sweeps),
+    h2_init, p_init — and seed, stream, time (the chain's seconds on the device clock).  A chain that diverged has NaN
+    estimates, as the reference has NA.  sparse=True adds beta_est_sparse to every chain whose h2_est is finite: one
+    further bsn_ldpred2_gibbs call (sparse, burn-in 50, 100 sweeps) at each chain's h2_est and p_est, made through
+    snp_ldpred2_grid: beta_est_sparse is bit for bit what that function returns for the chain by hand.
+
+    The random numbers come from the counter-based generator of snp_ldpred2_grid, keyed by `seed` (None: a fresh one,
+    kept on the result); a chain's stream id is its position in vec_p_init unless `stream` gives it, and must be below
+    2^63: the sparse follow-up runs at stream | 2^63 and so reuses no counter.  The MLE of (alpha, sigma2) is the exact
+    minimiser over the reference's box, not an L-BFGS-B run.  verbose and ncores are accepted
+    for the reference's signature."""
+    # the reference's checks, in its order, before any device work
+    beta, beta_se, n_eff = _sumstats(df_beta)
+    ind = _subset(corr, ind_corr, beta.size, "ind.corr", repeats_ok=True)
+    if not np.all(beta_se > 0):
+        raise ValueError("'df_beta$beta_se' should have only positive values.")
+    if not np.all(np.asarray(h2_init, dtype=np.float64) > 0) or np.size(h2_init) != 1:
+        raise ValueError("'h2_init' should have only positive values.")
+    if not (int(ncores) == ncores and ncores >= 1):
+        raise ValueError("'ncores' should be an integer >= 1.")
+    if not (beta.size == beta_se.size == n_eff.size):
+        raise ValueError(ERROR_LENGTH)
+    if ind is not None and np.unique(ind).size != ind.size:
+        raise ValueError("'ind.corr' should not have repeated indices.")
+    p_init = as_f64(np.ravel(np.asarray(vec_p_init, dtype=np.float64)))
+    G = p_init.size
+    if np.any(np.isnan(p_init)):
+        raise ValueError("'vec_p_init' should not have missing values.")
+    burn_in, num_iter = int(burn_in), int(num_iter)
+    if burn_in < 0:
+        raise ValueError("'burn_in' should not be negative.")
+    if num_iter < 1:
+        raise ValueError("'num_iter' should be at least 1.")
+    if burn_in + num_iter >= 2 ** 30:
+        raise ValueError("'burn_in + num_iter' should be below 2^30.")
+    report_step = num_iter + 1 if report_step is None else int(report_step)
+    if report_step < 1:
+        raise ValueError("'report_step' should be at least 1.")
+    report_step = min(report_step, num_iter + 1)
+    p_lo, p_hi = (float(v) for v in p_bounds)
+    a_lo, a_hi = (float(v) + 1 for v in alpha_bounds)      # alpha_bounds + 1 (R/LDpred2.R:254)
+    if not (0 < p_lo <= p_hi <= 1):
+        raise ValueError("'p_bounds' should be ordered and in (0, 1].")
+    if not a_lo <= a_hi:
+        raise ValueError("'alpha_bounds' should be ordered.")
+    if stream is None:
+        stream = np.arange(G, dtype=np.uint64)
+    else:
+        stream = np.ravel(np.asarray(stream))
+        if stream.size != G:
+            raise ValueError(ERROR_LENGTH)
+        if np.any(stream < 0) or np.any(stream.astype(np.uint64) >= np.uint64(2 ** 63)):
+            raise ValueError("'stream' should be in [0, 2^63).")
+        stream = np.ascontiguousarray(stream, dtype=np.uint64)
+    seed = int.from_bytes(os.urandom(8), "little") if seed is None else int(seed) & (2 ** 64 - 1)
+    h2_init = float(np.ravel(h2_init)[0])
+
+    N = as_f64(n_eff)
+    sd = 1 / np.sqrt(N * beta_se ** 2 + beta ** 2)
+    beta_hat = as_f64(beta * sd)
+    log_var = as_f64(2 * np.log(sd))
+    m = beta_hat.size
+    tot = burn_in + num_iter
+    n_report = num_iter // report_step
+    beta_est, postp_est, corr_est = (np.empty((m, G), dtype=np.float64, order="F") for _ in range(3))
+    sample = np.empty((m, n_report, G), dtype=np.float64, order="F")
+    path_p, path_h2, path_alpha = (np.empty((tot, G), dtype=np.float64, order="F") for _ in range(3))
+    secs = np.zeros(G)
+    beta_sparse = None
+    L = _lib.load()
+    with _Resident(corr) as sf:
+        mean_ld = float(np.mean(ld_scores_sfbm(sf, ind)))
+        check(L.bsn_ldpred2_auto(sf.handle, ptr(beta_hat, f64p), ptr(N, f64p), ptr(log_var, f64p), m, ptr(ind, i64p),
+                                 ptr(p_init, f64p), ptr(stream, u64p), G, h2_init, burn_in, num_iter, report_step,
+                                 int(not allow_jump_sign), float(shrink_corr), int(bool(use_MLE)), p_lo, p_hi, a_lo, a_hi,
+                                 mean_ld, seed, beta_est.ctypes.data_as(f64p), postp_est.ctypes.data_as(f64p),
+                                 corr_est.ctypes.data_as(f64p), sample.ctypes.data_as(f64p), path_p.ctypes.data_as(f64p),
+                                 path_h2.ctypes.data_as(f64p), path_alpha.ctypes.data_as(f64p), secs.ctypes.data_as(f64p)))
+        h2_est = np.array([np.mean(path_h2[burn_in:, g]) for g in range(G)])
+        p_est = np.array([np.mean(path_p[burn_in:, g]) for g in range(G)])
+        alpha_est = np.array([np.mean(path_alpha[burn_in:, g]) for g in range(G)])
+        ok = np.nonzero(np.isfinite(h2_est))[0]      # sparse && !is.na(h2_est)
+        if sparse and ok.size:
+            # ldpred2_gibbs_one through snp_ldpred2_grid, so that the result is what that call gives by hand, bit for bit (it
+            # forms beta_hat as beta / sqrt(...) and scales back by the product; the reference's beta * sd and / sd here
+            # differ from that in the last place)
+            gp = {"p": p_est[ok], "h2": h2_est[ok], "sparse": np.ones(ok.size, dtype=bool),
+                  "stream": np.ascontiguousarray(stream[ok] | np.uint64(2 ** 63))}
+            beta_sparse = np.asarray(snp_ldpred2_grid(sf, {"beta": beta, "beta_se": beta_se, "n_eff": n_eff}, gp, burn_in=50,
+                                                      num_iter=100, ind_corr=ind, seed=seed))
+    out = []
+    for g in range(G):
+        r = {"beta_est": beta_est[:, g] / sd, "postp_est": postp_est[:, g].copy(), "corr_est": corr_est[:, g].copy(),
+             "sample_beta": np.ascontiguousarray(sample[:, :, g]), "path_p_est": path_p[:, g].copy(),
+             "path_h2_est": path_h2[:, g].copy(), "path_alpha_est": path_alpha[:, g].copy(),
+             "h2_est": float(h2_est[g]), "p_est": float(p_est[g]), "alpha_est": float(alpha_est[g]),
+             "h2_init": h2_init, "p_init": float(p_init[g]), "seed": seed, "stream": int(stream[g]), "time": float(secs[g])}
+        if beta_sparse is not None and g in ok:
+            r["beta_est_sparse"] = beta_sparse[:, int(np.nonzero(ok == g)[0][0])].copy()
+        out.append(r)
+    return out

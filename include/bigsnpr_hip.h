@@ -520,6 +520,25 @@ int bsn_ldpred2_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n
 int bsn_ldpred2_gibbs_sampling(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, int64_t m, const int64_t *ind_sub,
                                double h2, double p, int32_t sparse, uint64_t stream, int burn_in, int num_iter, uint64_t seed,
                                double *sample_out, double *seconds_out);
+/* LDpred2-auto: ldpred2_gibbs_auto (src/ldpred2-auto.cpp:57-202) for G chains per call, chain g from p_init[g] and the
+ * random numbers of stream[g] (NULL: g).  log_var [m] is 2 log(sd) (read with use_mle only); alpha_lo / alpha_hi bound
+ * alpha + 1, as the reference passes them; mean_ld is the mean LD score over ind_sub.  The coordinate draws are those of
+ * bsn_ldpred2_gibbs at the counter (j, k, stream[g]), k counting from the first burn-in sweep; the draws of a sweep's
+ * epilogue (the two gammas of rbeta, the bootstrap of the causal set) carry a purpose tag in the two top bits of the
+ * sweep word, hence burn_in + num_iter < 2^30.  The bounded MLE of (alpha + 1, sigma2) is the exact minimiser over the
+ * reference's box, found by bisection on the profile's derivative with sums of one fixed order, in the place of the
+ * reference's L-BFGS-B run.  Outputs are column-major per chain: beta_est, postp_est, corr_est [m * G] (averages over
+ * num_iter, all NaN where the reference returns NA); sample_beta [m * n_report * G] with n_report = num_iter / report_step
+ * (may be NULL when that is 0), the causal entries of curr_beta after sweep burn_in + c * report_step - 1; path_p,
+ * path_h2, path_alpha [(burn_in + num_iter) * G], NaN from the sweep on at which a chain diverged (path_alpha all NaN
+ * without use_mle).  seconds_out (may be NULL): each chain's seconds on the device clock.  Every result equals the
+ * sequential loop over the same arithmetic bit for bit.  Arguments are checked before any device work. */
+int bsn_ldpred2_auto(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, const double *log_var, int64_t m,
+                     const int64_t *ind_sub, const double *p_init, const uint64_t *stream, int64_t G, double h2_init,
+                     int burn_in, int num_iter, int report_step, int no_jump_sign, double shrink_corr, int use_mle,
+                     double p_lo, double p_hi, double alpha_lo, double alpha_hi, double mean_ld, uint64_t seed,
+                     double *beta_est, double *postp_est, double *corr_est, double *sample_beta,
+                     double *path_p, double *path_h2, double *path_alpha, double *seconds_out);
 
 /* ---- products with the resident matrix: bigsparser's sp_prodVec and sp_solve_sym, ld_scores_sfbm ------------------------
  * ind_sub [m] (0-based columns of `corr`, any order; NULL: all of them, m = m2) means "as if run on corr[ind_sub, ind_sub]".
