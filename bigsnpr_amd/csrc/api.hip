@@ -471,7 +471,7 @@ void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
 
 // counts of the codes 0, 1, 2, missing of every selected variant over the selected rows, 4 x m int32 on
 // the device
-static void counts_device(bsn_op *op, const int64_t *ind_row, int64_t n, int32_t *d_counts) {
+void counts_device(bsn_op *op, const int64_t *ind_row, int64_t n, int32_t *d_counts) {
   bsn_bed *bed = op->bed;
   if (op->rows_identity) {
     counts_all_rows(bed, op->cols_contig ? nullptr : op->d_cols.p, op->col0, op->m, d_counts);

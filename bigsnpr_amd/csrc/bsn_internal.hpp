@@ -406,6 +406,9 @@ void counts_all_rows(bsn_bed *b, const int32_t *d_cols, int64_t col0, int64_t m,
 // host result, 4 x m (counts of 0, 1, 2, NA) for arbitrary row / column selections (api.hip)
 void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
                  int32_t *res);
+// api.hip: counts of the codes 0, 1, 2, missing of every variant of the operator over its rows (ind_row: the operator's own
+// list, NULL = the first n), 4 x m int32 on the device
+void counts_device(bsn_op *op, const int64_t *ind_row, int64_t n, int32_t *d_counts);
 // api.hip: the handle's device-resident code counts over all samples (bsn_bed::stats_cache).  A selection of the handle's
 // variants as both sides see it: the host list (nullptr: the run col0 .. col0 + m - 1) and the same list on the device.
 struct StatsCols {

@@ -145,6 +145,25 @@ int bsn_bed_cprod_planes(bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
 int bsn_mult_lin_reg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
                      const double *U, int64_t K, double *res);
 
+/* bigstatsr::big_univLinReg: per variant x of the selection, the least-squares coefficient of x in y ~ x + 1 + covar and
+ * its standard error.  U (n x K column-major, K <= 31) is an orthonormal basis of the columns [1, covar] over the selected
+ * rows (the host mirror takes it from their thin SVD); with y~ = y - U U' y:
+ *   estim = x' y~ / den, den = x' x - |U' x|^2, std_err = sqrt((y~' y~ - estim x' y~) / (den (n - K - 1))).
+ * A variant with a missing value among the rows, without variance over them, or with den <= 1e-14 x' x gives NaN in
+ * both.  2-bit images and byte images on a grid (CODE_DOSAGE). */
+int bsn_univ_linreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const double *y,
+                    const double *U, int64_t K, double *estim, double *std_err);
+/* bigstatsr::big_univLogReg: per variant x, the maximum-likelihood fit of y01 ~ x + 1 + covar (covar: n x q
+ * column-major, q <= 30, may be NULL when q = 0) by iteratively reweighted least squares from the covariates-only fit,
+ * which is computed inside.  Converged when max_k 2 |b_new - b_old| / (|b_new| + |b_old|) <= tol.  estim = the
+ * coefficient of x, std_err = sqrt of the [0, 0] entry of the inverse of the last solve's weighted Gram matrix, niter =
+ * the number of solves; niter = -1 with the last iterate when `maxiter` solves did not converge; NaN and niter = 0
+ * for a variant with a missing value among the rows, without variance, or whose system is singular (a Cholesky pivot
+ * at or below 1e-14 times its diagonal entry).  2-bit images and byte images on a grid. */
+int bsn_univ_logreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const double *y01,
+                    const double *covar, int64_t q, double tol, int32_t maxiter, double *estim, double *std_err,
+                    int32_t *niter);
+
 /* _bigsnpr_prod_and_rowSumsSq (6 args) src/bed-fun.cpp:103-133 (the kernel of
  * bed_projectSelfPCA, R/bed-projectPCA.R:45-59): XV[n x K] = A~ V[m x K] and
  * rowSumsSq[i] = sum_j A~[i, j]^2, column-major host buffers. */
