@@ -106,6 +106,8 @@ SIGNATURES = {
     "bsn_mult_lin_reg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
     "bsn_univ_linreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p, f64p]),
     "bsn_univ_logreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, C.c_double, C.c_int32, f64p, f64p, i32p]),
+    "bsn_impute_simple": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp), u8p, i64p]),
+    "bsn_impute_last_ms": (C.c_int, [f64p]),
     "bsn_bed_to_fbm": (C.c_int, [vp, i64p, i64, i64p, i64, u8p]),
     "bsn_bed_readbina": (C.c_int, [vp, u8p, u8p]),
     "bsn_bed_is_streamed": (C.c_int, [vp]),

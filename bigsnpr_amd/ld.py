@@ -43,6 +43,17 @@ class FBM_code256:
         self.bits = int(_lib.load().bsn_bed_bits(h))
         self._has_na = int(_lib.load().bsn_bed_na_known(h)) != 0   # counted on the device at creation
 
+    @classmethod
+    def _from_handle(cls, h, n, m, code):
+        """an FBM over an image the library made on the device (snp_fastImputeSimple): no bytes come from the host"""
+        self = cls.__new__(cls)
+        self.code256 = np.ascontiguousarray(code, dtype=np.float64)
+        self.nrow, self.ncol = int(n), int(m)
+        self._bed = bed(_handle=h, _n=self.nrow, _m=self.ncol)
+        self.bits = int(_lib.load().bsn_bed_bits(h))
+        self._has_na = int(_lib.load().bsn_bed_na_known(h)) != 0
+        return self
+
     @property
     def handle(self):
         return self._bed.handle

@@ -164,6 +164,31 @@ int bsn_univ_logreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64
                     const double *covar, int64_t q, double tol, int32_t maxiter, double *estim, double *std_err,
                     int32_t *niter);
 
+/* _bigsnpr_impute (3 args) src/impute-simple.cpp:10-73 + R/impute.R:189-203 — R: snp_fastImputeSimple.
+ * `src` is any resident 2-bit handle and is not modified; *out receives a NEW handle (the reference rewrites the FBM's
+ * file in place and returns it under another decode table).  method: 0 zero, 1 mode, 2 mean0, 3 mean2, 4 random — the
+ * reference's numbers plus 0.  With c1, c2 the numbers of calls 1 and 2, c the number of non-missing calls over all
+ * samples and c0 = c - c1 - c2, every missing position of a variant receives
+ *   zero    the call 0                                                        (FBM byte stays 3)
+ *   mode    the most frequent call, ties to the smaller (lines 52-56)         (FBM byte 4 + v)
+ *   mean0   nearbyint((c1 + 2.0 c2) / c), ties to even                        (FBM byte 4 + v)
+ *   mean2   r / 100, r = nearbyint(100 * ((c1 + 2.0 c2) / c)) in fp64          (FBM byte 7 + r)
+ *   random  (u0 < af) + (u1 < af), af = (0.5 c1 + c2) / c, u0 / u1 from one    (FBM byte 4 + v)
+ *           Philox4x32-10 call keyed by `seed` with the counter (sample, variant): not R's generator
+ * The result is a 2-bit image, for mean2 the int8 grid image of CODE_DOSAGE (v_off = 1, v_step = 0.01), exactly what
+ * bsn_fbm_open makes of the FBM bytes under CODE_IMPUTE_PRED / CODE_DOSAGE / c(0, 1, 2, 0, NA ...).  A variant without
+ * any call (c == 0) becomes 0 under zero and mode and STAYS MISSING under mean0, mean2 and random (the reference casts
+ * a NaN to unsigned char there); *n_all_missing counts such variants for every method.  fbm_bytes_out (n x m
+ * column-major, may be NULL) receives the content the reference's file would have; out may be NULL when only those
+ * bytes are wanted.  Refused by name: a byte image, an out-of-core handle, a result that does not fit the free device
+ * memory. */
+int bsn_impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8_t *fbm_bytes_out /* or NULL */,
+                      int64_t *n_all_missing /* or NULL */);
+/* device milliseconds (HIP events, host copies excluded) of the last bsn_impute_simple of this process: ms_out[0] the
+ * counts (a counting pass, or a copy of the handle's resident counts) and the per-variant rule, [1] the rewrite of the
+ * image, [2] the kernels that write the FBM bytes (0 when none were asked for) */
+int bsn_impute_last_ms(double *ms_out);
+
 /* _bigsnpr_prod_and_rowSumsSq (6 args) src/bed-fun.cpp:103-133 (the kernel of
  * bed_projectSelfPCA, R/bed-projectPCA.R:45-59): XV[n x K] = A~ V[m x K] and
  * rowSumsSq[i] = sum_j A~[i, j]^2, column-major host buffers. */
