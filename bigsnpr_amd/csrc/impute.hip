@@ -14,6 +14,14 @@
 namespace bsn {
 namespace {
 
+// what decides when a loop of the kernels below goes round again (tests/helpers/impute_inputs.py reads these lines and
+// tests/test_impute_shapes_cpu.py holds the shapes of tests/test_gpu_impute_shapes.py against them)
+constexpr int64_t kRewriteVecs = 256;      // rewrite grid: 16-B vectors of a row per workgroup in x (four turns of a wave)
+constexpr int64_t kRewriteGroups = 2048;   // rewrite grid: workgroups in all, a stride for the rest
+constexpr int64_t kBytesMaxCols = 65535;   // FBM bytes: variants per launch (gridDim.y)
+constexpr int64_t kBytesChunkMiB = 256;    // FBM bytes: size of a column chunk
+constexpr int64_t kBytesGroups = 1024;     // FBM bytes: workgroups over the samples of a variant, a stride for the rest
+
 // device milliseconds of the last call of this process (bsn_impute_last_ms): counts + rule, rewrite, FBM bytes
 double g_last_ms[3] = {0.0, 0.0, 0.0};
 
@@ -146,8 +154,8 @@ __global__ __launch_bounds__(256) void k_impute_bytes(const uint8_t *__restrict_
 // grid of the two rewrite kernels: x over the 16-B vectors of a row (at most four turns per lane), y over groups of four
 // variants, about 2048 workgroups in all with a stride for the rest
 dim3 rewrite_grid(int64_t nvec, int64_t m) {
-  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((nvec + 255) / 256, 2048));
-  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>((m + 3) / 4, std::max<int64_t>(1, 2048 / gx)));
+  const int64_t gx = std::max<int64_t>(1, std::min<int64_t>((nvec + kRewriteVecs - 1) / kRewriteVecs, kRewriteGroups));
+  const int64_t gy = std::max<int64_t>(1, std::min<int64_t>((m + 3) / 4, std::max<int64_t>(1, kRewriteGroups / gx)));
   return dim3((unsigned)gx, (unsigned)gy);
 }
 
@@ -246,11 +254,12 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
 
   // ---- the FBM's bytes, in column chunks of at most 256 MB ---------------------------------------------------------------
   if (fbm_bytes_out) {
-    int64_t cols_per = std::max<int64_t>(1, std::min<int64_t>(65535, (int64_t)((256ull << 20) / (size_t)n)));
+    int64_t cols_per =
+        std::max<int64_t>(1, std::min<int64_t>(kBytesMaxCols, (int64_t)(((size_t)kBytesChunkMiB << 20) / (size_t)n)));
     cols_per = std::min(cols_per, m);
     DevBuf<uint8_t> tmp;
     tmp.ensure((size_t)cols_per * (size_t)n);
-    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1024));
+    const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, kBytesGroups));
     for (int64_t j0 = 0; j0 < m; j0 += cols_per) {
       const int64_t cnt = std::min(cols_per, m - j0);
       BSN_HIP(hipEventRecord(ev_write.a, st));

@@ -126,9 +126,9 @@ def test_dosage_image_of_the_same_calls(ba, ex):
         np.testing.assert_allclose(b["std_err"], a["std_err"], rtol=1e-12, atol=0)
 
 
-def test_dosage_image_edges(ba):
-    """a byte image of real dosages against the CPU statement; a monomorphic column at a non-zero dosage and a column with
-    a missing byte are NaN in both scans (niter = 0), over all samples and over a row list"""
+def _dosage_edges(ba):
+    """333 x 44 random dosages: column 5 is 0.50 everywhere, column 6 is 2.00 everywhere, column 9 has a missing byte at
+    sample 17.  (image, decoded matrix, y01, y, covariates, a permutation of the samples)"""
     rng = np.random.default_rng(21)
     n, m = 333, 44
     raw = rng.integers(7, 208, size=(n, m)).astype(np.uint8)
@@ -139,7 +139,13 @@ def test_dosage_image_edges(ba):
     assert D.bits == 8
     X = np.asfortranarray(ba.CODE_DOSAGE[raw])
     y, ylin, cov = (rng.random(n) < 0.5).astype(np.float64), rng.standard_normal(n), rng.standard_normal((n, 4))
-    perm = rng.permutation(n)
+    return D, X, y, ylin, cov, rng.permutation(n)
+
+
+def test_dosage_image_edges(ba):
+    """a byte image of real dosages against the CPU statement; a monomorphic column at a non-zero dosage and a column with
+    a missing byte are NaN in both scans (niter = 0), over all samples and over a row list"""
+    D, X, y, ylin, cov, perm = _dosage_edges(ba)
     for ir in (None, np.r_[17, perm[perm != 17][:200]]):     # (the list holds the sample with the missing byte)
         sel = slice(None) if ir is None else ir
         Xs = np.asfortranarray(X[sel])
@@ -189,6 +195,120 @@ def test_constructed_columns(ba, ex):
     lin = ba.big_univLinReg(G, ex["ylin"], covar_train=ex["u"])
     assert np.isnan(lin["estim"][[7, 300]]).all() and np.isfinite(lin["estim"][301])
     _same_lin(lin, ref.linreg(X, ex["ylin"], ex["u"]), "linear, constructed columns")
+
+
+# ---- row lists and NaN rules in the other direction ---------------------------------------------------------------------------------
+
+def _scan_both(ba, G, X, rows, cols, y, ylin, cov, where, **kw):
+    """both scans over `rows` (and `cols`) against the CPU statement on that subset: (logistic, linear, statement of the
+    logistic scan)"""
+    Xs = np.asfortranarray(X[rows] if cols is None else X[np.ix_(rows, cols)])
+    got = ba.big_univLogReg(G, y[rows], ind_train=rows, ind_col=cols, covar_train=None if cov is None else cov[rows], verbose=False, **kw)
+    want = ref.logreg(Xs, y[rows], None if cov is None else cov[rows], **kw)
+    _same_log(got, want, "logistic, " + where)
+    lin = ba.big_univLinReg(G, ylin[rows], ind_train=rows, ind_col=cols, covar_train=None if cov is None else cov[rows])
+    _same_lin(lin, ref.linreg(Xs, ylin[rows], None if cov is None else cov[rows]), "linear, " + where)
+    return got, lin, want
+
+
+def test_missing_value_outside_the_row_list(ba, orc, golden_dir, missing_bed):
+    """variant 399 of example-missing.bed is missing at samples 17 and 71 only: over the other 198 samples it has a fit in
+    both scans, while every variant with a missing value among them stays NaN.  The same on a byte image: the matrix of
+    test_dosage_image_edges over a list without sample 17."""
+    X = orc.read_bed(missing_bed, na_val=3).astype(np.float64)
+    X[X == 3] = np.nan
+    X = np.asfortranarray(X)
+    n, j = X.shape[0], 399
+    rows = np.flatnonzero(~np.isnan(X[:, j]))
+    assert rows.size == n - 2 and list(np.flatnonzero(np.isnan(X[:, j]))) == [17, 71]
+    still = np.isnan(X[rows]).any(axis=0)
+    assert not still[j] and still.sum() > 300 and np.unique(X[rows, j]).size == 3
+    rng = np.random.default_rng(11)
+    y, ylin, cov = (rng.random(n) < 0.45).astype(np.float64), rng.standard_normal(n), rng.standard_normal((n, 3))
+    gb = ba.bed(os.path.join(golden_dir, "example-missing.bed"))
+    for order, ir in (("file order", rows), ("shuffled", rng.permutation(rows))):
+        got, lin, want = _scan_both(ba, gb, X, ir, None, y, ylin, cov, "example-missing without samples 17 and 71, " + order)
+        assert got["niter"][j] > 0 and np.isfinite(got["estim"][j]) and np.isfinite(got["std_err"][j])
+        assert np.isfinite(lin["estim"][j]) and np.isfinite(lin["std_err"][j])
+        assert (got["niter"][still] == 0).all() and np.isnan(got["estim"][still]).all() and np.isnan(lin["estim"][still]).all()
+        assert np.isfinite(lin["estim"][~still]).sum() > 100                 # (a variant may be constant on the list)
+    D, Xd, y, ylin, cov, perm = _dosage_edges(ba)
+    for order, ir in (("file order", np.flatnonzero(np.arange(Xd.shape[0]) != 17)), ("a shuffled part", perm[perm != 17][:200])):
+        got, lin, want = _scan_both(ba, D, Xd, ir, None, y, ylin, cov, "dosages without sample 17, " + order)
+        assert got["niter"][9] > 0 and np.isfinite(got["estim"][9]) and np.isfinite(lin["estim"][9]) and np.isfinite(lin["std_err"][9])
+        assert list(got["niter"][[5, 6]]) == [0, 0] and np.isnan(lin["estim"][[5, 6]]).all()
+        assert (got["niter"][np.r_[0:5, 7:44]] != 0).all()
+
+
+def test_constant_on_the_row_list_varying_outside(ba, ex):
+    """a variant that is constant over ind_train and varies elsewhere has no fit: NaN and niter = 0 in both scans, on a
+    2-bit image (code counts over the list) and on a byte image (n S2 = S1^2 over the list)"""
+    n = ex["n"]
+    rng = np.random.default_rng(77)
+    perm = rng.permutation(np.arange(1, n))                  # sample 0 of the file stays outside the list
+    rows, out = perm[:250], np.r_[0, perm[250:]]
+    g = np.array(ex["bytes"][:, :40], order="F")
+    g[rows, 10], g[out, 10] = 1, rng.integers(0, 3, out.size)        # constant 1 on the list, anything elsewhere
+    g[:, 11] = 0
+    g[0, 11] = 2                                                        # only sample 0 of the file differs: not in the list
+    g[:, 12] = 2
+    g[out[-1], 12] = 0                                                  # only one other sample outside the list differs
+    g[:, 13] = 0
+    g[rows[0], 13] = 1                                                  # varies on the list: only its FIRST row differs
+    g[:, 14] = 1
+    g[rows[-1], 14] = 2                                                 # ... only its last row
+    const, single = [10, 11, 12], [13, 14]
+    assert all(np.unique(g[rows, c]).size == 1 and np.unique(g[:, c]).size > 1 for c in const)
+    assert all(np.unique(g[rows, c]).size == 2 for c in single) and 0 not in rows
+    raw = (7 + 100 * g).astype(np.uint8)                                # the same calls as dosages 0.00 / 1.00 / 2.00 ...
+    raw[:, 10] = np.where(np.isin(np.arange(n), rows), 57, rng.integers(7, 208, n))   # ... except 0.50 on the list
+    raw[0, 11], raw[out[-1], 12] = 8, 206                               # and the smallest steps away from the constant
+    D = ba.FBM_code256(raw, code=ba.CODE_DOSAGE)
+    assert D.bits == 8
+    for what, G, X in (("2-bit", ba.FBM_code256(g), g.astype(np.float64)), ("dosages", D, ba.CODE_DOSAGE[raw])):
+        for order, ir in (("shuffled", rows), ("ascending", np.sort(rows))):
+            got, lin, want = _scan_both(ba, G, X, ir, None, ex["y"], ex["ylin"], ex["u"][:, :3], "%s, %s list" % (what, order))
+            assert list(got["niter"][const]) == [0, 0, 0] and list(want["niter"][const]) == [0, 0, 0]
+            assert np.isnan(got["estim"][const]).all() and np.isnan(got["std_err"][const]).all()
+            assert np.isnan(lin["estim"][const]).all() and np.isnan(lin["std_err"][const]).all()
+            assert (got["niter"][single] != 0).all() and np.isfinite(lin["estim"][single]).all()
+
+
+@pytest.mark.parametrize("q,n", [(3, 256), (3, 257), (14, 128), (14, 129), (0, 40), (0, 64), (0, 65),
+                                 (15, 128), (15, 129), (30, 128), (30, 129)])
+def test_sample_counts_at_the_tile_boundaries(ba, ex, q, n):
+    """ind_train = the first n samples.  An LDS tile of k_logreg holds 256 samples when q + 2 <= 16 and 128 otherwise:
+    (3, 256) fills one, (3, 257) starts a second with a single sample; (0, 40) is less than one step of 64
+    samples, (0, 64) exactly one, (0, 65) one more.  q = 14 still takes the tile of 256 (q + 2 = 16), so (14, 128) and
+    (14, 129) are two steps and two steps plus a sample of it; the tile of 128 starts at q = 15: (15, 128), (15, 129) and,
+    with z in a third operand tile, (30, 128), (30, 129)."""
+    rows, cols = np.arange(n), np.arange(300)
+    cov = ex["rnd"][:, :q] if q else None
+    assert q == 0 or np.linalg.matrix_rank(np.column_stack([np.ones(n), cov[:n]])) == q + 1
+    got, lin, want = _scan_both(ba, ex["gb"], ex["X"], rows, cols, ex["y"], ex["ylin"], cov, "q = %d, first %d samples" % (q, n))
+    assert (want["niter"] > 0).sum() > 250
+
+
+@pytest.mark.parametrize("maxiter", [3, 4])
+def test_workgroup_shapes(ba, ex, maxiter):
+    """37 columns = nine workgroups of four variants and one with a single live wave.  The four variants of the first all
+    stop at their first solve (two monomorphic, one with a missing value, one monomorphic at 2); with maxiter = 3 (4) some
+    workgroup holds converged variants beside ones that end at -1, and the wave of the last workgroup ends on its own."""
+    g = np.array(ex["bytes"][:, :40], order="F")
+    g[:, 0], g[:, 1], g[5, 2], g[:, 3] = 1, 0, 3, 2
+    cols = np.arange(37)
+    G = ba.FBM_code256(g)
+    X = g.astype(np.float64)
+    X[g == 3] = np.nan
+    rows = np.arange(ex["n"])
+    got, lin, want = _scan_both(ba, G, X, rows, cols, ex["y"], ex["ylin"], ex["u"], "37 columns, maxiter = %d" % maxiter, maxiter=maxiter)
+    assert cols.size % 4 == 1 and list(got["niter"][:4]) == [0, 0, 0, 0] and np.isnan(lin["estim"][:4]).all()
+    groups = [set(np.sign(want["niter"][k:k + 4])) for k in range(4, 36, 4)]
+    assert {1, -1} in groups, want["niter"]                              # converged and not converged in one workgroup
+    assert want["niter"][36] != 0 and got["niter"][36] == want["niter"][36]
+    last = want["niter"] == -1                                           # the last iterate of a variant that did not converge
+    assert last.any() and (np.abs(got["estim"][last] - want["estim"][last]) <= 1e-9 * want["std_err"][last]).all()
+    assert (np.abs(got["std_err"][last] / want["std_err"][last] - 1) <= 1e-7).all()
 
 
 def test_maxiter_and_the_message(ba, ex, capsys):

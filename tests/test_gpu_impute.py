@@ -6,20 +6,18 @@ source stays untouched; the FBM entry points that refuse missing values run on t
 import ctypes as C
 import os
 import sys
-import warnings
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
 import impute_ref as ref  # noqa: E402
+from impute_inputs import METHODS, SEED, check_edges, column, edge_matrix, impute, same_image  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-METHODS = ("zero", "mode", "mean0", "mean2", "random")
-SEED = ref.SEED
 
 
 @pytest.fixture(scope="module")
@@ -34,23 +32,6 @@ def ex(golden_dir):
     G = ref.read_bed_bytes(os.path.join(golden_dir, "example-missing.bed"), 200, 500)
     return dict(path=os.path.join(golden_dir, "example-missing.bed"), G=G,
                 want={me: ref.impute(G, me, seed=SEED)[0] for me in METHODS})
-
-
-def impute(ba, Gna, method, **kw):
-    """snp_fastImputeSimple with its expected warnings let through"""
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return ba.snp_fastImputeSimple(Gna, method, **kw)
-
-
-def column(ba, res, j):
-    """decoded column j of a result, through the accessor (2-bit image; -1 = missing) or a product with e_j (byte image;
-    in hundredths)"""
-    if res.bits == 2:
-        return ba.read_bed(res._bed, np.arange(res.nrow), np.array([j]))[:, 0]
-    e = np.zeros(res.ncol)
-    e[j] = 1.0
-    return np.rint(100 * ba.big_prodVec(res, e)).astype(np.int64)
 
 
 # ---- 1. example data, all five methods ------------------------------------------------------------------------------------
@@ -88,61 +69,12 @@ def test_example_data(ba, ex, method):
 
 
 # ---- 2. the result handle is the image bsn_fbm_open would make ----------------------------------------------------------
-def same_image(ba, res, n_vec_seed=3):
-    """`res` against a second FBM_code256 uploaded from its bytes under its table"""
-    twin = ba.FBM_code256(res.bytes, res.code256)
-    assert twin.bits == res.bits and twin._has_na == res._has_na
-    a, b = ba.snp_colstats(res), ba.snp_colstats(twin)
-    np.testing.assert_array_equal(a["sumX"], b["sumX"])
-    np.testing.assert_array_equal(a["denoX"], b["denoX"])
-    if res.bits == 2:
-        np.testing.assert_array_equal(res._bed.download(), twin._bed.download())   # pad bits included
-    if not res._has_na:
-        rng = np.random.default_rng(n_vec_seed)
-        x, y = rng.integers(-3, 4, res.ncol).astype(np.float64), rng.integers(-3, 4, res.nrow).astype(np.float64)
-        np.testing.assert_array_equal(ba.big_prodVec(res, x), ba.big_prodVec(twin, x))
-        np.testing.assert_array_equal(ba.big_cprodVec(res, y), ba.big_cprodVec(twin, y))
-    return twin
-
-
 @pytest.mark.parametrize("method", METHODS)
 def test_result_is_the_image_of_its_bytes(ba, ex, method):
     same_image(ba, impute(ba, ba.FBM_code256(ex["G"]), method, seed=SEED, return_bytes=True))
 
 
 # ---- 3. shapes at the edges of the layout -------------------------------------------------------------------------------------
-def edge_matrix(n, m):
-    """random calls with a third missing; for m = 65: variant 1 complete, 2 all missing, 3 / 4 with their only missing call
-    at the first / last sample, 64 (the last) all missing too; for m = 1 the caller passes the kind"""
-    rng = np.random.default_rng(1000 * n + m)
-    g = rng.integers(0, 3, (n, m)).astype(np.uint8)
-    g[rng.random((n, m)) < 0.33] = 3
-    if m > 4:
-        g[:, 1] = rng.integers(0, 3, n)
-        g[:, 2] = 3
-        g[:, 3] = rng.integers(0, 3, n)
-        g[0, 3] = 3
-        g[:, 4] = rng.integers(0, 3, n)
-        g[n - 1, 4] = 3
-        g[:, m - 1] = 3
-    return np.asfortranarray(g)
-
-
-def check_edges(ba, g, method):
-    want, _, want_all = ref.impute(g, method, seed=SEED)
-    res = impute(ba, ba.FBM_code256(g), method, seed=SEED, return_bytes=True)
-    assert np.array_equal(res.bytes, want)
-    assert res.n_all_missing == want_all == int((g == 3).all(0).sum())
-    stays = method in ("mean0", "mean2", "random") and want_all > 0
-    assert res._has_na == stays
-    allna = (g == 3).all(0)
-    assert (res.bytes[:, allna] == (4 if method == "mode" else 3)).all()
-    same_image(ba, res)
-    if res.bits == 2:   # the all-missing variants through the accessor: 0 for zero / mode, still missing otherwise
-        for j in np.flatnonzero(allna):
-            assert (column(ba, res, j) == (-1 if stays else 0)).all()
-
-
 @pytest.mark.parametrize("n", [1, 3, 17, 1025])
 @pytest.mark.parametrize("method", METHODS)
 def test_shapes_at_the_edges(ba, n, method):
