@@ -337,7 +337,7 @@ hipStream_t upload_stream(bsn_bed *b) {
 
 // true when the runtime knows `p` as page-locked host memory (bsn_host_alloc, or registered by the
 // caller): the DMA engines can reach it directly, no staging
-static bool host_is_pinned(const void *p) {
+bool host_is_pinned(const void *p) {
   hipPointerAttribute_t at;
   if (hipPointerGetAttributes(&at, p) != hipSuccess) {
     (void)hipGetLastError();   // an ordinary pointer is reported as an error: not one

@@ -441,6 +441,7 @@ void subset_pack(bsn_bed *b, const int32_t *d_rows, int64_t n, const int32_t *d_
 void copy_h2d(bsn_bed *b, void *d_dst, const void *src, size_t bytes, hipStream_t stream = nullptr);  // default: the handle's stream
 hipStream_t upload_stream(bsn_bed *b);
 void copy_d2h(bsn_bed *b, void *dst, const void *d_src, size_t bytes);
+bool host_is_pinned(const void *p);   // the runtime knows `p` as page-locked host memory: the DMA engines write it directly
 
 // api.hip: operator over a sub-view; defer_scale leaves centre / scale unset (stats_pending path)
 void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,

@@ -453,6 +453,12 @@ struct SvdWorkspace {
   double *h_pin = nullptr;
   size_t h_pin_n = 0;
   hipEvent_t ev_small = nullptr;   // the small matrices of a block step have reached the host
+  // early Rayleigh-Ritz (HipSvdBackend::early_grams / prefinalize): "the Gram blocks of this step have reached the host"
+  // (recorded on the solve's stream: Z and the stored Q are final there too), "S of the guess has left its staging
+  // buffer" and "u, v of the guess are on the host" (both on the handle's second stream); the staging buffer of S
+  hipEvent_t ev_early = nullptr, ev_guess_up = nullptr;
+  double *h_guess = nullptr;
+  size_t h_guess_n = 0;
   // sharded solve, product pass in segments (A_Zblock): the stream the reduce-scatters run on, one event per segment
   // ("its partial sums are ready") and one for "all segments have arrived"; the segments' sample lists and receive buffer
   hipStream_t st_comm = nullptr;
@@ -477,6 +483,9 @@ struct SvdWorkspace {
     if (ev_arrived) (void)hipEventDestroy(ev_arrived);
     if (st_comm) (void)hipStreamDestroy(st_comm);
     if (ev_small) (void)hipEventDestroy(ev_small);
+    if (ev_early) (void)hipEventDestroy(ev_early);
+    if (ev_guess_up) (void)hipEventDestroy(ev_guess_up);
+    if (h_guess) (void)hipHostFree(h_guess);
     if (h_pin) (void)hipHostFree(h_pin);
   }
 };
@@ -504,6 +513,29 @@ struct HipSvdBackend : SvdBackend {
   bool no_fused = false;     // BSN_NO_FUSED_STEP=1: the step-by-step path only (A/B, debugging)
   bool speculate = true;     // queue the start of the next step behind the orthonormalisation (BSN_NO_SPECULATION=1: off)
   bool spec_rounded = false; // ... and it has been: the driver's next round_W is a no-op
+  // Early Rayleigh-Ritz (svd_driver.hpp; one GPU, resident image, fused step; BSN_NO_EARLY_RITZ=1: off).  The Gram blocks
+  // of a step are queued between its two passes and u, v of the guess "the solve ends at this step" are formed and
+  // sent to the host on the handle's second stream while the product pass runs on the solve's.
+  bool early_on = false;
+  bool grams_early = false;  // the Gram blocks of this step are in the arena already: fused() does not compute them
+  double *eg_Z = nullptr, *eg_Q = nullptr;
+  int eg_p = 0, eg_cb = 0;
+  bool guess_live = false;      // u, v of the last prefinalize are (or will be) what a finalize with the same arguments gives
+  bool guess_inflight = false;  // the second stream may still be working on a guess: dS / dU / dV / u / v are not free
+  int guess_pp = 0, guess_k = 0;
+  double *guess_u = nullptr, *guess_v = nullptr;
+  std::vector<double> guess_S, guess_dinv;
+  // bsn_svd_info::early_ritz.  n_guess runs on through the 56-bit repeat of a solve on this backend (like niter, which
+  // the caller sums over both attempts); guess_used is set by every finalize, so it is the last attempt's
+  int n_guess = 0, guess_used = 0;
+  void guess_wait() {
+    if (!guess_inflight) return;
+    BSN_HIP(hipStreamSynchronize(upload_stream(op->bed)));
+    guess_inflight = false;
+  }
+  ~HipSvdBackend() {   // (an error thrown under a guess in flight: the caller's u / v and the workspace stay in use until it ends)
+    if (guess_inflight && op && op->bed && op->bed->stream_up) (void)hipStreamSynchronize(op->bed->stream_up);
+  }
   int n_small_ar = 0;        // small all-reduces issued (diagnostics)
   // warm start on a leading subset of this rank's variants
   int64_t m_op_full = 0, m_sub = 0;
@@ -647,6 +679,8 @@ struct HipSvdBackend : SvdBackend {
     wcol = 0;
     mx_valid = false;
     spec_rounded = false;
+    guess_live = false;
+    grams_early = false;
     op->preq_X = nullptr;
     hipLaunchKernelGGL(k_random, dim3((unsigned)((nr + 255) / 256), bb), dim3(256), 0, st, Wc, nr, nr, bb, seed,
                        row0, n);
@@ -781,6 +815,7 @@ struct HipSvdBackend : SvdBackend {
   void At_Qblock(int p0, int cb) override {
     Tick tk(this, 1);
     if (progress) progress();
+    guess_live = false;   // (the solve goes on)
     if (ooc) return At_Qblock_ooc(p0, cb);
     op_cprod(op, newest_block(p0), n, cb, Z.p + (int64_t)p0 * m_local, m_local);
   }
@@ -1014,8 +1049,12 @@ struct HipSvdBackend : SvdBackend {
     const size_t pc = (size_t)p * cb, hg = (size_t)(p + cb) * cb;
     double *flag = dorth.p + 16, *dRout = flag + 1, *dZtZ = dRout + B2, *X = dZtZ + pc, *HG1 = X + (p > 0 ? hg : 0),
            *HG2 = HG1 + hg, *C = HG2 + hg, *Ct = C + pc, *Ri = Ct + pc;
+    // (early_grams has put Z'Zb into dZtZ and Q'Qb into the first p rows of the left half of X: same kernels, same
+    // operands, and an entry of gemm_tn_any depends on its two columns and the row tiling only — same numbers)
+    const bool have_grams = grams_early && with_grams && p == eg_p && cb == eg_cb;
+    grams_early = false;
     BSN_HIP(hipMemsetAsync(flag, 0, (size_t)(1 + B2) * 8, st));
-    if (p > 0) gemm_tn_any(Z.p, Z.p + (int64_t)p0 * m_local, m_local, p, cb, dZtZ);
+    if (p > 0 && !have_grams) gemm_tn_any(Z.p, Z.p + (int64_t)p0 * m_local, m_local, p, cb, dZtZ);
     BSN_HIP(hipMemcpyAsync(Wsave.p, Wc, (size_t)nr * cb * 8, hipMemcpyDeviceToDevice, st));
     OrthSmall a;
     a.p = p;
@@ -1034,7 +1073,7 @@ struct HipSvdBackend : SvdBackend {
     a.Cs = a.Gs = a.Rs = a.Ris = a.Ro = a.Dv = a.tmp = nullptr;
     for (int pass = 0; pass < 2; pass++) {
       double *HG = pass == 0 ? HG1 : HG2;
-      if (pass == 0 && p > 0) {
+      if (pass == 0 && p > 0 && !have_grams) {
         gemm_tn_any(Q.p, Q.p + (int64_t)p0 * nr, nr, p + cb, 2 * cb, X, p + cb);
         ar_small(dZtZ, (int64_t)(pc + 2 * hg));
       } else {
@@ -1129,10 +1168,111 @@ struct HipSvdBackend : SvdBackend {
     wcol = p0 + r;
     Wc = Q.p + (int64_t)wcol * nr;   // the next panel goes behind the block just stored
   }
+  // ---- early Rayleigh-Ritz: the hooks of svd_driver.hpp ------------------------------------------------
+  // where the early Gram blocks land in the pinned staging buffer: behind everything fused() downloads
+  double *early_host(size_t *cnt = nullptr) {
+    const size_t half = (size_t)(cap + kMaxB + 4) * kMaxB * 2 + 512;
+    if (cnt) *cnt = half;
+    return ws.pinned(2 * half) + half;
+  }
+  bool early_grams(int p, int p0, int cb, double *blkZ, double *blkQ) override {
+    grams_early = false;
+    // (exactly where fused() serves the step: it then finds its Gram blocks done)
+    if (!early_on || p <= 0 || cb <= 0 || cb > kMaxB || p + cb > kOrthMaxP || p + cb > cap + kMaxB) return false;
+    if (Wc != Q.p + (int64_t)p * nr || p0 + cb != p) return false;
+    Tick tk(this, 3);
+    const size_t pc = (size_t)p * cb, hg = (size_t)(p + cb) * cb;
+    size_t room = 0;
+    double *hp = early_host(&room);
+    if (pc + hg > room) return false;
+    double *dZtZ = dorth.p + 16 + 1 + B2, *X = dZtZ + pc;   // fused()'s arena
+    gemm_tn_any(Z.p, Z.p + (int64_t)p0 * m_local, m_local, p, cb, dZtZ);
+    gemm_tn_any(Q.p, Q.p + (int64_t)p0 * nr, nr, p, cb, X, p + cb);
+    BSN_HIP(hipGetLastError());
+    BSN_HIP(hipMemcpyAsync(hp, dZtZ, (pc + hg) * 8, hipMemcpyDeviceToHost, st));
+    if (!ws.ev_early) BSN_HIP(hipEventCreateWithFlags(&ws.ev_early, hipEventDisableTiming));
+    BSN_HIP(hipEventRecord(ws.ev_early, st));
+    eg_Z = blkZ;
+    eg_Q = blkQ;
+    eg_p = p;
+    eg_cb = cb;
+    grams_early = true;
+    return true;
+  }
+  bool early_grams_wait() override {
+    if (!grams_early) return false;
+    Tick tk(this, 3);
+    BSN_HIP(hipEventSynchronize(ws.ev_early));
+    n_sync++;
+    const double *hp = early_host();
+    const size_t pc = (size_t)eg_p * eg_cb;
+    std::memcpy(eg_Z, hp, pc * 8);
+    for (int j = 0; j < eg_cb; j++)
+      std::memcpy(eg_Q + (size_t)j * eg_p, hp + pc + (size_t)j * (eg_p + eg_cb), (size_t)eg_p * 8);
+    return true;
+  }
+  // u = Q S and v = Z S diag(dinv) with finalize's kernels, operands and column chunks, on the handle's second stream
+  // behind ev_early, and their download; returns without waiting.  Only into page-locked u / v: a pageable
+  // destination would hold this thread in a staged copy while the product pass waits to be followed up.
+  void prefinalize(int pp, int k, const double *S, const double *dinv, double *u, double *v) override {
+    guess_live = false;
+    if (!S || !early_on || !ws.ev_early || pp <= 0 || pp > cap + kMaxB || k <= 0 || (!u && !v)) return;
+    if ((u && !host_is_pinned(u)) || (v && !host_is_pinned(v))) return;
+    Tick tk(this, 6);
+    hipStream_t up = upload_stream(op->bed);
+    DevBuf<double> &dS = ws.dS, &dU = ws.dU, &dV = ws.dV;
+    const size_t sk = (size_t)pp * k, need_S = (size_t)(cap + kMaxB) * k * 2 + 16;
+    // one guess at a time writes dS / dU / dV / u / v: they follow each other on one stream, and a buffer grows only
+    // with nothing in flight
+    if (need_S > dS.n || (size_t)nr * k > dU.n || (size_t)m_local * k > dV.n) guess_wait();
+    dS.ensure(need_S);
+    dU.ensure((size_t)nr * k);
+    dV.ensure((size_t)m_local * k);
+    if (!ws.ev_guess_up) BSN_HIP(hipEventCreateWithFlags(&ws.ev_guess_up, hipEventDisableTiming));
+    else BSN_HIP(hipEventSynchronize(ws.ev_guess_up));   // S of the previous guess has left the staging buffer
+    if (2 * sk > ws.h_guess_n) {
+      if (ws.h_guess) (void)hipHostFree(ws.h_guess);
+      ws.h_guess = nullptr;
+      ws.h_guess_n = 0;
+      BSN_HIP(hipHostMalloc((void **)&ws.h_guess, need_S * sizeof(double), hipHostMallocDefault));
+      ws.h_guess_n = need_S;
+    }
+    double *hs = ws.h_guess;
+    std::memcpy(hs, S, sk * 8);
+    for (int t = 0; t < k; t++)
+      for (int i = 0; i < pp; i++) hs[sk + (size_t)i + (size_t)t * pp] = S[(size_t)i + (size_t)t * pp] * dinv[t];
+    guess_inflight = true;
+    BSN_HIP(hipMemcpyAsync(dS.p, hs, 2 * sk * 8, hipMemcpyHostToDevice, up));
+    BSN_HIP(hipEventRecord(ws.ev_guess_up, up));
+    BSN_HIP(hipStreamWaitEvent(up, ws.ev_early, 0));   // Z of this step and the stored Q are final
+    for (int c0 = 0; c0 < k; c0 += kMaxB) {
+      const int nc = k - c0 < kMaxB ? k - c0 : kMaxB;
+      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((nr + 255) / 256)), dim3(256), kTP * kMaxB * 8, up,
+                         Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, (const double *)nullptr, (int64_t)0,
+                         0.0, 1.0, dU.p + (int64_t)c0 * nr, nr, nr);
+      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((m_local + 255) / 256)), dim3(256),
+                         kTP * kMaxB * 8, up, Z.p, m_local, pp, dS.p + sk + (size_t)c0 * pp,
+                         nc, (const double *)nullptr, (int64_t)0, 0.0, 1.0,
+                         dV.p + (int64_t)c0 * m_local, m_local, m_local);
+    }
+    BSN_HIP(hipGetLastError());
+    if (u) BSN_HIP(hipMemcpyAsync(u, dU.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, up));
+    if (v) BSN_HIP(hipMemcpyAsync(v, dV.p, (size_t)m_local * k * 8, hipMemcpyDeviceToHost, up));
+    guess_pp = pp;
+    guess_k = k;
+    guess_u = u;
+    guess_v = v;
+    guess_S.assign(S, S + sk);
+    guess_dinv.assign(dinv, dinv + k);
+    guess_live = true;
+    n_guess++;
+  }
   // thick restart: Q[:, :keep] = Q[:, :pp] S and Z[:, :keep] = Z[:, :pp] S (local rows of both), the waiting
   // panel moves behind column `keep`, the device copy of Q'Q becomes the identity on the kept part
   bool restart(int pp, int keep, const double *S, int rn, const double *Mk) override {
     if (keep + rn > pp || keep <= 0) return false;   // the panel moves to the left of where it is
+    guess_live = false;   // Q and Z change under it, and its buffers are the scratch of this restart
+    guess_wait();
     DevBuf<double> &dS = ws.dS, &tQ = ws.dU, &tZ = ws.dV;
     dS.ensure((size_t)pp * keep + 16);
     tQ.ensure((size_t)nr * keep);
@@ -1164,6 +1304,18 @@ struct HipSvdBackend : SvdBackend {
   }
   void finalize(int pp, int k, const double *S, const double *dinv, double *u, double *v) override {
     Tick tk(this, 6);
+    guess_used = 0;
+    if (guess_live && pp == guess_pp && k == guess_k && u == guess_u && v == guess_v &&
+        std::memcmp(S, guess_S.data(), (size_t)pp * k * 8) == 0 && std::memcmp(dinv, guess_dinv.data(), (size_t)k * 8) == 0) {
+      // the guess held: u and v are on their way (or there) — the same kernels on the same operands
+      guess_live = false;
+      guess_wait();
+      guess_used = 1;
+      sync_stream();
+      return;
+    }
+    guess_live = false;
+    guess_wait();
     std::vector<double> Sv((size_t)pp * k);
     for (int t = 0; t < k; t++)
       for (int i = 0; i < pp; i++) Sv[(size_t)i + (size_t)t * pp] = S[(size_t)i + (size_t)t * pp] * dinv[t];
@@ -1562,6 +1714,7 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     bk.timing = getenv("BSN_TIMING") != nullptr;
     bk.speculate = getenv("BSN_NO_SPECULATION") == nullptr;
     bk.no_fused = getenv("BSN_NO_FUSED_STEP") != nullptr;
+    bk.early_on = !bk.dist && !ooc && !bk.no_fused && getenv("BSN_NO_EARLY_RITZ") == nullptr;
     bk.fused_stats = fused && !served;
     bk.warm_den = o->warm_denominator >= 2 ? o->warm_denominator : 16;
     int64_t dim = bk.n < bk.m_total ? bk.n : bk.m_total;
@@ -1831,6 +1984,8 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
       info->compacted = compacted ? 1 : 0;
       info->compact_ms = t_compact;
       info->exchange_mode = bk.exchange_mode;
+      info->early_ritz[0] = bk.n_guess;
+      info->early_ritz[1] = bk.guess_used;
       for (int c = 0; c < 4; c++) info->exchange_ms[c] = 0, info->n_exchange[c] = 0;
       if (bk.comm && o->exchange_timing) {
         double ems[kCommClasses];

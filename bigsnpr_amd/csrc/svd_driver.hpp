@@ -98,6 +98,27 @@ struct SvdBackend {
     (void)on;
     return false;
   }
+  // Early Rayleigh-Ritz (optional; the defaults say "not supported" and the step keeps its old order).  The projected
+  // pair of a block step is complete once At_Qblock has produced the step's Z block: the product pass and the
+  // orthonormalisation behind it only add the coupling block, i.e. the residual estimate and the decision to stop.
+  // early_grams — called between At_Qblock and A_Zblock — queues the two Gram blocks of the newest columns (what
+  // step_fused / ZtZ / QtQ deliver, entry for entry) and returns without waiting; early_grams_wait — called once
+  // A_Zblock has been queued — blocks until they are in blkZ / blkQ.  step_fused of that step then only orthonormalises
+  // (it may write the same numbers to its blkZ / blkQ again).
+  virtual bool early_grams(int p, int p0, int cb, double *blkZ, double *blkQ) {
+    (void)p; (void)p0; (void)cb; (void)blkZ; (void)blkQ;
+    return false;
+  }
+  virtual bool early_grams_wait() { return false; }
+  // What finalize does, queued without waiting while the product pass of the step runs: a guess that the solve ends at
+  // this step.  A finalize with the same arguments, byte for byte, that follows with nothing in between but the step's
+  // orthonormalisation finds its work done and only waits.  S == nullptr: the driver drops the guess — the step took
+  // the careful path, clipped its block or restarts, or the solve goes on to its next step (told before that step's
+  // At_Qblock); the backend lets it run out and the next finalize does the work.  The driver tells every drop: a backend
+  // need not watch its own writes to Q[:, :pp] or Z[:, :pp] for it.
+  virtual void prefinalize(int pp, int k, const double *S, const double *dinv, double *u, double *v) {
+    (void)pp; (void)k; (void)S; (void)dinv; (void)u; (void)v;
+  }
   // u (n x k) = Q[:, :pp] S ; v (m_local x k) = Z[:, :pp] S diag(dinv); host outputs
   virtual void finalize(int pp, int k, const double *S, const double *dinv, double *u,
                         double *v) = 0;
@@ -345,40 +366,8 @@ inline SvdResult block_lanczos_svd(SvdBackend &bk, const SvdOptions &opt, double
   int rl_rows = 0, rl_cols = 0;
   int exhausted_restarts = 0;   // thick restarts taken while the space was exhausted by count (p >= dim)
 
-  while (cb > 0) {
-    const int p0 = p - cb;
-    bk.At_Qblock(p0, cb);
-    int S_next = 0;
-    if (opt.slices_base > 0) {
-      const int Sz = step_slices(z_gain);   // digits of Z in the product pass
-      S_next = step_slices(1.0);            // grid of the block it produces = digits of the next crossproduct pass
-      bk.set_precision(Sz);
-      if (S_next > opt.slices_base || Sz > opt.slices_base) res.wide_steps++;
-      if (std::max(Sz, S_next) > res.slices_used_max) res.slices_used_max = std::max(Sz, S_next);
-      if (opt.verbose)
-        std::fprintf(stderr, "[bsn svd] step %d: %d-bit product pass, next block on %d bits (leading residual %.2e, product weight %.3f)\n",
-                     res.niter + 1, 8 * Sz, 8 * S_next, rho_lead, z_gain);
-    }
-    bk.A_Zblock(p0, cb);
-    // the grid of the block this step produces: narrow already by the previous step's residuals -> queued behind the
-    // orthonormalisation as always; else decided below, once this step's residuals are known
-    const bool hold = sched && S_next > opt.slices_base;
-    if (opt.slices_base > 0) {
-      bk.set_precision(S_next);
-      bk.hold_rounding(hold);
-    }
-    res.nops += 2;
-    res.niter++;
-    // Gram blocks of the new columns p0 .. p-1 (Z of this step is complete now, Q was stored rounded)
-    // and the orthonormalisation of W: in one go when the backend can, else piece by piece
-    blk.assign((size_t)p * cb, 0.0);
-    blk2.assign((size_t)p * cb, 0.0);
-    int rn = bk.step_fused(p, p0, cb, blk.data(), blk2.data(), Rt);
-    const bool fused_failed = rn == -2;
-    if (rn == -1) {
-      bk.ZtZ(p, p0, cb, blk.data());
-      bk.QtQ(p, p0, cb, blk2.data());
-    }
+  // The Gram blocks of the newest columns p0 .. p-1 (blk = Z'Z block, blk2 = Q'Q block, p x cb each) join the projected pair
+  auto absorb_grams = [&](int p, int p0, int cb) {
     // NaN / Inf in the projected blocks: in the operator's centre or scale (a scale of 0), in a start block handed in,
     // or an overflow (entries beyond 1e150 square out of range).  Nothing below is defined on them — say so here
     for (size_t t = 0; t < blk.size(); t++)
@@ -409,8 +398,174 @@ inline SvdResult block_lanczos_svd(SvdBackend &bk, const SvdOptions &opt, double
         a = 0.5 * (Mat(p0 + i, p0 + j) + Mat(p0 + j, p0 + i));
         Mat(p0 + i, p0 + j) = Mat(p0 + j, p0 + i) = a;
       }
+  };
+
+  // Rayleigh-Ritz on span(Q[:, :pp]), the half that needs the projected pair only: (Gz) s = theta (Mq) s with Mq = R'R,
+  // i.e. the standard problem for R^-T Gz R^-1, s = R^-1 y.  Fills eval / evec (ascending) and rr_rank; returns the
+  // rank of the Cholesky factor of Q'Q (== pp unless the basis is numerically dependent).
+  auto ritz = [&](int pp) -> int {
+    std::vector<double> Mp((size_t)pp * pp), Gp((size_t)pp * pp), Rm, Rmi, tmp((size_t)pp * pp);
+    for (int j = 0; j < pp; j++)
+      for (int i = 0; i < pp; i++) {
+        Mp[(size_t)i + (size_t)j * pp] = Mat(i, j);
+        Gp[(size_t)i + (size_t)j * pp] = Gat(i, j);
+      }
+    int rk = chol_upper(pp, Mp, Rm, 1e-14);
+    if (opt.verbose > 1) {
+      double dev = 0;
+      for (int j = 0; j < pp; j++)
+        for (int i = 0; i < pp; i++) dev = std::max(dev, std::fabs(Mat(i, j) - (i == j ? 1.0 : 0.0)));
+      std::fprintf(stderr, "[bsn svd]   Q'Q: max |M - I| = %.3e, Cholesky rank %d of %d\n", dev, rk, pp);
+    }
+    rr_rank = pp;
+    if (rk == pp) {
+      inv_upper(pp, Rm, Rmi);
+      // tmp = Gp * Rmi ; evec = Rmi' * tmp
+      small_mm(pp, pp, pp, Gp.data(), Rmi.data(), tmp.data());
+      evec.assign((size_t)pp * pp, 0.0);
+      for (int j = 0; j < pp; j++)
+        for (int i = 0; i <= j; i++) {
+          double a = 0;
+          for (int t = 0; t <= i; t++) a += Rmi[(size_t)t + (size_t)i * pp] * tmp[(size_t)t + (size_t)j * pp];
+          evec[(size_t)i + (size_t)j * pp] = a;
+          evec[(size_t)j + (size_t)i * pp] = a;
+        }
+      eig_sym(pp, evec, eval);
+      // back-transform: s = Rmi * y (upper triangular)
+      small_mm(pp, pp, pp, Rmi.data(), evec.data(), tmp.data());
+      evec.swap(tmp);
+    } else {
+      // The stored basis is numerically DEPENDENT (Q'Q singular to 1e-14).  It happens when the Krylov space
+      // is exhausted but rounded products keep handing over "new" directions that are amplified noise — a
+      // request for more singular values than the matrix has rank, k > rank(A).  Canonical orthogonalisation:
+      // Q'Q = V L V', keep the r directions with L > 1e-8 max L, T = V L^(-1/2) (pp x r); the Ritz pairs of
+      // span(Q) are those of T' (Z'Z) T, s = T y; the pp - r dropped directions get Ritz value 0.
+      std::vector<double> V(Mp), lam;
+      eig_sym(pp, V, lam);
+      const double lmax = lam[pp - 1];
+      int r = 0;
+      while (r < pp && lam[pp - 1 - r] > 1e-8 * lmax && lmax > 0) r++;
+      std::vector<double> T((size_t)pp * std::max(r, 1), 0.0), GT((size_t)pp * std::max(r, 1)), B((size_t)r * r), bl;
+      for (int c = 0; c < r; c++) {
+        const double f = 1.0 / std::sqrt(lam[pp - 1 - c]);
+        for (int i = 0; i < pp; i++) T[(size_t)i + (size_t)c * pp] = V[(size_t)i + (size_t)(pp - 1 - c) * pp] * f;
+      }
+      small_mm(pp, pp, r, Gp.data(), T.data(), GT.data());
+      for (int j = 0; j < r; j++)
+        for (int i = 0; i <= j; i++) {
+          double a = 0;
+          for (int t = 0; t < pp; t++) a += T[(size_t)t + (size_t)i * pp] * GT[(size_t)t + (size_t)j * pp];
+          B[(size_t)i + (size_t)j * r] = B[(size_t)j + (size_t)i * r] = a;
+        }
+      eig_sym(r, B, bl);
+      rr_rank = r;
+      eval.assign((size_t)pp, 0.0);
+      evec.assign((size_t)pp * pp, 0.0);
+      for (int c = 0; c < r; c++) {   // ascending order, the r computed pairs at the top end
+        const int col = pp - r + c;
+        eval[(size_t)col] = bl[(size_t)c];
+        for (int i = 0; i < pp; i++) {
+          double a = 0;
+          for (int t = 0; t < r; t++) a += T[(size_t)i + (size_t)t * pp] * B[(size_t)t + (size_t)c * r];
+          evec[(size_t)i + (size_t)col * pp] = a;
+        }
+      }
+      if (opt.verbose)
+        std::fprintf(stderr, "[bsn svd]   dependent basis: %d of %d directions kept for the Rayleigh-Ritz step\n", r, pp);
+    }
+    return rk;
+  };
+
+  // the k largest Ritz pairs of the last Rayleigh-Ritz step as finalize wants them: S (pp x k), 1 / sigma, sigma
+  auto extract = [&](int pp, std::vector<double> &S, std::vector<double> &dinv, double *sigma) {
+    const int kk = k < pp ? k : pp;
+    S.assign((size_t)pp * k, 0.0);
+    dinv.assign((size_t)k, 0.0);
+    for (int t = 0; t < k; t++) {
+      double dt = 0;
+      if (t < kk) {
+        const int col = pp - 1 - t;
+        const double th = eval[col] > 0 ? eval[col] : 0;
+        dt = std::sqrt(th);
+        dinv[t] = dt > 0 ? 1.0 / dt : 0.0;
+        for (int i = 0; i < pp; i++) S[(size_t)i + (size_t)t * pp] = evec[(size_t)i + (size_t)col * pp];
+      }
+      if (sigma) sigma[t] = dt;
+    }
+  };
+  // the guess in flight (prefinalize): the step it was made at, and what it was made from
+  bool guess = false;
+  std::vector<double> S_guess, dinv_guess;
+  auto drop_guess = [&]() {
+    if (guess) bk.prefinalize(0, k, nullptr, nullptr, u, v);
+    guess = false;
+  };
+
+  while (cb > 0) {
+    const int p0 = p - cb;
+    drop_guess();   // the solve goes on: At_Qblock writes Z behind the guess of the previous step (the next one queues behind it)
+    bk.At_Qblock(p0, cb);
+    // Gram blocks of the new columns p0 .. p-1 (Z of this step is complete now, Q was stored rounded): ahead of the
+    // product pass when the backend can, so that the Rayleigh-Ritz step runs on the host while the device streams
+    blk.assign((size_t)p * cb, 0.0);
+    blk2.assign((size_t)p * cb, 0.0);
+    bool early = bk.early_grams(p, p0, cb, blk.data(), blk2.data());
+    int S_next = 0;
+    if (opt.slices_base > 0) {
+      const int Sz = step_slices(z_gain);   // digits of Z in the product pass
+      S_next = step_slices(1.0);            // grid of the block it produces = digits of the next crossproduct pass
+      bk.set_precision(Sz);
+      if (S_next > opt.slices_base || Sz > opt.slices_base) res.wide_steps++;
+      if (std::max(Sz, S_next) > res.slices_used_max) res.slices_used_max = std::max(Sz, S_next);
+      if (opt.verbose)
+        std::fprintf(stderr, "[bsn svd] step %d: %d-bit product pass, next block on %d bits (leading residual %.2e, product weight %.3f)\n",
+                     res.niter + 1, 8 * Sz, 8 * S_next, rho_lead, z_gain);
+    }
+    bk.A_Zblock(p0, cb);
+    // the grid of the block this step produces: narrow already by the previous step's residuals -> queued behind the
+    // orthonormalisation as always; else decided below, once this step's residuals are known
+    const bool hold = sched && S_next > opt.slices_base;
+    if (opt.slices_base > 0) {
+      bk.set_precision(S_next);
+      bk.hold_rounding(hold);
+    }
+    res.nops += 2;
+    res.niter++;
+    // The product pass is queued.  With the Gram blocks taken early, the half of the Rayleigh-Ritz step that needs the
+    // projected pair alone runs HERE, on the host, while the device streams — when the count condition alone already
+    // says that this step takes one (the other triggers are known after the orthonormalisation: they keep the late
+    // path below).  And every such step whose basis holds k vectors and is of full rank hands the backend the guess
+    // that the solve ends here: if it does, u and v are on the host when the pass is over; if it does not, the guess
+    // cost transfers hidden behind the pass.
+    bool early_rr = false;
+    if (early) early = bk.early_grams_wait();
+    if (early) {
+      absorb_grams(p, p0, cb);
+      if (p >= (sched ? std::min(k, klead) : k)) {
+        const int rk = ritz(p);
+        early_rr = true;
+        // (a block that the bound against n below may clip, p + cb > n, is not worth a guess that would be dropped)
+        if (p >= k && rk == p && (int64_t)p + cb <= bk.n) {
+          extract(p, S_guess, dinv_guess, nullptr);
+          bk.prefinalize(p, k, S_guess.data(), dinv_guess.data(), u, v);
+          guess = true;
+        }
+      }
+    }
+    // the orthonormalisation of W — and the Gram blocks, unless they were taken early — in one go when the backend
+    // can, else piece by piece
+    int rn = bk.step_fused(p, p0, cb, blk.data(), blk2.data(), Rt);
+    const bool fused_failed = rn == -2;
+    if (rn == -1 && !early) {
+      bk.ZtZ(p, p0, cb, blk.data());
+      bk.QtQ(p, p0, cb, blk2.data());
+    }
+    if (!early) absorb_grams(p, p0, cb);
     // Rt: cb x cb (rn rows used): W_in = Q C2 + W_out Rt
-    if (rn < 0) rn = orth(p, cb, C2, Rt, /*try_fused=*/!fused_failed);
+    if (rn < 0) {
+      drop_guess();   // the careful path
+      rn = orth(p, cb, C2, Rt, /*try_fused=*/!fused_failed);
+    }
     // The complement of span(Q) in R^n has n - p directions, whatever the deficiency tests make of a rounded panel: on
     // 16-bit products the projected block of a nearly full space is two genuine directions and six of rounding noise,
     // all above the absolute threshold.  Without this bound a matrix with fewer rows than the basis limit (34 x 1701,
@@ -444,80 +599,10 @@ inline SvdResult block_lanczos_svd(SvdBackend &bk, const SvdOptions &opt, double
     if (rn > cap - p) rn = cap - p;
     if (rn < 0) rn = 0;
 
-    // Rayleigh-Ritz on span(Q[:, :pp]): (Gz) s = theta (Mq) s with Mq = R'R,
-    // i.e. the standard problem for R^-T Gz R^-1, s = R^-1 y.  Not needed while the basis is smaller
-    // than k and the iteration goes on (the device idles while the host works here).
-    if (pp >= (sched ? std::min(k, klead) : k) || rn == 0 || exhausted || want_restart) {
-      std::vector<double> Mp((size_t)pp * pp), Gp((size_t)pp * pp), Rm, Rmi, tmp((size_t)pp * pp);
-      for (int j = 0; j < pp; j++)
-        for (int i = 0; i < pp; i++) {
-          Mp[(size_t)i + (size_t)j * pp] = Mat(i, j);
-          Gp[(size_t)i + (size_t)j * pp] = Gat(i, j);
-        }
-      int rk = chol_upper(pp, Mp, Rm, 1e-14);
-      if (opt.verbose > 1) {
-        double dev = 0;
-        for (int j = 0; j < pp; j++)
-          for (int i = 0; i < pp; i++) dev = std::max(dev, std::fabs(Mat(i, j) - (i == j ? 1.0 : 0.0)));
-        std::fprintf(stderr, "[bsn svd]   Q'Q: max |M - I| = %.3e, Cholesky rank %d of %d\n", dev, rk, pp);
-      }
-      rr_rank = pp;
-      if (rk == pp) {
-        inv_upper(pp, Rm, Rmi);
-        // tmp = Gp * Rmi ; evec = Rmi' * tmp
-        small_mm(pp, pp, pp, Gp.data(), Rmi.data(), tmp.data());
-        evec.assign((size_t)pp * pp, 0.0);
-        for (int j = 0; j < pp; j++)
-          for (int i = 0; i <= j; i++) {
-            double a = 0;
-            for (int t = 0; t <= i; t++) a += Rmi[(size_t)t + (size_t)i * pp] * tmp[(size_t)t + (size_t)j * pp];
-            evec[(size_t)i + (size_t)j * pp] = a;
-            evec[(size_t)j + (size_t)i * pp] = a;
-          }
-        eig_sym(pp, evec, eval);
-        // back-transform: s = Rmi * y (upper triangular)
-        small_mm(pp, pp, pp, Rmi.data(), evec.data(), tmp.data());
-        evec.swap(tmp);
-      } else {
-        // The stored basis is numerically DEPENDENT (Q'Q singular to 1e-14).  It happens when the Krylov space
-        // is exhausted but rounded products keep handing over "new" directions that are amplified noise — a
-        // request for more singular values than the matrix has rank, k > rank(A).  Canonical orthogonalisation:
-        // Q'Q = V L V', keep the r directions with L > 1e-8 max L, T = V L^(-1/2) (pp x r); the Ritz pairs of
-        // span(Q) are those of T' (Z'Z) T, s = T y; the pp - r dropped directions get Ritz value 0.
-        std::vector<double> V(Mp), lam;
-        eig_sym(pp, V, lam);
-        const double lmax = lam[pp - 1];
-        int r = 0;
-        while (r < pp && lam[pp - 1 - r] > 1e-8 * lmax && lmax > 0) r++;
-        std::vector<double> T((size_t)pp * std::max(r, 1), 0.0), GT((size_t)pp * std::max(r, 1)), B((size_t)r * r), bl;
-        for (int c = 0; c < r; c++) {
-          const double f = 1.0 / std::sqrt(lam[pp - 1 - c]);
-          for (int i = 0; i < pp; i++) T[(size_t)i + (size_t)c * pp] = V[(size_t)i + (size_t)(pp - 1 - c) * pp] * f;
-        }
-        small_mm(pp, pp, r, Gp.data(), T.data(), GT.data());
-        for (int j = 0; j < r; j++)
-          for (int i = 0; i <= j; i++) {
-            double a = 0;
-            for (int t = 0; t < pp; t++) a += T[(size_t)t + (size_t)i * pp] * GT[(size_t)t + (size_t)j * pp];
-            B[(size_t)i + (size_t)j * r] = B[(size_t)j + (size_t)i * r] = a;
-          }
-        eig_sym(r, B, bl);
-        rr_rank = r;
-        eval.assign((size_t)pp, 0.0);
-        evec.assign((size_t)pp * pp, 0.0);
-        for (int c = 0; c < r; c++) {   // ascending order, the r computed pairs at the top end
-          const int col = pp - r + c;
-          eval[(size_t)col] = bl[(size_t)c];
-          for (int i = 0; i < pp; i++) {
-            double a = 0;
-            for (int t = 0; t < r; t++) a += T[(size_t)i + (size_t)t * pp] * B[(size_t)t + (size_t)c * r];
-            evec[(size_t)i + (size_t)col * pp] = a;
-          }
-        }
-        if (opt.verbose)
-          std::fprintf(stderr, "[bsn svd]   dependent basis: %d of %d directions kept for the Rayleigh-Ritz step\n", r, pp);
-      }
-    }
+    // Rayleigh-Ritz on span(Q[:, :pp]) (ritz, above).  Not needed while the basis is smaller than k and the iteration
+    // goes on.  Taken early — under the product pass — when the count condition asked for it; the triggers that only
+    // the orthonormalisation knows (rn == 0, exhausted, a restart) find the device idle while the host works here.
+    if (!early_rr && (pp >= (sched ? std::min(k, klead) : k) || rn == 0 || exhausted || want_restart)) ritz(pp);
     bool done = false;
     const double hard_zero = 1e-10;
     const double negligible = std::max(hard_zero, 64.0 * opt.resid_floor * opt.resid_floor);
@@ -628,6 +713,7 @@ inline SvdResult block_lanczos_svd(SvdBackend &bk, const SvdOptions &opt, double
               Mk[(size_t)i + (size_t)j * keep] = Mk[(size_t)j + (size_t)i * keep] = mm;
             }
         }
+        drop_guess();   // the restart rewrites the basis the guess reads
         if (bk.restart(pp, keep, Sk.data(), rn_full, Mk.data())) {
           for (int j = 0; j < cap; j++)
             for (int i = 0; i < cap; i++) Gat(i, j) = Mat(i, j) = 0.0;
@@ -675,19 +761,12 @@ inline SvdResult block_lanczos_svd(SvdBackend &bk, const SvdOptions &opt, double
 
   // extract the k largest
   res.basis = pp;
-  int kk = k < pp ? k : pp;
-  std::vector<double> S((size_t)pp * k, 0.0), dinv((size_t)k, 0.0);
-  for (int t = 0; t < k; t++) {
-    d[t] = 0;
-    if (t < kk) {
-      int col = pp - 1 - t;
-      double th = eval[col] > 0 ? eval[col] : 0;
-      d[t] = std::sqrt(th);
-      dinv[t] = d[t] > 0 ? 1.0 / d[t] : 0.0;
-      for (int i = 0; i < pp; i++) S[(size_t)i + (size_t)t * pp] = evec[(size_t)i + (size_t)col * pp];
-    }
-  }
-  bk.finalize(pp, k, S.data(), dinv.data(), u, v);
+  std::vector<double> S, dinv;
+  extract(pp, S, dinv, d);
+  // (a guess that is still standing was made at this very step, from this eval / evec: the same bytes; the backend
+  // compares them and only waits)
+  if (guess) bk.finalize(pp, k, S_guess.data(), dinv_guess.data(), u, v);
+  else bk.finalize(pp, k, S.data(), dinv.data(), u, v);
   return res;
 }
 

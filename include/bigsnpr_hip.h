@@ -389,6 +389,11 @@ typedef struct bsn_svd_info {
    * for steps that have one (used from a share of 0.30: nearly complete or batch-structured data; same integers) */
   double na_free_steps[2];
   int32_t na_skip;
+  /* early Rayleigh-Ritz (one GPU, resident image, page-locked u / v; BSN_NO_EARLY_RITZ=1: off): [0] guesses "the solve
+   * ends at this step" for which u and v were formed and sent to the host beside the step's product pass, [1] 1 if
+   * the u / v returned came from one (the last step's), 0 if they were formed after the last pass.  A solve that is
+   * repeated on 56-bit panels reports both attempts together in [0], as niter and nops do; [1] is the repeat's. */
+  int32_t early_ritz[2];
 } bsn_svd_info;
 /* Returns 0 on success, 1 on error, and 2 when the solve ran to the end of its basis without all
  * k residuals meeting tol (outputs are filled with the best available triplets, bsn_last_error()
