@@ -949,8 +949,9 @@ __global__ void k_band_fill8(const int32_t *__restrict__ stats, int nslice, cons
 // an int8 operand, so it enters as two digit planes k^2 = 128 H + L (0 <= H <= 126, 0 <= L <= 127).  Eight
 // exact int8 products per tile pair, in four groups of two (blockIdx.z) so that a wave's accumulators fit its
 // registers:   0: X.X', M.M'   1: X.M', M.X'   2: H.M', L.M'   3: M.H', M.L'
-// A workgroup's sample range never crosses a 131 072-sample slice (127^2 x 131 072 < 2^31); its int32 sums are
-// added to int64 statistics (exact, order-independent), stats64[pair][8][64][64].
+// A workgroup's sample range is never longer than a 131 072-sample slice (127^2 x 131 072 < 2^31; byte_na_split,
+// ld_plan.hpp); it may straddle a slice boundary, which does not matter here: its int32 sums are added to int64
+// statistics (exact, order-independent), stats64[pair][8][64][64].
 __device__ __forceinline__ uint32_t val8m_ld(uint32_t w, uint32_t &na) {
   const uint32_t t = w ^ 0x80808080u;
   const uint32_t y = (t & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
@@ -1456,7 +1457,6 @@ struct BandRun {
   void byte_na(), byte_xy(), shared_decode(), xy(), small_band(), fill_band(int64_t p0, int64_t np);
 };
 constexpr int64_t kBatch = 4096;          // 4096 x 6 x 64 x 64 x 4 B = 403 MB of int32 statistics (two-stage paths only)
-constexpr int64_t kSliceBytes = 131072;   // byte image: samples per int32 accumulator slice
 // second stage of the two-stage paths of the 2-bit image
 void BandRun::fill_band(int64_t p0, int64_t np) {
   hipLaunchKernelGGL(k_band_fill, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats.p, J.d_pairs.p + p0, (int)np, J.m,
@@ -1467,19 +1467,15 @@ void BandRun::fill_band(int64_t p0, int64_t np) {
 
 // byte image, missing values among the selected samples: the six pairwise-complete sums (eight int8 products)
 void BandRun::byte_na() {
-  const int nslice = (int)((bed->pitch + kSliceBytes - 1) / kSliceBytes);   // at most 6: band_run
   const int64_t batch8 = 512;   // 512 x 8 x 64 x 64 x 8 B = 134 MB of int64 statistics
   J.d_stats64.ensure((size_t)std::min(batch8, J.npairs) * 8 * TB * TB);
   for (int64_t p0 = pA; p0 < pB; p0 += batch8) {
     const int64_t np = std::min(batch8, pB - p0);
-    // enough workgroups to fill the chip; a split never crosses a 131 072-sample slice
-    int64_t ks = std::max<int64_t>(nslice, std::min<int64_t>(std::max<int64_t>(1, 4096 / (np * 4)), bed->pitch / 256));
-    const int64_t kb = std::min(round_up((bed->pitch + ks - 1) / ks, 64), kSliceBytes);
-    ks = (bed->pitch + kb - 1) / kb;
+    const KSplit ks = byte_na_split(bed->pitch, np);   // enough workgroups to fill the chip, none longer than a slice
     BSN_HIP(hipMemsetAsync(J.d_stats64.p, 0, (size_t)np * 8 * TB * TB * 8, bed->stream));
     tm.begin();
-    hipLaunchKernelGGL(k_pair_stats8, dim3((unsigned)np, (unsigned)ks, 4), dim3(64), 0, bed->stream, bed->d_img,
-                       bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, kb, J.d_stats64.p);
+    hipLaunchKernelGGL(k_pair_stats8, dim3((unsigned)np, (unsigned)ks.splits, 4), dim3(64), 0, bed->stream, bed->d_img,
+                       bed->pitch, J.d_cols.p, J.d_pairs.p + p0, J.d_mask8.p, ks.bytes, J.d_stats64.p);
     tm.end();
     hipLaunchKernelGGL(k_band_fill8na, dim3((unsigned)np), dim3(256), 0, bed->stream, J.d_stats64.p,
                        J.d_pairs.p + p0, (int)np, J.m, J.d_lo.p, J.W, bo.thr, bo.mode, bo.nrows, bo.band);
@@ -1489,17 +1485,11 @@ void BandRun::byte_na() {
 
 // byte image, cross product only
 void BandRun::byte_xy() {
-  const int nslice = (int)((bed->pitch + kSliceBytes - 1) / kSliceBytes);   // at most 6: band_run
+  const int nslice = byte_slices(bed->pitch);   // at most kByteMaxSlices: band_run
   J.d_stats.ensure((size_t)std::min(kBatch, J.npairs) * 6 * TB * TB);
   for (int64_t p0 = pA; p0 < pB; p0 += kBatch) {
     const int64_t np = std::min(kBatch, pB - p0);
-    // K splits never straddle a slice: one slice -> any 64-byte-aligned split of the row; several ->
-    // a power-of-two number of splits per 131 072-byte slice
-    const int64_t want = std::max<int64_t>(1, 8192 / (np * nslice));
-    KSplit ks{1, kSliceBytes};
-    if (nslice == 1) ks = k_split(bed->pitch, want, 64, 256);
-    else
-      while (ks.splits * 2 <= want && ks.splits < 512) ks.splits *= 2, ks.bytes /= 2;
+    const KSplit ks = byte_xy_split(bed->pitch, np);   // splits per slice: none straddles a slice
     BSN_HIP(hipMemsetAsync(J.d_stats.p, 0, (size_t)np * 6 * TB * TB * 4, bed->stream));
     tm.begin();
     hipLaunchKernelGGL(k_pair_xy8, dim3((unsigned)np, (unsigned)(ks.splits * nslice)), dim3(64), 0, bed->stream,
@@ -1638,7 +1628,8 @@ static void band_run(BandJob &J, LdMode mode, const double *d_thr, const double 
   if (c1 < 0 || c1 > J.m) c1 = J.m;
   if (c0 % TR != 0 || c1 - c0 > J.chunk_cols) fail("internal: LD band block [%lld, %lld)", (long long)c0, (long long)c1);
   if (bed->bits == 8 && mode == LdMode::clump_bed) fail("internal: the bed clumping formula does not apply to a byte image");
-  if (bed->bits == 8 && bed->pitch > 6 * kSliceBytes) fail("windowed LD on a dosage FBM supports at most %lld samples", (long long)(6 * kSliceBytes));
+  if (bed->bits == 8 && byte_slices(bed->pitch) > kByteMaxSlices)
+    fail("windowed LD on a dosage FBM supports at most %lld samples", (long long)(kByteMaxSlices * kSliceBytes));
   BandFacts f;
   f.bits = bed->bits, f.pitch = bed->pitch, f.n = bed->n, f.mode = mode;
   f.complete = J.complete, f.contig = J.contig, f.all_rows = J.all_rows, f.have_cnn = J.d_cnn.p != nullptr, f.npairs_b = J.npairs_b;

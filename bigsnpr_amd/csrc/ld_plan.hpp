@@ -4,6 +4,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "byte_plan.hpp"
+
 namespace bsn {
 // the fp64 epilogue of a pair (ld.hip: pair_value; BandOut::mode carries the same numbers to the device)
 enum class LdMode : int {
@@ -98,6 +100,26 @@ struct KSplit { int splits; int64_t bytes; };
 inline KSplit k_split(int64_t pitch, int64_t want, int64_t align, int64_t min_bytes) {
   const int64_t s = std::max<int64_t>(1, std::min(want, pitch / min_bytes));
   const int64_t bytes = ((pitch + s - 1) / s + align - 1) / align * align;
+  return KSplit{(int)((pitch + bytes - 1) / bytes), bytes};
+}
+
+// Byte image, cross product only (k_pair_xy8), a batch of np tile pairs.  `splits` is the number of splits PER SLICE and the
+// grid's y is splits * byte_slices(pitch): slice s of a pair has an int32 plane of its own, so a split never straddles a slice.
+// One slice: any 64-byte-aligned split of the row; several: a power-of-two number of splits per 131 072-byte slice.
+inline KSplit byte_xy_split(int64_t pitch, int64_t np) {
+  const int nslice = byte_slices(pitch);
+  const int64_t want = std::max<int64_t>(1, 8192 / (np * nslice));
+  if (nslice == 1) return k_split(pitch, want, 64, 256);
+  KSplit ks{1, kSliceBytes};
+  while (ks.splits * 2 <= want && ks.splits < 512) ks.splits *= 2, ks.bytes /= 2;
+  return ks;
+}
+// Byte image with missing values (k_pair_stats8, four workgroups per split), a batch of np tile pairs: `splits` over the whole
+// row, enough to fill the chip.  A split may straddle a slice boundary but is never LONGER than a slice: its int32 sums
+// are added to int64 statistics, so only the length counts.
+inline KSplit byte_na_split(int64_t pitch, int64_t np) {
+  const int64_t ks = std::max<int64_t>(byte_slices(pitch), std::min<int64_t>(std::max<int64_t>(1, 4096 / (np * 4)), pitch / 256));
+  const int64_t bytes = std::min(((pitch + ks - 1) / ks + 63) / 64 * 64, kSliceBytes);
   return KSplit{(int)((pitch + bytes - 1) / bytes), bytes};
 }
 

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "bsn_internal.hpp"
+#include "byte_plan.hpp"
 #include "prodt_sparse.hpp"
 #include <type_traits>
 
@@ -1122,14 +1123,17 @@ __device__ __forceinline__ uint32_t val8m(uint32_t w, uint32_t &na) {
   return w & ~(z | (z - na));
 }
 
-// k_cprod8: contraction over samples.  One wave owns 16 variants for the whole sample range; the 8 waves
+// k_cprod8: contraction over samples.  One wave owns 16 variants for the sample range of its slice; the 8 waves
 // of a workgroup share the digit panel of the current 256-sample chunk through LDS (double-buffered).
 //   A operand: lane l -> variant row (l&15), k-group (l>>4): 16 B = 16 samples;  B: digit column (l&15)
+// |k| <= 127 times a digit in [-128, 127]: one int32 accumulator holds at most 131 072 samples (byte_plan.hpp), so
+// blockIdx.y is the slice: `slice_chunks` chunks of the row from chunk blockIdx.y * slice_chunks on, summed into
+// block blockIdx.y of acc_out ([slice][plane][variant][column]); k_cprod_final8 adds the slices in 64 bits.
 template <int NB, bool HASNA, bool CONTIG>
 __global__ __launch_bounds__(512) void k_cprod8(const uint8_t *__restrict__ img, int64_t pitch,
                                                 const int32_t *__restrict__ cols, int64_t col0, int64_t m,
                                                 const int8_t *__restrict__ xq, int32_t *__restrict__ acc_out,
-                                                int64_t m_out) {
+                                                int64_t m_out, int slice_chunks) {
   constexpr int KC = 256, LD = KC / 64, NCOL = 16 * NB, XS = KC / 16 * NCOL, WAVES = 8, NT = 64 * WAVES;
   constexpr int NPL = HASNA ? 2 : 1;
   __shared__ uint4 xs[2][XS];
@@ -1138,9 +1142,11 @@ __global__ __launch_bounds__(512) void k_cprod8(const uint8_t *__restrict__ img,
   int64_t j = snp_base + c;
   if (j > m - 1) j = m - 1;
   const int64_t col = CONTIG ? col0 + j : (int64_t)cols[j];
-  const uint8_t *rowp = img + col * pitch + g * 16;
-  const int nchunks = (int)(pitch / KC);
-  const uint4 *xq4 = (const uint4 *)xq;
+  const int ch0 = (int)blockIdx.y * slice_chunks;   // (one slice: 0, and nchunks is the whole row)
+  const int nchunks = min((int)(pitch / KC) - ch0, slice_chunks);
+  const uint8_t *rowp = img + col * pitch + (int64_t)ch0 * KC + g * 16;
+  const uint4 *xq4 = (const uint4 *)xq + (int64_t)ch0 * XS;
+  acc_out += (int64_t)blockIdx.y * NPL * m_out * NCOL;
   v4i acc[NPL][NB];
 #pragma unroll
   for (int p = 0; p < NPL; p++)
@@ -1200,15 +1206,26 @@ __global__ __launch_bounds__(512) void k_cprod8(const uint8_t *__restrict__ img,
   }
 }
 
+// horner over the digit columns of k_cprod8, each summed over its `nslice` sample slices (`stride` int32 apart) in 64 bits
+__device__ __forceinline__ double horner_slices(const int32_t *a, int S, int nslice, int64_t stride) {
+  double r = 0;
+  for (int s = S - 1; s >= 0; s--) {
+    long long d = 0;
+    for (int t = 0; t < nslice; t++) d += a[t * stride + s];
+    r = r * 256.0 + (double)d;
+  }
+  return r;
+}
 // z[j, v] = (vstep P + (voff - c_j) (Sx - Q)) / (s_j qs):  value = voff + vstep k on non-missing genotypes
 __global__ void k_cprod_final8(const int32_t *acc, int64_t m, int ncol, int S, const VecMeta *meta,
                                const double *center, const double *scale, double *Z, int64_t ldz, int has_q,
-                               double vstep, double voff) {
+                               double vstep, double voff, int nslice) {
   int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int v = blockIdx.y;
   if (j >= m) return;
-  const double P = horner(acc + j * ncol + v * S, S);
-  const double Q = has_q ? horner(acc + (m + j) * ncol + v * S, S) : 0.0;
+  const int64_t stride = (has_q ? 2 : 1) * m * ncol;
+  const double P = horner_slices(acc + j * ncol + v * S, S, nslice, stride);
+  const double Q = has_q ? horner_slices(acc + (m + j) * ncol + v * S, S, nslice, stride) : 0.0;
   const double Sx = (double)meta[v].sum_hi * 16777216.0 + (double)meta[v].sum_lo;
   const double c = center ? center[j] : 0.0, s = scale ? scale[j] : 1.0, qs = meta[v].qscale;
   double z = qs > 0 ? (vstep * P + (voff - c) * (Sx - Q)) / (s * qs) : 0.0 / s;
@@ -1786,6 +1803,8 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
   refuse_generic(b, "this function (it needs the streaming products)");
   const int S = op->slices;
   if (nvec <= 0) return;
+  if (b->bits == 8 && byte_slices(b->pitch) > kByteMaxSlices)
+    fail("the crossproduct on a dosage FBM supports at most %lld samples", (long long)(kByteMaxSlices * kSliceBytes));
   op_na_blocks(op, nvec * S);
   const bool have_digits = op->preq_X == d_X && op->preq_ldx == ldx && op->preq_nvec == nvec && d_X != nullptr &&
                            op->preq_S == S && nvec <= cprod_vmax(op, S);
@@ -1798,15 +1817,17 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
     int nv = nvec - v0 < vmax ? nvec - v0 : vmax;
     int NB = pick_nb(nv * S), ncol = 16 * NB;
     int8_t *q = op->d_q.ensure((size_t)npad * kMaxCols * 2);
-    int32_t *acc = op->d_acc.ensure((size_t)2 * op->m * kMaxCols);
+    // (byte image: one block of partial sums per 131 072-sample slice)
+    const int nslice = b->bits == 8 ? byte_slices(b->pitch) : 1;
+    int32_t *acc = op->d_acc.ensure(std::max((size_t)2 * op->m * kMaxCols, (size_t)nslice * 2 * op->m * ncol));
     if (!have_digits) quantise(op, xsrc + (int64_t)v0 * ldx, ldx, b->n, npad, nv, 0, S, ncol, 1, 0, meta, q);
     prof_begin(op, op->stats_pending ? 2 : NB == 3 ? 4 : 0);  // the pass that carries the code counts is timed apart
     if (b->bits == 8) {
-      const dim3 grid8((unsigned)((op->m + 127) / 128));
+      const dim3 grid8((unsigned)((op->m + 127) / 128), (unsigned)nslice);
       const int32_t *cols8 = op->cols_contig ? nullptr : op->d_cols.p;
 #define BSN_CPROD8(NBV, NAV, CV)                                                                          \
   BSN_KLAUNCH((k_cprod8<NBV, NAV, CV>), grid8, dim3(512), 0, b->stream, b->d_img, b->pitch, cols8, \
-                     op->col0, op->m, q, acc, op->m)
+                     op->col0, op->m, q, acc, op->m, (int)(kSliceBytes / 256))
       if (NB == 1) {
         if (op->no_na) { if (op->cols_contig) BSN_CPROD8(1, false, true); else BSN_CPROD8(1, false, false); }
         else { if (op->cols_contig) BSN_CPROD8(1, true, true); else BSN_CPROD8(1, true, false); }
@@ -1820,7 +1841,7 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
       op->passes++;
       hipLaunchKernelGGL(k_cprod_final8, dim3((unsigned)((op->m + 255) / 256), nv), dim3(256), 0, b->stream, acc,
                          op->m, ncol, S, meta, op->d_center.p, op->d_scale.p, d_Z + (int64_t)v0 * ldz, ldz,
-                         op->no_na ? 0 : 1, b->v_step, b->v_off);
+                         op->no_na ? 0 : 1, b->v_step, b->v_off, nslice);
       BSN_HIP(hipGetLastError());
       continue;
     }
@@ -2015,10 +2036,11 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
     if (ky < 1) ky = 1;
   }
 #endif
-  // int32 accumulators: a slab adds at most 768 per variant (planes up to 4, digits up to 128)
-  const int64_t ky_min = (m_pad + 2499999) / 2500000;
+  // int32 accumulators: a slab adds at most 768 per variant (planes up to 4, digits up to 128); on a byte image
+  // 127 * 128 (grid indices up to 127), which leaves 132 104 variants per slab (byte_plan.hpp)
+  const int64_t ky_min = b->bits == 8 ? byte_min_slabs(m_pad) : (m_pad + 2499999) / 2500000;
   if (ky < ky_min && !smaj) ky = (int)ky_min;
-  int64_t mc = round_up((steps + ky - 1) / ky, 1) * 64;
+  const int64_t mc = slab_variants(steps, ky);
   if (!smaj) ky = (int)((m_pad + mc - 1) / mc);
   // complete variants: the missing-value plane is all zero, skip its look-ups and MFMAs
   const bool has_q = lutQ != 0u && !(op->no_na && lutQ == kLutNA);

@@ -367,4 +367,19 @@ void nt_ld_k_split(int64_t pitch, int64_t want, int64_t align, int64_t min_bytes
   const KSplit k = k_split(pitch, want, align, min_bytes);
   out[0] = k.splits, out[1] = k.bytes;
 }
+// byte image (byte_plan.hpp and the two split rules of ld_plan.hpp): what band_run, op_cprod and prod_planes launch with
+// out: slices of the row, splits (byte_xy: per slice; byte_na: over the row), bytes per split
+void nt_byte_xy_split(int64_t pitch, int64_t np, int64_t *out) {
+  const KSplit k = byte_xy_split(pitch, np);
+  out[0] = byte_slices(pitch), out[1] = k.splits, out[2] = k.bytes;
+}
+void nt_byte_na_split(int64_t pitch, int64_t np, int64_t *out) {
+  const KSplit k = byte_na_split(pitch, np);
+  out[0] = byte_slices(pitch), out[1] = k.splits, out[2] = k.bytes;
+}
+// out: kSliceBytes, kByteMaxSlices, kByteTermMax, kByteSlabVariants
+void nt_byte_limits(int64_t *out) { out[0] = kSliceBytes, out[1] = kByteMaxSlices, out[2] = kByteTermMax, out[3] = kByteSlabVariants; }
+// the slabs of prod_planes on a byte image: the fewest it may launch, and the variants per slab when it launches ky
+int64_t nt_byte_min_slabs(int64_t m_pad) { return byte_min_slabs(m_pad); }
+int64_t nt_slab_variants(int64_t steps, int64_t ky) { return slab_variants(steps, ky); }
 }

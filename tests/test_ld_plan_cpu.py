@@ -1,5 +1,6 @@
 """The kernel choice of the windowed-LD band (bigsnpr_amd/csrc/ld_plan.hpp: plan_band, xy_kernel, small_band_kernel,
-k_split), pinned on the CPU through tests/native.  The expected values are literal: they were written from the
+k_split) and the split geometry of the byte image (byte_xy_split, byte_na_split, byte_plan.hpp), pinned on the CPU through
+tests/native.  The expected values are literal: they were written from the
 conditions of band_run as it stood before the decision was moved out of it, one row per kernel id that
 bsn_ld_last_stats can report (0-4, 6-11) and one on either side of every threshold."""
 import ctypes as C
@@ -27,6 +28,11 @@ def nt():
     lib = C.CDLL(build_native.build())
     lib.nt_ld_xy_kernel.argtypes = [C.c_void_p, C.c_int64]
     lib.nt_ld_k_split.argtypes = [C.c_int64] * 4 + [C.c_void_p]
+    lib.nt_byte_xy_split.argtypes = lib.nt_byte_na_split.argtypes = [C.c_int64] * 2 + [C.c_void_p]
+    lib.nt_byte_limits.argtypes = [C.c_void_p]
+    lib.nt_byte_min_slabs.argtypes = [C.c_int64]
+    lib.nt_slab_variants.argtypes = [C.c_int64] * 2
+    lib.nt_byte_min_slabs.restype = lib.nt_slab_variants.restype = C.c_int64
     return lib
 
 
@@ -143,3 +149,80 @@ def test_k_split(nt, args, want):
     nt.nt_ld_k_split(*args, out.ctypes.data_as(C.c_void_p))
     assert (int(out[0]), int(out[1])) == want
     assert out[0] * out[1] >= args[0] and out[1] % args[2] == 0   # the splits cover the row in aligned pieces
+
+
+# ---- byte image: the exact-integer size argument (byte_plan.hpp) and the two split rules band_run launches with -----------------
+SLICE = 131072
+# every slice count, ragged and exact multiples, and the neighbours of a boundary (a pitch is a multiple of 256)
+BYTE_PITCHES = sorted({256, 512, 1280, 100096, SLICE - 256, SLICE, SLICE + 256, 135424, 2 * SLICE - 256, 2 * SLICE, 2 * SLICE + 256,
+                       3 * SLICE - 4096, 3 * SLICE, 3 * SLICE + 256, 4 * SLICE, 4 * SLICE + 65536, 5 * SLICE, 5 * SLICE + 256, 6 * SLICE - 256,
+                       6 * SLICE} | {s * SLICE + 256 * 37 * s for s in range(1, 6)})
+BYTE_NP = sorted(set(range(1, 40)) | {2 ** e for e in range(13)} | {2 ** e + 1 for e in range(12)} | {2 ** e - 1 for e in range(2, 13)} |
+                 {100, 300, 511, 513, 1000, 3000})
+
+
+def _limits(nt):
+    out = np.zeros(4, dtype=np.int64)
+    nt.nt_byte_limits(out.ctypes.data_as(C.c_void_p))
+    return tuple(int(v) for v in out)
+
+
+def test_byte_limits(nt):
+    slice_bytes, max_slices, term_max, slab = _limits(nt)
+    assert (slice_bytes, max_slices, term_max) == (SLICE, 6, 127 * 128)
+    assert term_max * slice_bytes < 2 ** 31                       # one slice of samples fits an int32 accumulator
+    assert slab % 64 == 0 and slab <= (2 ** 31 - 1) // term_max == 132104 < slab + 64   # and so does one slab of variants
+    assert BYTE_PITCHES[0] == 256 and BYTE_PITCHES[-1] == max_slices * slice_bytes and BYTE_NP[0] == 1 and BYTE_NP[-1] == 4096
+    assert {-(-p // SLICE) for p in BYTE_PITCHES} == {1, 2, 3, 4, 5, 6}
+    assert all(any(-(-p // SLICE) == s and p % SLICE != 0 for p in BYTE_PITCHES) for s in range(1, 7))
+
+
+@pytest.mark.parametrize("pitch", BYTE_PITCHES)
+def test_byte_xy_split(nt, pitch):
+    """k_pair_xy8: grid y = splits per slice x slices, split y covers [y bytes, (y + 1) bytes) and adds to plane y // splits"""
+    out = np.zeros(3, dtype=np.int64)
+    for np_ in BYTE_NP:
+        nt.nt_byte_xy_split(pitch, np_, out.ctypes.data_as(C.c_void_p))
+        nslice, splits, nbytes = (int(v) for v in out)
+        assert nslice == -(-pitch // SLICE) and splits >= 1
+        grid_y = splits * nslice
+        assert nbytes % 64 == 0 and nbytes >= 64
+        assert grid_y * nbytes >= pitch                            # the splits cover [0, pitch)
+        b0 = np.arange(grid_y, dtype=np.int64) * nbytes
+        b1 = np.minimum(b0 + nbytes, pitch)
+        live = b0 < b1
+        assert live[0] and b1[live][-1] == pitch and np.all(b0[live][1:] == b1[live][:-1])
+        plane = np.arange(grid_y) // splits                        # the kernel's `slice`
+        assert np.all(b0[live] // SLICE == plane[live]) and np.all((b1[live] - 1) // SLICE == plane[live])   # none straddles
+        assert plane.max() == nslice - 1
+        if nslice == 1:                                            # one slice: k_split as before
+            k = np.zeros(2, dtype=np.int64)
+            nt.nt_ld_k_split(pitch, max(1, 8192 // np_), 64, 256, k.ctypes.data_as(C.c_void_p))
+            assert (splits, nbytes) == (int(k[0]), int(k[1]))
+        else:
+            assert splits & (splits - 1) == 0 and splits * nbytes == SLICE and nbytes >= 256
+
+
+@pytest.mark.parametrize("pitch", BYTE_PITCHES)
+def test_byte_na_split(nt, pitch):
+    """k_pair_stats8: grid y = splits over the whole row; a split adds int32 sums into int64 statistics, so only its length counts"""
+    out = np.zeros(3, dtype=np.int64)
+    for np_ in BYTE_NP:
+        nt.nt_byte_na_split(pitch, np_, out.ctypes.data_as(C.c_void_p))
+        nslice, splits, nbytes = (int(v) for v in out)
+        assert nbytes % 64 == 0 and 64 <= nbytes <= SLICE          # no longer than a slice
+        assert splits >= nslice and splits * nbytes >= pitch > (splits - 1) * nbytes   # cover [0, pitch), no empty split
+        assert splits <= 65535
+
+
+def test_byte_slabs(nt):
+    """k_prod8: whatever number of slabs the grid rule of prod_planes asks for, none holds more than 132 104 variants"""
+    slab = _limits(nt)[3]
+    for m_pad in [64, 128, slab - 64, slab, slab + 64, 2 * slab, 2 * slab + 64, 1000000 // 64 * 64, 2500032, 5000000 // 64 * 64,
+                  20 * slab + 64]:
+        ky_min = nt.nt_byte_min_slabs(m_pad)
+        assert ky_min == -(-m_pad // slab)
+        assert ky_min == 1 or nt.nt_slab_variants(m_pad // 64, ky_min - 1) > slab      # the bound is tight
+        for ky in sorted({ky_min, ky_min + 1, 2 * ky_min, max(ky_min, 17), max(ky_min, 64)}):
+            mc = nt.nt_slab_variants(m_pad // 64, ky)
+            assert mc % 64 == 0 and 64 <= mc <= slab <= 132104 and mc * ky >= m_pad
