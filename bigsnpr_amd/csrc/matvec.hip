@@ -24,6 +24,7 @@
 
 #include "bsn_internal.hpp"
 #include "byte_plan.hpp"
+#include "prod_plan.hpp"
 #include "prodt_sparse.hpp"
 #include <type_traits>
 
@@ -245,21 +246,9 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
       // missing-value plane carries c w - 3 w, in exact integers: 3 A + (B - 3 A) - B == 0
       if ((raw3 & 1) && PERM != 2) B -= 3 * A;
       const int pos = PERM == 1 ? ((e & 3) * 4 + (e >> 2)) : e;
-#ifdef BSN_ABLATION
-      // BSN_DIGITS=2 (timing only: the finalize kernels read balanced base-256 digits): sign x 7-bit magnitude chunks
-      const bool sm = (raw3 >> 8) == 2;
-      const long long sgA = A < 0 ? -1 : 1, sgB = B < 0 ? -1 : 1;
-      long long mA = A < 0 ? -A : A, mB = B < 0 ? -B : B;
-#endif
 #pragma unroll
       for (int s = 0; s < S; s++) {
-#ifdef BSN_ABLATION
-        const int8_t da = sm ? (int8_t)(sgA * (mA & 0x7F)) : (int8_t)(A & 0xFF), db = sm ? (int8_t)(sgB * (mB & 0x7F)) : (int8_t)(B & 0xFF);
-        mA >>= 7;
-        mB >>= 7;
-#else
         const int8_t da = (int8_t)(A & 0xFF), db = (int8_t)(B & 0xFF);
-#endif
         A = (A - da) >> 8;
         B = (B - db) >> 8;
         if constexpr (PERM == 2) {
@@ -275,13 +264,7 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
     for (int p = 0; p < nplanes; p++)
 #pragma unroll
       for (int s = 0; s < S; s++) {
-#ifdef BSN_ABLATION
-        // BSN_DIGITS=1 (timing only): slice-major columns — digit s of all vectors side by side, so that with 16 vectors
-        // of three digits every column block holds ONE digit position
-        const int col = (raw3 >> 8) == 1 ? s * (int)gridDim.y + v : v * S + s;
-#else
         const int col = v * S + s;
-#endif
         int8_t *dst = q + ((kb * nplanes + p) * ncol + col) * 16;
         *(uint4 *)dst = p == 0 ? uint4{pk[0][s][0], pk[0][s][1], pk[0][s][2], pk[0][s][3]}
                                : uint4{pk[1][s][0], pk[1][s][1], pk[1][s][2], pk[1][s][3]};
@@ -312,7 +295,6 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
 // RAW0: plane 0 is the device code itself (no look-up).  STATS: the per-variant counts of the
 // codes 1, 2 and missing over all samples ride along (popcounts on the raw dwords; the first
 // crossproduct pass of a solve, which thereby replaces the separate statistics pass).
-// ABL != 0 only exists in -DBSN_ABLATION builds (profiling variants that compute wrong numbers).
 // CONTIG: the variants are col0 .. col0+m-1; the genotype loads are then buffer loads with a
 // scalar descriptor based at the workgroup's first row, one 32-bit lane offset per tile and a scalar
 // chunk offset, so that addressing costs no VALU (global loads spend a 64-bit add on each).
@@ -326,8 +308,8 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
 // step without a missing code is zero).  Chosen by the host from the measured share of such steps (op_na_blocks):
 // at 1 % scattered missing values no step is free and the branch only costs; on nearly complete or batch-structured
 // data most are.
-template <int NB, int NPLANE, int KC, bool RAW0, bool STATS, bool CONTIG, int ABL = 0, int TILES = 2,
-          int WAVES = 8, int MINW = 1, int TAG = 0, bool TILED = false, int SGB = 0, bool NASKIP = false>
+template <int NB, int NPLANE, int KC, bool RAW0, bool STATS, bool CONTIG, int TILES = 2, int WAVES = 8, int MINW = 1,
+          int TAG = 0, bool TILED = false, int SGB = 0, bool NASKIP = false>
 __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__restrict__ img, int64_t pitch,
                                                const int32_t *__restrict__ cols, int64_t col0,
                                                int64_t m, const int8_t *__restrict__ xq,
@@ -363,10 +345,8 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
   // 16 B of tile t at byte `off` (uniform) of the variant row
   auto gload = [&](const int t, const int off) -> uint4 {
     if constexpr (CONTIG) {
-      // ablation 64 / 128: nt / sc1 cache policy on the genotype stream (correct results)
-      constexpr int AUX = ((ABL & 64) ? 2 : 0) | ((ABL & 128) ? 16 : 0);
       const int soff = TILED ? ((off >> 8) << 14) + (off & 255) : off;
-      const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff[t], soff, AUX);
+      const v4u r = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff[t], soff, 0);
       return uint4{r.x, r.y, r.z, r.w};
     } else {
       return *(const uint4 *)(rowp[t] + off);
@@ -431,7 +411,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
       if constexpr (NX > 3) xr3 = src[at(3)];
     }
     __builtin_amdgcn_sched_barrier(0);  // keep the digit loads up here, a chunk ahead of their use
-    if constexpr (SGB & 2) __builtin_amdgcn_s_setprio(2);  // experiment: the MFMA phase outranks waves that are loading
+    if constexpr (SGB & 2) __builtin_amdgcn_s_setprio(2);  // the MFMA phase outranks waves that are loading
     const int off2 = ch2 * (KC / 4);
     // one K-step of one tile: 16 samples x 16 variants per lane-quad, decode + MFMAs
     auto kstep = [&](const int t, const uint32_t w, const uint4 (&bv)[NB]) {
@@ -452,9 +432,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
         if (NASKIP && p == 1 && !plane1) continue;
         const uint32_t lut = p == 0 ? lutA : p == 1 ? lutB : lutC;
         v4i a;
-        if (ABL & 2) {  // ablation: no decode, raw bits as operand
-          a = v4i{(int)w, (int)(w ^ lut), (int)s1, (int)s3};
-        } else if (RAW0 && p == 0) {
+        if (RAW0 && p == 0) {
           a = v4i{(int)s0, (int)s1, (int)s2, (int)s3};
         } else {
           a = v4i{(int)lut4(lut, s0), (int)lut4(lut, s1), (int)lut4(lut, s2), (int)lut4(lut, s3)};
@@ -462,11 +440,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
           v4i b = {(int)bv[nb].x, (int)bv[nb].y, (int)bv[nb].z, (int)bv[nb].w};
-          if (ABL & 1) {  // ablation: no MFMA, keep the operands alive
-            asm volatile("" ::"v"(a), "v"(b));
-          } else {
-            acc[t][p][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc[t][p][nb], 0, 0, 0);
-          }
+          acc[t][p][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc[t][p][nb], 0, 0, 0);
         }
       }
     };
@@ -476,12 +450,6 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
     uint4 bv[NB], bn[PFB ? NB : 1];
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) bv[nb] = xs[SET][(g * 4) * NCOL + nb * 16 + c];
-    if constexpr (PFB) {
-      if (ABL & 4) {  // ablation: digit operand read once per chunk instead of once per K-step
-#pragma unroll
-        for (int nb = 0; nb < NB; nb++) bn[nb] = bv[nb];
-      }
-    }
 #pragma unroll
     for (int it = 0; it < LD; it++) {
 #pragma unroll
@@ -493,10 +461,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
 #pragma unroll
             for (int nb = 0; nb < NB; nb++) bv[nb] = xs[SET][(it * 16 + g * 4 + d) * NCOL + nb * 16 + c];
           }
-        } else if (ABL & 16) {  // ablation: no LDS read of the digit operand
-#pragma unroll
-          for (int nb = 0; nb < NB; nb++) { bn[nb] = bv[nb]; bn[nb].x += 1; }
-        } else if (!(ABL & 4) && it * 4 + d + 1 < LD * 4) {
+        } else if (it * 4 + d + 1 < LD * 4) {
           const int itn = (it * 4 + d + 1) / 4, dn = (it * 4 + d + 1) % 4;
 #pragma unroll
           for (int nb = 0; nb < NB; nb++) bn[nb] = xs[SET][(itn * 16 + g * 4 + dn) * NCOL + nb * 16 + c];
@@ -519,13 +484,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
 #pragma unroll
     for (int t = 0; t < TILES; t++)
 #pragma unroll
-      for (int it = 0; it < LD; it++) {
-        if (ABL & 32) {  // ablation: no genotype loads after the prologue
-          ga[SET][t][it].x ^= (uint32_t)off2;
-        } else {
-          ga[SET][t][it] = gload(t, off2 + it * 64);
-        }
-      }
+      for (int it = 0; it < LD; it++) ga[SET][t][it] = gload(t, off2 + it * 64);
     if constexpr (SGB & 1) {
       // Explicit software pipeline (profiles/r04_sched.txt: 2 % on the two-block kernel): the decode of the following
       // K-steps is slotted into the shadows of the MFMAs — the VALU instructions of a K-step spread evenly behind its
@@ -564,7 +523,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
       if constexpr (NX > 2) if (staged(2)) xs[SET ^ 1][tid + 2 * NT] = xr2;
       if constexpr (NX > 3) if (staged(3)) xs[SET ^ 1][tid + 3 * NT] = xr3;
     }
-    if (!(ABL & 8)) __syncthreads();  // ablation 8: no barrier
+    __syncthreads();
   };
   for (int ch = 0; ch < nchunks; ch += 2) {
     chunk(std::integral_constant<int, 0>{}, ch);
@@ -675,11 +634,11 @@ __global__ __launch_bounds__(128) void k_cprod_final(const int32_t *__restrict__
 //   D        : lane l -> sample group (l&15), digit columns 4*(l>>4)+r
 // RAWP: the P plane is the device code itself (no look-up).
 // TILED: `img` is the streaming-layout copy; a step of the workgroup (64 variants x 256 B) is one tile.
-// TAG only changes the kernel's name (warm-start launches).  ABL != 0: -DBSN_ABLATION builds only.
+// TAG only changes the kernel's name (warm-start launches).
 // (Shapes that were measured and dropped — 8-wave workgroups, three register sets, 2 / 4 samples decoded together,
 // XCD-aware slab placement, wave pairs / lane halves with 64 accumulators, an explicit MFMA : VALU schedule, the codes as
 // the A operand: profiles/r02_ablation.txt, r03_shape_sweeps.txt, r04_two_block_kernels.txt.)
-template <int NB, bool CONTIG, bool RAWP, bool HASQ = true, int ABL = 0, int TAG = 0, bool TILED = false>
+template <int NB, bool CONTIG, bool RAWP, bool HASQ = true, int TAG = 0, bool TILED = false>
 __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, int64_t pitch,
                                               const int32_t *__restrict__ cols, int64_t col0,
                                               int64_t m_pad, int64_t mc,
@@ -783,12 +742,7 @@ __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, i
       T[3][r4] = perm8(hi23, hi01, 0x07060302u);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (ABL & 32) {  // ablation: no genotype loads after the prologue
-#pragma unroll
-      for (int r = 0; r < 16; r++) X[SET][r] += (uint32_t)jn2;
-    } else {
-      load(jn2, X[SET]);
-    }
+    load(jn2, X[SET]);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int q = 0; q < 4; q++)
@@ -798,23 +752,14 @@ __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, i
 #pragma unroll
         for (int r4 = 0; r4 < 4; r4++) {
           const uint32_t sel = (T[q][r4] >> (2 * u0)) & 0x03030303u;
-          if (ABL & 2) {  // ablation: no decode
-            g0[r4] = (int)T[q][r4];
-            na[r4] = (int)(T[q][r4] ^ lutQ);
-          } else {
-            g0[r4] = RAWP ? (int)sel : (int)lut4(lutP, sel);
-            if (HASQ) na[r4] = (int)lut4(lutQ, sel);
-          }
+          g0[r4] = RAWP ? (int)sel : (int)lut4(lutP, sel);
+          if (HASQ) na[r4] = (int)lut4(lutQ, sel);
         }
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) {
-          if (ABL & 1) {  // ablation: no MFMA
-            asm volatile("" ::"v"(g0), "v"(na), "v"(aw[nb]), "v"(awc[nb]));
-          } else {
-            acc[q * 4 + u0][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[nb], g0, acc[q * 4 + u0][nb], 0, 0, 0);
-            if (HASQ)
-              acc[q * 4 + u0][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(awc[nb], na, acc[q * 4 + u0][nb], 0, 0, 0);
-          }
+          acc[q * 4 + u0][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(aw[nb], g0, acc[q * 4 + u0][nb], 0, 0, 0);
+          if (HASQ)
+            acc[q * 4 + u0][nb] = __builtin_amdgcn_mfma_i32_16x16x64_i8(awc[nb], na, acc[q * 4 + u0][nb], 0, 0, 0);
         }
       }
     ws[SET ^ 1][wtid] = wreg;
@@ -1378,16 +1323,7 @@ void prof_collect(bsn_op *op, double ms[kProfKinds], int count[kProfKinds]) {
   op->ev_more.clear();
 }
 
-// Column blocks of 16 digit columns per launch.  Three (48 columns: 16 vectors x 3 slices, the early steps of a solve
-// whose vectors are wanted beyond the 16-bit floor, svd_driver.hpp) exist for the two shapes such a solve runs on —
-// k_cprod on the 2-bit image and k_prodT on its sample-major copy; everything else stays at two.
-constexpr int kMaxCols = 48;
-static int pick_nb(int ncols_needed) { return ncols_needed <= 16 ? 1 : ncols_needed <= 32 ? 2 : 3; }
-static bool nb3_allowed() {
-  static const bool on = getenv("BSN_NO_NB3") == nullptr;   // A/B switch: the same sums in two launches (bit-identical)
-  return on;
-}
-constexpr int kMetaVecs = 32;   // vectors per launch at most
+// (kMaxCols, kMetaVecs, pick_nb: prod_plan.hpp)
 static VecMeta *meta_buffer(bsn_op *op) {
   return (VecMeta *)op->d_meta.ensure((size_t)kMetaVecs * 8 + (size_t)kMetaVecs * 256 * 2);
 }
@@ -1400,13 +1336,7 @@ static void quantise(bsn_op *op, const double *d_X, int64_t ldx, int64_t len, in
   hipStream_t st = op->bed->stream;
   const bool bytes = op->bed->bits == 8;
   const double vstep = bytes ? op->bed->v_step : 1.0, voff = bytes ? op->bed->v_off : 0.0;
-  int raw3 = (!bytes && mode == 1) ? 1 : 0;
-#ifdef BSN_ABLATION
-  // energy experiments of round 5 (profiles/r05_power.txt): BSN_DIGITS=1 slice-major digit columns, =2 sign x 7-bit
-  // magnitude digits.  The streaming kernels run on these operands at their real cost; the RESULTS are wrong (the
-  // finalize kernels read vector-major balanced digits), so this exists in the profiling build only.
-  if (const char *dg = getenv("BSN_DIGITS")) raw3 |= atoi(dg) << 8;
-#endif
+  const int raw3 = (!bytes && mode == 1) ? 1 : 0;
   if (bytes) permute = 0;  // the byte image holds the samples of a 16-block in natural order
   if (permute == 2 && !(mode == 1 && (raw3 & 1))) fail("internal: the interleaved digit rows are the scaled product's");
   // meta: kMetaVecs records, then the slice maxima of k_absmax (kMetaVecs x 256 x 2 doubles)
@@ -1461,20 +1391,6 @@ static const double *scatter_rows_if_needed(bsn_op *op, const double *d_X, int64
   return xf;
 }
 
-// Ablation builds only (-DBSN_ABLATION, tools/build_ablation.py): BSN_TUNE selects profiling
-// variants of the two streaming kernels that compute wrong numbers by construction.  The product
-// library contains none of them.
-#ifdef BSN_ABLATION
-static int tune_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("BSN_TUNE");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
-}
-#endif
-
 // binomial scaling from the code counts (R/binom-scaling.R:133-142 on the sums of
 // src/bed-fun.cpp:22-38: sumX = n1 + 2 n2, nb_nona = n - nNA), same operations in the same order
 #pragma clang fp contract(off)
@@ -1523,133 +1439,68 @@ __global__ __launch_bounds__(256) void k_stats_summary(const int32_t *counts, in
 
 // the streaming-layout copy serves an operator over a 64-aligned contiguous range of variants
 static bool use_tiled(const bsn_op *op) {
-#ifdef BSN_ABLATION
-  if (tune_variant() != 0) return false;   // the profiling variants exist on the plain image only
-#endif
   return op->bed->d_tiled != nullptr && op->cols_contig && (op->col0 & 63) == 0;
 }
 
+// One crossproduct launch: the instance that choose_cprod (prod_plan.hpp) names, on the image it reads.  The list below is
+// the instances that exist — the counting and the three-plane pass have no three-block kernel, only the plain pass has
+// skipping ones; tiles per wave on the tiled copy: 4, the counting pass 2.
 template <int NPLANE, bool RAW0, bool STATS>
 static void launch_cprod(bsn_op *op, int NB, const int8_t *q, int32_t *acc, uint32_t l0,
                          uint32_t l1, uint32_t l2, int32_t *counts = nullptr) {
   bsn_bed *b = op->bed;
-  constexpr int KC = 512;
+  constexpr int KC = 512, TT = STATS ? 2 : 4;
+  constexpr bool PLAIN = NPLANE == 2 && RAW0 && !STATS;
   // int32 accumulators over the whole sample range: a plane adds at most 4 * 128 per sample
   if (b->pitch * 4 > 4000000) fail("more than 4e6 samples are not supported by the crossproduct kernel");
   const int32_t *cols = op->cols_contig ? nullptr : op->d_cols.p;
   const int32_t npad = (int32_t)(b->pitch * 4 - b->n);
-  const bool warm = op->prof_kind_override == 3;   // warm-start launches run under their own kernel name (TAG = 1)
-  // k_cprod<NB, NPLANE, KC, RAW0, STATS, CONTIG, ABL, TILES, WAVES, MINW, TAG, TILED, SGB> on `image`
-#define BSN_CPROD(NBV, CONTIGV, ABLV, TV, WV, TAGV, TILEDV, SGBV, image)                                              \
-  BSN_KLAUNCH((k_cprod<NBV, NPLANE, KC, RAW0, STATS, CONTIGV, ABLV, TV, WV, 1, TAGV, TILEDV, SGBV>),                  \
-              dim3((unsigned)((op->m + 16 * TV * WV - 1) / (16 * TV * WV))), dim3(64 * WV), 0, b->stream, image,      \
-              b->pitch, cols, op->col0, op->m, q, acc, op->m, l0, l1, l2, counts, npad)
-  // Shapes (profiles/r02_ablation.txt, r03_shape_sweeps.txt, r04_two_block_kernels.txt): one column block — 8 waves x 2
-  // tiles on the plain image, 8 x 4 on the tiled copy (2 % faster there; the counting variant needs 150 registers with
-  // 4 tiles and keeps 2); two column blocks — 16 waves x 2 tiles share one digit panel (half the L2 reads of it), with
-  // the explicit MFMA / decode interleave + raised priority through the MFMA phase (SGB = 3: 2 %).
-  if constexpr (NPLANE == 2 && RAW0 && !STATS) {
-    if (op->na_skip_c && NB >= 2) {   // the missing-value plane only where a K-step has a missing code (op_na_blocks)
-      if (NB == 3) {
-        if (op->cols_contig) BSN_KLAUNCH((k_cprod<3, 2, KC, true, false, true, 0, 2, 16, 1, 0, false, 0, true>),
-                                         dim3((unsigned)((op->m + 511) / 512)), dim3(1024), 0, b->stream, b->d_img, b->pitch,
-                                         cols, op->col0, op->m, q, acc, op->m, l0, l1, l2, counts, npad);
-        else BSN_KLAUNCH((k_cprod<3, 2, KC, true, false, false, 0, 2, 16, 1, 0, false, 0, true>),
-                         dim3((unsigned)((op->m + 511) / 512)), dim3(1024), 0, b->stream, b->d_img, b->pitch, cols, op->col0,
-                         op->m, q, acc, op->m, l0, l1, l2, counts, npad);
-      } else {
-        if (op->cols_contig) BSN_KLAUNCH((k_cprod<2, 2, KC, true, false, true, 0, 2, 16, 1, 0, false, 0, true>),
-                                         dim3((unsigned)((op->m + 511) / 512)), dim3(1024), 0, b->stream, b->d_img, b->pitch,
-                                         cols, op->col0, op->m, q, acc, op->m, l0, l1, l2, counts, npad);
-        else BSN_KLAUNCH((k_cprod<2, 2, KC, true, false, false, 0, 2, 16, 1, 0, false, 0, true>),
-                         dim3((unsigned)((op->m + 511) / 512)), dim3(1024), 0, b->stream, b->d_img, b->pitch, cols, op->col0,
-                         op->m, q, acc, op->m, l0, l1, l2, counts, npad);
-      }
-      BSN_HIP(hipGetLastError());
-      return;
-    }
+  CprodFacts f;
+  f.NB = NB, f.plain = PLAIN, f.stats = STATS, f.cols_contig = op->cols_contig, f.tiled = use_tiled(op);
+  f.warm = op->prof_kind_override == 3, f.na_skip = op->na_skip_c;
+  const CprodKernel k = choose_cprod(f);
+  const uint8_t *image = k.tiled ? b->d_tiled : b->d_img;
+  const int per_wg = 16 * k.tiles * k.waves;   // variants of a workgroup
+  const dim3 grid((unsigned)((op->m + per_wg - 1) / per_wg)), block(64 * k.waves);
+#define BSN_CPROD(NBV, CONTIGV, TV, WV, TAGV, TILEDV, SGBV, NASKIPV)                                                   \
+  if (k == CprodKernel{NBV, CONTIGV, TV, WV, TAGV, TILEDV, SGBV, NASKIPV}) {                                           \
+    BSN_KLAUNCH((k_cprod<NBV, NPLANE, KC, RAW0, STATS, CONTIGV, TV, WV, 1, TAGV, TILEDV, SGBV, NASKIPV>), grid, block, \
+                0, b->stream, image, b->pitch, cols, op->col0, op->m, q, acc, op->m, l0, l1, l2, counts, npad);        \
+    BSN_HIP(hipGetLastError());                                                                                        \
+    return;                                                                                                            \
   }
-  if (NB == 3) {   // three column blocks: 16 waves x 2 tiles on the plain image (contiguous or gathered variants)
-    if constexpr (STATS || NPLANE == 3) {
-      fail("internal: no three-block counting kernel");
-    } else {
-#ifdef BSN_ABLATION
-      // shape sweep of the three-block kernel (profiling build only; correct results): BSN_NB3 bit 0: without the explicit
-      // MFMA / decode pipeline, bit 1: 8-wave workgroups (two per CU), bit 3: 4 tiles per wave in 8-wave workgroups
-      static const int nb3v = getenv("BSN_NB3") ? atoi(getenv("BSN_NB3")) : 0;
-      if (op->cols_contig && (nb3v & 11)) {
-        if ((nb3v & 11) == 1) BSN_CPROD(3, true, 0, 2, 16, 0, false, 0, b->d_img);
-        else if ((nb3v & 11) == 2) BSN_CPROD(3, true, 0, 2, 8, 0, false, 3, b->d_img);
-        else if ((nb3v & 11) == 3) BSN_CPROD(3, true, 0, 2, 8, 0, false, 0, b->d_img);
-        else BSN_CPROD(3, true, 0, 4, 8, 0, false, 0, b->d_img);
-        BSN_HIP(hipGetLastError());
-        return;
-      }
-#endif
-      if (op->cols_contig) BSN_CPROD(3, true, 0, 2, 16, 0, false, 3, b->d_img);
-      else BSN_CPROD(3, false, 0, 2, 16, 0, false, 0, b->d_img);
-    }
-    BSN_HIP(hipGetLastError());
-    return;
+  BSN_CPROD(1, false, 2, 8, 0, false, 0, false)
+  BSN_CPROD(1, true, 2, 8, 0, false, 0, false)
+  BSN_CPROD(1, true, 2, 8, 1, false, 0, false)
+  BSN_CPROD(1, true, TT, 8, 0, true, 0, false)
+  BSN_CPROD(1, true, TT, 8, 1, true, 0, false)
+  BSN_CPROD(2, false, 2, 16, 0, false, 0, false)
+  BSN_CPROD(2, true, 2, 16, 0, false, 3, false)
+  BSN_CPROD(2, true, 2, 16, 0, true, 3, false)
+  if constexpr (!STATS && NPLANE < 3) {
+    BSN_CPROD(3, false, 2, 16, 0, false, 0, false)
+    BSN_CPROD(3, true, 2, 16, 0, false, 3, false)
   }
-  if (use_tiled(op)) {
-    constexpr int TV = STATS ? 2 : 4;
-    if (NB == 1) { if (warm) BSN_CPROD(1, true, 0, TV, 8, 1, true, 0, b->d_tiled); else BSN_CPROD(1, true, 0, TV, 8, 0, true, 0, b->d_tiled); }
-    else BSN_CPROD(2, true, 0, 2, 16, 0, true, 3, b->d_tiled);
-    BSN_HIP(hipGetLastError());
-    return;
-  }
-#ifdef BSN_ABLATION
-  // BSN_TUNE (profiling variants; 11 .. 19 / 111 .. 119 compute wrong numbers by construction):
-  //   11 / 12 / 13 / 15 / 16 / 17 / 18 / 19   one column block: no MFMA / no decode / neither (memory skeleton) / no
-  //                                          barrier / no LDS operand reads / no genotype loads / no LDS at all / compute only
-  //   111 / 112 / 113 / 117 / 119            the same for two column blocks;  114: two blocks WITHOUT the explicit pipeline
-  //   121 / 123                              two blocks: pipeline alone / s_setprio alone (correct results)
-  if constexpr (NPLANE == 2 && RAW0 && !STATS) {
-    const int abl = tune_variant();
-    if (op->cols_contig && abl != 0) {
-      bool done = true;
-      if (NB == 1) {
-        switch (abl) {
-          case 11: BSN_CPROD(1, true, 1, 2, 8, 0, false, 0, b->d_img); break;
-          case 12: BSN_CPROD(1, true, 2, 2, 8, 0, false, 0, b->d_img); break;
-          case 13: BSN_CPROD(1, true, 3, 2, 8, 0, false, 0, b->d_img); break;
-          case 15: BSN_CPROD(1, true, 8, 2, 8, 0, false, 0, b->d_img); break;
-          case 16: BSN_CPROD(1, true, 16, 2, 8, 0, false, 0, b->d_img); break;
-          case 17: BSN_CPROD(1, true, 32, 2, 8, 0, false, 0, b->d_img); break;
-          case 18: BSN_CPROD(1, true, 24, 2, 8, 0, false, 0, b->d_img); break;
-          case 19: BSN_CPROD(1, true, 56, 2, 8, 0, false, 0, b->d_img); break;
-          default: done = false;
-        }
-      } else {
-        switch (abl) {
-          case 111: BSN_CPROD(2, true, 1, 2, 16, 0, false, 0, b->d_img); break;
-          case 112: BSN_CPROD(2, true, 2, 2, 16, 0, false, 0, b->d_img); break;
-          case 113: BSN_CPROD(2, true, 3, 2, 16, 0, false, 0, b->d_img); break;
-          case 114: BSN_CPROD(2, true, 0, 2, 16, 0, false, 0, b->d_img); break;
-          case 117: BSN_CPROD(2, true, 32, 2, 16, 0, false, 0, b->d_img); break;
-          case 119: BSN_CPROD(2, true, 56, 2, 16, 0, false, 0, b->d_img); break;
-          case 121: BSN_CPROD(2, true, 0, 2, 16, 0, false, 1, b->d_img); break;
-          case 123: BSN_CPROD(2, true, 0, 2, 16, 0, false, 2, b->d_img); break;
-          default: done = false;
-        }
-      }
-      if (done) {
-        BSN_HIP(hipGetLastError());
-        return;
-      }
-    }
-  }
-#endif
-  if (NB == 1) {
-    if (!op->cols_contig) BSN_CPROD(1, false, 0, 2, 8, 0, false, 0, b->d_img);
-    else if (warm) BSN_CPROD(1, true, 0, 2, 8, 1, false, 0, b->d_img);
-    else BSN_CPROD(1, true, 0, 2, 8, 0, false, 0, b->d_img);
-  } else {
-    if (op->cols_contig) BSN_CPROD(2, true, 0, 2, 16, 0, false, 3, b->d_img);
-    else BSN_CPROD(2, false, 0, 2, 16, 0, false, 0, b->d_img);
+  if constexpr (PLAIN) {
+    BSN_CPROD(2, false, 2, 16, 0, false, 0, true)
+    BSN_CPROD(2, true, 2, 16, 0, false, 0, true)
+    BSN_CPROD(3, false, 2, 16, 0, false, 0, true)
+    BSN_CPROD(3, true, 2, 16, 0, false, 0, true)
   }
 #undef BSN_CPROD
+  fail("internal: no crossproduct kernel with %d column blocks for this pass", NB);
+}
+
+// z = finalize of a crossproduct launch of NB column blocks
+static void launch_cprod_final(bsn_op *op, int NB, const int32_t *acc, int S, int nv, const VecMeta *meta, double *Z,
+                               int64_t ldz, bool has_q) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((op->m + 127) / 128)), dim3(128), 0, op->bed->stream, acc, op->m, S, nv, meta,
+                       op->d_center.p, op->d_scale.p, Z, ldz, has_q ? 1 : 0);
+  };
+  if (NB == 1) go(k_cprod_final<16>);
+  else if (NB == 2) go(k_cprod_final<32>);
+  else go(k_cprod_final<48>);
   BSN_HIP(hipGetLastError());
 }
 
@@ -1776,13 +1627,7 @@ void op_na_blocks(bsn_op *op, int digit_cols) {
   op->na_skip_p = b->na_free[1] >= min_free;
 }
 
-// vectors per crossproduct launch: three column blocks on a 2-bit image unless the launch also counts the codes
-static int cprod_vmax(const bsn_op *op, int S) {
-  const int nbmax = (op->bed->bits == 2 && !op->stats_pending && nb3_allowed()) ? 3 : 2;
-  int v = 16 * nbmax / S;
-  if (v > kMetaVecs) v = kMetaVecs;
-  return v < 1 ? 1 : v;
-}
+static int cprod_vmax(const bsn_op *op, int S) { return cprod_vmax(op->bed->bits, op->stats_pending, S); }
 
 void op_cprod_prequant(bsn_op *op, const double *d_X, int64_t ldx, int nvec) {
   bsn_bed *b = op->bed;
@@ -1866,65 +1711,81 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
     }
     const bool has_q = op->stats_pending || !op->no_na;
     if (op->stats_pending) finish_fused_stats(op);
-    if (NB == 1)
-      hipLaunchKernelGGL((k_cprod_final<16>), dim3((unsigned)((op->m + 127) / 128)), dim3(128), 0, b->stream, acc, op->m,
-                         S, nv, meta, op->d_center.p, op->d_scale.p, d_Z + (int64_t)v0 * ldz, ldz, has_q ? 1 : 0);
-    else if (NB == 2)
-      hipLaunchKernelGGL((k_cprod_final<32>), dim3((unsigned)((op->m + 127) / 128)), dim3(128), 0, b->stream, acc, op->m,
-                         S, nv, meta, op->d_center.p, op->d_scale.p, d_Z + (int64_t)v0 * ldz, ldz, has_q ? 1 : 0);
-    else
-      hipLaunchKernelGGL((k_cprod_final<48>), dim3((unsigned)((op->m + 127) / 128)), dim3(128), 0, b->stream, acc, op->m,
-                         S, nv, meta, op->d_center.p, op->d_scale.p, d_Z + (int64_t)v0 * ldz, ldz, has_q ? 1 : 0);
-    BSN_HIP(hipGetLastError());
+    launch_cprod_final(op, NB, acc, S, nv, meta, d_Z + (int64_t)v0 * ldz, ldz, has_q);
   }
 }
 
-template <int NB, bool CONTIG>
-static void launch_prod(bsn_op *op, dim3 grid, int64_t m_pad, int64_t mc, const int8_t *q, int32_t *acc,
+// One launch of k_prod: the instance that choose_prod (prod_plan.hpp) names, on the variant-major image or its tiled copy
+// (same arithmetic, contiguous 16-KB steps)
+static void launch_prod(bsn_op *op, int NB, dim3 grid, int64_t m_pad, int64_t mc, const int8_t *q, int32_t *acc,
                         int64_t npad, uint32_t lutP, uint32_t lutQ, bool has_q) {
   bsn_bed *b = op->bed;
   const int32_t *cols = op->d_cols.p;
-  const bool warm = op->prof_kind_override == 3;   // warm-start launches run under their own kernel name (TAG = 1)
-  // k_prod<NB, CONTIG, RAWP, HASQ, ABL, TAG, TILED> on `image`
-#define BSN_PROD(RAWP, HASQ, ABLV, TAGV, TILEDV, image)                                                        \
-  BSN_KLAUNCH((k_prod<NB, CONTIG, RAWP, HASQ, ABLV, TAGV, TILEDV>), grid, dim3(256), 0, b->stream, image,      \
-              b->pitch, cols, op->col0, m_pad, mc, q, acc, npad, lutP, lutQ)
-#ifdef BSN_ABLATION
-  // BSN_TUNE = 61 .. 64 (one column block) / 161 .. 164 (two): no MFMA / no decode / memory skeleton / compute only
-  if constexpr (CONTIG) {
-    const int tv = tune_variant() - (NB == 2 ? 100 : 0);
-    if (tv >= 61 && tv <= 64 && lutP == kLutRaw && has_q) {
-      if (tv == 61) BSN_PROD(true, true, 1, 0, false, b->d_img);
-      else if (tv == 62) BSN_PROD(true, true, 2, 0, false, b->d_img);
-      else if (tv == 63) BSN_PROD(true, true, 3, 0, false, b->d_img);
-      else BSN_PROD(true, true, 32, 0, false, b->d_img);
-      BSN_HIP(hipGetLastError());
-      return;
-    }
+  const ProdKernel k = choose_prod(NB, op->cols_contig, use_tiled(op), lutP == kLutRaw, has_q, op->prof_kind_override == 3);
+  const uint8_t *image = k.tiled ? b->d_tiled : b->d_img;
+#define BSN_PROD(NBV, CV, RAWP, HASQ, TAGV, TILEDV)                                                                  \
+  if (k == ProdKernel{NBV, CV, RAWP, HASQ, TAGV, TILEDV}) {                                                          \
+    BSN_KLAUNCH((k_prod<NBV, CV, RAWP, HASQ, TAGV, TILEDV>), grid, dim3(256), 0, b->stream, image, b->pitch, cols,   \
+                op->col0, m_pad, mc, q, acc, npad, lutP, lutQ);                                                      \
+    BSN_HIP(hipGetLastError());                                                                                      \
+    return;                                                                                                          \
   }
-#endif
-  if constexpr (CONTIG) {
-    if (use_tiled(op)) {  // streaming-layout copy: same arithmetic, contiguous 16-KB steps
-      if (lutP == kLutRaw) {
-        if (has_q) { if (warm) BSN_PROD(true, true, 0, 1, true, b->d_tiled); else BSN_PROD(true, true, 0, 0, true, b->d_tiled); }
-        else { if (warm) BSN_PROD(true, false, 0, 1, true, b->d_tiled); else BSN_PROD(true, false, 0, 0, true, b->d_tiled); }
-      } else {
-        if (has_q) BSN_PROD(false, true, 0, 0, true, b->d_tiled);
-        else BSN_PROD(false, false, 0, 0, true, b->d_tiled);
-      }
-      BSN_HIP(hipGetLastError());
-      return;
-    }
-  }
-  if (lutP == kLutRaw) {
-    if (has_q) { if (warm) BSN_PROD(true, true, 0, 1, false, b->d_img); else BSN_PROD(true, true, 0, 0, false, b->d_img); }
-    else { if (warm) BSN_PROD(true, false, 0, 1, false, b->d_img); else BSN_PROD(true, false, 0, 0, false, b->d_img); }
-  } else {
-    if (has_q) BSN_PROD(false, true, 0, 0, false, b->d_img);
-    else BSN_PROD(false, false, 0, 0, false, b->d_img);
-  }
+  // with / without the second plane, each with its warm-start name, on the raw codes; the same through a look-up
+#define BSN_PROD6(NBV, CV, TILEDV)                                                                \
+  BSN_PROD(NBV, CV, true, true, 0, TILEDV) BSN_PROD(NBV, CV, true, true, 1, TILEDV)               \
+  BSN_PROD(NBV, CV, true, false, 0, TILEDV) BSN_PROD(NBV, CV, true, false, 1, TILEDV)             \
+  BSN_PROD(NBV, CV, false, true, 0, TILEDV) BSN_PROD(NBV, CV, false, false, 0, TILEDV)
+  BSN_PROD6(1, true, false) BSN_PROD6(1, true, true) BSN_PROD6(1, false, false)
+  BSN_PROD6(2, true, false) BSN_PROD6(2, true, true) BSN_PROD6(2, false, false)
+#undef BSN_PROD6
 #undef BSN_PROD
+  fail("internal: no product kernel with %d column blocks", NB);
+}
+
+// One launch of k_prodT on the sample-major copy: the instance that choose_prodT (prod_plan.hpp) names.
+// (workgroup shapes 4 x 8 / 4 x 4 / 2 x 8 / 4 x 16 tiles x waves, chunks of 256 variants: all slower, profiles/r04_sample_major.txt)
+static void launch_prodT(bsn_op *op, const ProdTKernel &k, dim3 grid, int nchunks, int cps, const int8_t *q, int32_t *acc,
+                         int64_t npad, uint32_t lutQ, int seg_bs, int seg_stride, int seg_off) {
+  bsn_bed *b = op->bed;
+#define BSN_PRODT(NBV, HASQV, TAGV, SGBV, NASKIPV, SPARSEV)                                                           \
+  if (k == ProdTKernel{NBV, HASQV, TAGV, SGBV, NASKIPV, SPARSEV}) {                                                   \
+    BSN_KLAUNCH((k_prodT<NBV, HASQV, 2, 16, TAGV, SGBV, NASKIPV, SPARSEV>), grid, dim3(1024), 0, b->stream, b->d_smaj, \
+                b->rows_smaj, op->col0 / 512, nchunks, cps, q, acc, npad, lutQ, seg_bs, seg_stride, seg_off);         \
+    BSN_HIP(hipGetLastError());                                                                                       \
+    return;                                                                                                           \
+  }
+  BSN_PRODT(2, true, 0, 3, false, false) BSN_PRODT(2, true, 1, 3, false, false)
+  BSN_PRODT(2, false, 0, 3, false, false) BSN_PRODT(2, false, 1, 3, false, false)
+  BSN_PRODT(3, true, 0, 3, false, false) BSN_PRODT(3, false, 0, 3, false, false)
+  BSN_PRODT(2, true, 0, 0, true, false) BSN_PRODT(3, true, 0, 0, true, false)
+  BSN_PRODT(3, true, 0, 3, false, true) BSN_PRODT(3, true, 1, 3, false, true)
+#undef BSN_PRODT
+  fail("internal: no sample-major product kernel with %d column blocks", k.NB);
+}
+
+// y = finalize of a product launch of NB column blocks over `rows` output rows (blk_rows > 0: a segment's blocked output)
+static void launch_prod_final(bsn_bed *b, int NB, const int32_t *acc, int64_t npad, int ky, int S, int nv, const VecMeta *meta,
+                              const int32_t *d_rows, int64_t rows, double *Y, int64_t ldy, int sub_const, double beta,
+                              int64_t blk_rows) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, b->stream, acc, npad, ky, S, nv, meta, d_rows,
+                       rows, Y, ldy, sub_const, beta, blk_rows);
+  };
+  if (NB == 1) go(k_prod_final<16>);
+  else if (NB == 2) go(k_prod_final<32>);
+  else go(k_prod_final<48>);
   BSN_HIP(hipGetLastError());
+}
+
+// compute units of the device (k_prodT's slab rule fills whole rounds of them)
+static int device_cus() {
+  static const int ncu = [] {
+    hipDeviceProp_t pr;
+    int dev = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+               ? pr.multiProcessorCount : 256;
+  }();
+  return ncu;
 }
 
 // Y (+)= sum_j P[code_ij] W1[j, v] + sum_j lutQ[code_ij] W2[j, v]  (- sum_j W2[j, v] if sub_const)
@@ -1946,163 +1807,45 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
   if (nvec <= 0) return;
   op->preq_X = nullptr;
   op_na_blocks(op, nvec * S);
-  // k_prod addresses a 64-variant step with 32-bit offsets from its first row
-  if (b->pitch >= ((int64_t)1 << 24)) fail("more than 6.7e7 samples are not supported by the product kernel");
-  const int64_t npad = n_padded(b);
-  // Two or three column blocks over a contiguous range of variants that starts on a 512-variant chunk, and the handle
-  // has its sample-major copy: the product runs as k_prodT (k_cprod's shape, contraction over the contiguous index).
   if (b->smaj_job) (void)image_smaj_poll(b);   // a copy being made beside this solve: has it arrived?
-  const bool smaj_ok = b->bits == 2 && b->d_smaj != nullptr && op->cols_contig && (op->col0 & 511) == 0 && mode == 1 &&
-                       lutP == kLutRaw && lutQ == kLutNA && !getenv("BSN_NO_SMAJ");
-  const int vmax_smaj = std::min(kMetaVecs, (smaj_ok && nb3_allowed() && nvec * S > 32 ? kMaxCols : 32) / S);
-  const bool smaj = smaj_ok && nvec <= vmax_smaj && pick_nb(nvec * S) >= 2;   // (ONE launch: the geometry below is k_prodT's)
-  // (a panel that needs several launches stays on k_prod, which has two column blocks at most: 16 vectors x 56 bits with
-  // the copy in place used to cut itself into launches of three — "three column blocks without the sample-major copy")
-  const int vmax = smaj ? vmax_smaj : std::max(1, std::min(kMetaVecs, 32 / S));
-  if (sg && !smaj) return;   // (nothing queued: the caller takes the plain pass)
-  const int64_t m_pad = round_up(op->m, smaj ? 512 : 64);
-  VecMeta *meta = meta_buffer(op);
-  // K split so that the grid has a few thousand workgroups
-  int64_t wgx = b->bits == 8 ? npad / 256 : npad / 1024;  // workgroups along the samples
-  int ky = (int)((4096 + wgx - 1) / wgx);
-  int64_t steps = m_pad / 64;
-  int smaj_cps = 0;   // k_prodT: chunks of 512 variants per slab
-  if (smaj) {
-    // one 1024-thread workgroup per CU is resident: among 6 .. 24 slabs the split whose grid fills whole rounds of
-    // the chip best (782 x 17 workgroups = 51.9 rounds of 256 at 400 000 samples); a slab stays below 2.5e6 variants
-    static const int ncu = [] {
-      hipDeviceProp_t pr;
-      int dev = 0;
-      return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-                 ? pr.multiProcessorCount : 256;
-    }();
-    wgx = (b->n + 511) / 512;
-    const int64_t nchunks = m_pad / 512;
-    // ... less what the slabs cost: every slab writes its own n x 16 NB int32 partial sums and the finalize kernel reads them
-    // back — 0.15 % of the image's bytes per slab at 400K x 1M, 1.2 % on the 125 000-variant shard of an 8-GPU run, where
-    // 18 slabs (the best fill) measured 3.93 ms per pass against 3.80 - 3.82 with 8 - 10 (round 6, profiles/r06_shard_slabs.txt:
-    // the traffic weighs about 0.3 of its bytes — the writes drain beside the stream); the full-size choice (17) is unchanged
-    const double slab_cost = 0.3 * 2.0 * (double)npad * 16.0 * pick_nb((nvec < vmax ? nvec : vmax) * S) * 4.0 /
-                             ((double)m_pad * (double)(b->pitch));
-    int best = 1;
-    double best_score = -1e300;
-    for (int c = 1; c <= 24 && c <= nchunks; c++) {
-      if (c < 6 && c < nchunks && nchunks >= 6) continue;
-      const int64_t W = wgx * c;
-      const double fill = (double)W / ((double)ncu * (double)((W + ncu - 1) / ncu));
-      const double score = fill - slab_cost * c;
-      if (score > best_score + 1e-9) best_score = score, best = c;
-    }
-    ky = best;
-#ifdef BSN_ABLATION
-    if (const char *e = getenv("BSN_KY_T")) ky = std::max(1, std::min(atoi(e), (int)nchunks));  // slab sweep of k_prodT (correct results)
-#endif
-    const int64_t ky_min2 = (m_pad + 2499999) / 2500000;
-    if (ky < ky_min2) ky = (int)ky_min2;
-    smaj_cps = (int)((nchunks + ky - 1) / ky);
-    ky = (int)((nchunks + smaj_cps - 1) / smaj_cps);
-  }
-  if (!smaj) {   // (k_prodT's slab count and chunks per slab were fixed together above: clamping one would drop chunks)
-    if (ky > steps) ky = (int)steps;
-    if (ky > 64) ky = 64;
-  }
-  if (ky < 1) ky = 1;
-  if (smaj && (int64_t)ky * smaj_cps < m_pad / 512) fail("internal: the slabs of k_prodT do not cover the variants");
-  if (b->bits == 2 && pick_nb((nvec < vmax ? nvec : vmax) * S) == 1) {
-    // (one column block: the kernel is bound by HBM; with two it is bound by instruction issue, more slabs only help
-    // there — 400 000 x 125 000, 16 vectors: 4 slabs 3.45 ms, 5: 3.19, 9: 3.13, 11: 3.12 — and the rule above stays)
-    // ... but every slab writes (and the finalize kernel reads back) its own n x 16 NB accumulators: on a matrix with
-    // few samples per variant that is real traffic (50 000 x 200 000: 64 slabs = 16 % of the image), so the split is
-    // capped at 4 % of the image bytes; and two workgroups per CU are resident, so among the splits left the one
-    // whose grid fills whole rounds of 512 best wins (same matrix: 10 slabs = 490 workgroups, 0.72 - 0.75 ms per
-    // call against 0.80 - 0.84 with 64 and 0.86 with 11 = 539; profiles/r03_c2_grid_sweep.txt)
-    const int ncol_max = 16 * pick_nb((nvec < vmax ? nvec : vmax) * S);
-    int64_t cap = (int64_t)(0.04 * (double)m_pad / (32.0 * ncol_max));
-    if (cap < 1) cap = 1;
-    if (ky > cap) ky = (int)cap;
-    int best = ky;
-    double best_fill = 0.0;
-    for (int c = ky; c >= 1 && 2 * c >= ky; c--) {
-      const int64_t W = wgx * c;
-      const double fill = (double)W / (512.0 * (double)((W + 511) / 512));
-      if (fill > best_fill + 1e-9) best_fill = fill, best = c;
-    }
-    ky = best;
-  }
-#ifdef BSN_ABLATION
-  if (!smaj) {
-    if (const char *e = getenv("BSN_KY")) ky = atoi(e);  // grid-shape sweep (correct results)
-    if (ky > steps) ky = (int)steps;
-    if (ky < 1) ky = 1;
-  }
-#endif
-  // int32 accumulators: a slab adds at most 768 per variant (planes up to 4, digits up to 128); on a byte image
-  // 127 * 128 (grid indices up to 127), which leaves 132 104 variants per slab (byte_plan.hpp)
-  const int64_t ky_min = b->bits == 8 ? byte_min_slabs(m_pad) : (m_pad + 2499999) / 2500000;
-  if (ky < ky_min && !smaj) ky = (int)ky_min;
-  const int64_t mc = slab_variants(steps, ky);
-  if (!smaj) ky = (int)((m_pad + mc - 1) / mc);
   // complete variants: the missing-value plane is all zero, skip its look-ups and MFMAs
   const bool has_q = lutQ != 0u && !(op->no_na && lutQ == kLutNA);
-  // k_prodT<3> with the missing-value plane runs in its sparse form (one matrix instruction for both planes,
-  // prodt_sparse.hpp: 27.8 against 29.5 ms per pass at 400K x 1M); with two column blocks the 18-instruction decode
-  // outweighs the two matrix instructions it saves per tile (23.3 against 22.4 ms, profiles/sparse_prod_ab.txt) and the
-  // dense kernel stays.  BSN_NO_SPARSE_PROD=1: the dense two-plane kernel (A/B switch, bit-identical; read on every call)
-  // Its per-slice sums differ from the dense kernel's by carries between the digit slices, and k_prod_final adds the
-  // slices in fp64: the same Y needs that sum exact — below 2^53 for the largest panel the scale admits (codes up to 3,
-  // integers below 2^(8S-1), m_pad variants).  True for every 24-bit panel; the 56-bit panels of a wide solve keep the dense kernel.
-  const bool sparse_ok = smaj && has_q && getenv("BSN_NO_SPARSE_PROD") == nullptr &&
-                         ldexp(3.0 * (double)m_pad, 8 * S - 1) < 9007199254740992.0;
+  // the geometry of the pass (prod_plan.hpp): k_prodT on the sample-major copy or k_prod, vectors per launch, slabs
+  ProdFacts f;
+  f.bits = b->bits, f.n = b->n, f.m = op->m, f.pitch = b->pitch, f.col0 = op->col0, f.cols_contig = op->cols_contig;
+  f.have_smaj = b->d_smaj != nullptr && !getenv("BSN_NO_SMAJ");
+  f.mode = mode, f.raw_na = lutP == kLutRaw && lutQ == kLutNA, f.has_q = has_q;
+  f.no_sparse = getenv("BSN_NO_SPARSE_PROD") != nullptr;   // (A/B switch, bit-identical; read on every call)
+  f.nvec = nvec, f.S = S, f.segmented = sg != nullptr;
+  if (f.have_smaj) f.ncu = device_cus();
+#ifdef BSN_ABLATION
+  if (const char *e = getenv("BSN_KY")) f.ky = std::max(1, atoi(e));      // slab sweeps (correct results)
+  if (const char *e = getenv("BSN_KY_T")) f.ky_t = std::max(1, atoi(e));
+#endif
+  const ProdPlan pl = plan_prod(f);
+  if (pl.refuse == ProdRefusal::pitch_limit) fail("more than 6.7e7 samples are not supported by the product kernel");
+  if (pl.refuse == ProdRefusal::nothing_queued) return;   // (the caller takes the plain pass)
+  const bool smaj = pl.smaj;
+  const int vmax = pl.vmax, ky = pl.ky, smaj_cps = pl.smaj_cps;
+  const int64_t npad = n_padded(b), m_pad = pl.m_pad, mc = pl.mc;
+  if (smaj && (int64_t)ky * smaj_cps < m_pad / 512) fail("internal: the slabs of k_prodT do not cover the variants");
+  VecMeta *meta = meta_buffer(op);
+  const bool warm = op->prof_kind_override == 3;   // warm-start launches run under their own kernel name (TAG = 1)
   for (int v0 = 0; v0 < nvec; v0 += vmax) {
     int nv = nvec - v0 < vmax ? nvec - v0 : vmax;
     int NB = pick_nb(nv * S), ncol = 16 * NB;
-    // (where the host rule takes the kernels that skip the plane of K-steps without a missing code, they stay: nearly
-    // complete data, 1e-4 missing, 186.5 ms per solve on them against 198.7 on the sparse form)
-    const bool sparse = sparse_ok && NB == 3 && !op->na_skip_p;
+    const ProdTKernel kt = choose_prodT(NB, has_q, warm, op->na_skip_p, pl.sparse_ok);   // (read where smaj && NB >= 2)
     int8_t *q = op->d_q.ensure((size_t)(npad > m_pad ? npad : m_pad) * kMaxCols * 2);
     size_t acc_need = (size_t)ky * npad * ncol;
     if (acc_need < (size_t)2 * op->m * kMaxCols) acc_need = (size_t)2 * op->m * kMaxCols;
     int32_t *acc = op->d_acc.ensure(acc_need);
     // (k_prodT decodes like k_cprod: its digit rows take the crossproduct's byte order; the sparse form its own)
-    quantise(op, d_X + (int64_t)v0 * ldx, ldx, op->m, m_pad, nv, mode, S, ncol, smaj && NB >= 2 ? (sparse ? 2 : 1) : 0, 0, meta, q,
+    quantise(op, d_X + (int64_t)v0 * ldx, ldx, op->m, m_pad, nv, mode, S, ncol, smaj && NB >= 2 ? (kt.sparse ? 2 : 1) : 0, 0, meta, q,
              d_W2 ? d_W2 + (int64_t)v0 * ldx : nullptr);
-    dim3 grid((unsigned)wgx, (unsigned)ky);
+    dim3 grid((unsigned)pl.wgx, (unsigned)ky);
     prof_begin(op, NB == 3 ? 5 : 1);
     if (smaj && NB >= 2) {
       const int nchunks = (int)(m_pad / 512);
-      const bool warm = op->prof_kind_override == 3;
-#define BSN_PRODT_(NBV, HASQV, TAGV, GRID, BS, STRIDE, OFF)                                                          \
-  BSN_KLAUNCH((k_prodT<NBV, HASQV, 2, 16, TAGV>), GRID, dim3(1024), 0, b->stream, b->d_smaj, b->rows_smaj, op->col0 / 512, \
-              nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF)
-#ifdef BSN_ABLATION
-      static const int nb3p = getenv("BSN_NB3") ? atoi(getenv("BSN_NB3")) : 0;   // bit 2: k_prodT<3> without the explicit pipeline
-#define BSN_PRODT3(HASQV, GRID, BS, STRIDE, OFF)                                                                      \
-  do {                                                                                                               \
-    if (nb3p & 4)                                                                                                    \
-      BSN_KLAUNCH((k_prodT<3, HASQV, 2, 16, 0, 0>), GRID, dim3(1024), 0, b->stream, b->d_smaj, b->rows_smaj, op->col0 / 512, \
-                  nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF);                                           \
-    else BSN_PRODT_(3, HASQV, 0, GRID, BS, STRIDE, OFF);                                                             \
-  } while (0)
-#else
-#define BSN_PRODT3(HASQV, GRID, BS, STRIDE, OFF) BSN_PRODT_(3, HASQV, 0, GRID, BS, STRIDE, OFF)
-#endif
-#define BSN_PRODT_SKIP(NBV, GRID, BS, STRIDE, OFF)                                                                   \
-  BSN_KLAUNCH((k_prodT<NBV, true, 2, 16, 0, 0, true>), GRID, dim3(1024), 0, b->stream, b->d_smaj, b->rows_smaj,       \
-              op->col0 / 512, nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF)
-#define BSN_PRODT_SPARSE(TAGV, GRID, BS, STRIDE, OFF)                                                                \
-  BSN_KLAUNCH((k_prodT<3, true, 2, 16, TAGV, 3, false, true>), GRID, dim3(1024), 0, b->stream, b->d_smaj,  \
-              b->rows_smaj, op->col0 / 512, nchunks, smaj_cps, q, acc, npad, lutQ, BS, STRIDE, OFF)
-#define BSN_PRODT(HASQV, TAGV, GRID, BS, STRIDE, OFF)                                                                \
-  do {                                                                                                               \
-    if (HASQV && sparse) {   /* (three column blocks) */                                                             \
-      BSN_PRODT_SPARSE(TAGV, GRID, BS, STRIDE, OFF);                                                                 \
-    } else if (HASQV && op->na_skip_p) {   /* the missing-value plane only where a K-step has a missing code */      \
-      if (NB == 2) BSN_PRODT_SKIP(2, GRID, BS, STRIDE, OFF);                                                         \
-      else BSN_PRODT_SKIP(3, GRID, BS, STRIDE, OFF);                                                                 \
-    } else if (NB == 2) BSN_PRODT_(2, HASQV, TAGV, GRID, BS, STRIDE, OFF);                                           \
-    else BSN_PRODT3(HASQV, GRID, BS, STRIDE, OFF);                                                                   \
-  } while (0)
-      // (workgroup shapes 4 x 8 / 4 x 4 / 2 x 8 / 4 x 16 tiles x waves, chunks of 256 variants: all slower, profiles/r04_sample_major.txt)
       if (sg) {
         // the pass in segments of sample blocks: kernel + finalize of a segment, then the caller's hook (svd.hip queues the
         // segment's reduce-scatter on its second stream) while the next segment's kernel is queued behind on this one
@@ -2110,42 +1853,25 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
           const ProdSegment &sgm = sg->segs[sidx];
           const dim3 gs((unsigned)(sg->pieces * sgm.bs), (unsigned)ky);
           if (sidx > 0) prof_begin(op, NB == 3 ? 5 : 1, true);
-          if (has_q) BSN_PRODT(true, 0, gs, sgm.bs, sg->stride, sgm.off);
-          else BSN_PRODT(false, 0, gs, sgm.bs, sg->stride, sgm.off);
-          BSN_HIP(hipGetLastError());
+          launch_prodT(op, kt, gs, nchunks, smaj_cps, q, acc, npad, lutQ, sgm.bs, sg->stride, sgm.off);
           prof_end(op);
           const int64_t rows_s = (int64_t)sgm.bs * 512, tot = rows_s * sg->pieces;
-          if (NB == 2)
-            hipLaunchKernelGGL((k_prod_final<32>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, b->stream, acc, npad, ky,
-                               S, nv, meta, sgm.d_rows, tot, sgm.d_out, (int64_t)0, sub_const, 0.0, rows_s);
-          else
-            hipLaunchKernelGGL((k_prod_final<48>), dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, b->stream, acc, npad, ky,
-                               S, nv, meta, sgm.d_rows, tot, sgm.d_out, (int64_t)0, sub_const, 0.0, rows_s);
-          BSN_HIP(hipGetLastError());
+          launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, sgm.d_rows, tot, sgm.d_out, 0, sub_const, 0.0, rows_s);
           (*sg->after)(sidx);
         }
         op->passes++;
         sg->done = true;
         continue;
       }
-      if (has_q) { if (warm) BSN_PRODT(true, 1, grid, 0, 0, 0); else BSN_PRODT(true, 0, grid, 0, 0, 0); }
-      else { if (warm) BSN_PRODT(false, 1, grid, 0, 0, 0); else BSN_PRODT(false, 0, grid, 0, 0, 0); }
-#undef BSN_PRODT
-#undef BSN_PRODT_SPARSE
-#undef BSN_PRODT_SKIP
-#undef BSN_PRODT3
-#undef BSN_PRODT_
-      BSN_HIP(hipGetLastError());
+      launch_prodT(op, kt, grid, nchunks, smaj_cps, q, acc, npad, lutQ, 0, 0, 0);
     } else if (NB > 2) {
       fail("internal: three column blocks without the sample-major copy");
     } else if (b->bits == 8) {
       if (mode != 1) fail("internal: plane products are not defined on a byte image");
-      const dim3 grid8 = grid;
-      const int64_t npad8 = npad;
       const int32_t *cols8 = op->d_cols.p;
 #define BSN_PROD8(NBV, NAV, CV)                                                                          \
-  BSN_KLAUNCH((k_prod8<NBV, NAV, CV>), grid8, dim3(256), 0, b->stream, b->d_img, b->pitch, cols8, \
-                     op->col0, m_pad, mc, q, acc, npad8)
+  BSN_KLAUNCH((k_prod8<NBV, NAV, CV>), grid, dim3(256), 0, b->stream, b->d_img, b->pitch, cols8, \
+                     op->col0, m_pad, mc, q, acc, npad)
       if (NB == 1) {
         if (op->no_na) { if (op->cols_contig) BSN_PROD8(1, false, true); else BSN_PROD8(1, false, false); }
         else { if (op->cols_contig) BSN_PROD8(1, true, true); else BSN_PROD8(1, true, false); }
@@ -2155,30 +1881,14 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
       }
 #undef BSN_PROD8
       BSN_HIP(hipGetLastError());
-    } else
-    if (op->cols_contig) {
-      if (NB == 1) launch_prod<1, true>(op, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
-      else launch_prod<2, true>(op, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
     } else {
-      if (NB == 1) launch_prod<1, false>(op, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
-      else launch_prod<2, false>(op, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
+      launch_prod(op, NB, grid, m_pad, mc, q, acc, npad, lutP, lutQ, has_q);
     }
     prof_end(op);
     op->last_kernel = g_last_kernel;
     op->passes++;
-    if (NB == 1)
-      hipLaunchKernelGGL((k_prod_final<16>), dim3((unsigned)((op->n + 255) / 256)), dim3(256), 0, b->stream,
-                         acc, npad, ky, S, nv, meta, op->rows_identity ? nullptr : op->d_rows.p, op->n,
-                         d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta);
-    else if (NB == 2)
-      hipLaunchKernelGGL((k_prod_final<32>), dim3((unsigned)((op->n + 255) / 256)), dim3(256), 0, b->stream,
-                         acc, npad, ky, S, nv, meta, op->rows_identity ? nullptr : op->d_rows.p, op->n,
-                         d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta);
-    else
-      hipLaunchKernelGGL((k_prod_final<48>), dim3((unsigned)((op->n + 255) / 256)), dim3(256), 0, b->stream,
-                         acc, npad, ky, S, nv, meta, op->rows_identity ? nullptr : op->d_rows.p, op->n,
-                         d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta);
-    BSN_HIP(hipGetLastError());
+    launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, op->rows_identity ? nullptr : op->d_rows.p, op->n,
+                      d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta, 0);
   }
 }
 

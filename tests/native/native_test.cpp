@@ -2,7 +2,8 @@
 // (bigsnpr_amd/csrc/svd_driver.hpp, dense_small.hpp) on CPU with a dense host backend so
 // that the driver logic — including the column-sharded multi-rank path with an all-reduce
 // hook — can be tested without a GPU (gloo, world_size 2).  Not part of the product.
-// Also the kernel choice of the windowed-LD band (ld_plan.hpp), which is plain C++ for the same reason.
+// Also the kernel choice of the windowed-LD band (ld_plan.hpp) and the launch geometry and kernel choice of the streaming
+// products (prod_plan.hpp), which are plain C++ for the same reason.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "ld_plan.hpp"
 #include "orth_small.hpp"
+#include "prod_plan.hpp"
 #include "svd_driver.hpp"
 
 using namespace bsn;
@@ -382,4 +384,38 @@ void nt_byte_limits(int64_t *out) { out[0] = kSliceBytes, out[1] = kByteMaxSlice
 // the slabs of prod_planes on a byte image: the fewest it may launch, and the variants per slab when it launches ky
 int64_t nt_byte_min_slabs(int64_t m_pad) { return byte_min_slabs(m_pad); }
 int64_t nt_slab_variants(int64_t steps, int64_t ky) { return slab_variants(steps, ky); }
+
+// ---- prod_plan.hpp (tests/test_prod_plan_cpu.py) ----
+// facts: bits, n, m, pitch, col0, cols_contig, have_smaj, mode, raw_na, has_q, no_sparse, nvec, S, ncu, segmented, ky, ky_t
+// out: refuse (0 none, 1 pitch limit, 2 nothing queued), smaj, vmax, m_pad, wgx, ky, smaj_cps, mc, sparse_ok
+void nt_prod_plan(const int64_t *f, int64_t *out) {
+  ProdFacts p;
+  p.bits = (int)f[0], p.n = f[1], p.m = f[2], p.pitch = f[3], p.col0 = f[4], p.cols_contig = f[5] != 0, p.have_smaj = f[6] != 0;
+  p.mode = (int)f[7], p.raw_na = f[8] != 0, p.has_q = f[9] != 0, p.no_sparse = f[10] != 0, p.nvec = (int)f[11], p.S = (int)f[12];
+  p.ncu = (int)f[13], p.segmented = f[14] != 0, p.ky = (int)f[15], p.ky_t = (int)f[16];
+  const ProdPlan r = plan_prod(p);
+  out[0] = (int64_t)r.refuse, out[1] = r.smaj, out[2] = r.vmax, out[3] = r.m_pad, out[4] = r.wgx, out[5] = r.ky, out[6] = r.smaj_cps;
+  out[7] = r.mc, out[8] = r.sparse_ok;
+}
+int nt_pick_nb(int ncols) { return pick_nb(ncols); }
+int nt_cprod_vmax(int bits, int stats_pending, int S) { return cprod_vmax(bits, stats_pending != 0, S); }
+// out: kMaxCols, kMetaVecs
+void nt_prod_limits(int32_t *out) { out[0] = kMaxCols, out[1] = kMetaVecs; }
+// facts: NB, plain, stats, cols_contig, tiled, warm, na_skip;  out: NB, contig, tiles, waves, tag, tiled, sgb, naskip
+void nt_choose_cprod(const int32_t *f, int32_t *out) {
+  CprodFacts c;
+  c.NB = f[0], c.plain = f[1] != 0, c.stats = f[2] != 0, c.cols_contig = f[3] != 0, c.tiled = f[4] != 0, c.warm = f[5] != 0, c.na_skip = f[6] != 0;
+  const CprodKernel k = choose_cprod(c);
+  out[0] = k.NB, out[1] = k.contig, out[2] = k.tiles, out[3] = k.waves, out[4] = k.tag, out[5] = k.tiled, out[6] = k.sgb, out[7] = k.naskip;
+}
+// out: NB, contig, rawp, hasq, tag, tiled
+void nt_choose_prod(int NB, int contig, int tiled, int rawp, int has_q, int warm, int32_t *out) {
+  const ProdKernel k = choose_prod(NB, contig != 0, tiled != 0, rawp != 0, has_q != 0, warm != 0);
+  out[0] = k.NB, out[1] = k.contig, out[2] = k.rawp, out[3] = k.hasq, out[4] = k.tag, out[5] = k.tiled;
+}
+// out: NB, hasq, tag, sgb, naskip, sparse
+void nt_choose_prodT(int NB, int has_q, int warm, int na_skip, int sparse_ok, int32_t *out) {
+  const ProdTKernel k = choose_prodT(NB, has_q != 0, warm != 0, na_skip != 0, sparse_ok != 0);
+  out[0] = k.NB, out[1] = k.hasq, out[2] = k.tag, out[3] = k.sgb, out[4] = k.naskip, out[5] = k.sparse;
+}
 }
