@@ -67,6 +67,7 @@ SIGNATURES = {
     "bsn_comm_destroy": (C.c_int, [vp]),
     "bsn_ld_last_stats": (C.c_int, [f64p]),
     "bsn_robust_scale_tau2": (C.c_int, [vp, i64, i64, C.c_int32, C.c_double, C.c_double, f64p, f64p]),
+    "bsn_robust_medians": (C.c_int, [vp, i64, i64, C.c_int32, f64p, f64p]),
     "bsn_robust_pair_scales": (C.c_int, [vp, i64, i64, C.c_int32, C.c_double, C.c_double, f64p, f64p]),
     "bsn_robust_mc_count": (C.c_int, [vp, i64, vp, i64, C.c_double, C.POINTER(C.c_int64)]),
     "bsn_robust_scale_cols": (C.c_int, [vp, i64, i64, C.c_int32, f64p]),

@@ -585,6 +585,21 @@ int bsn_robust_scale_tau2(const double *d_X, int64_t m, int64_t ld, int32_t ncol
   });
 }
 
+int bsn_robust_medians(const double *d_X, int64_t m, int64_t ld, int32_t ncol, const double *centre, double *med_out) {
+  return guarded([&] {
+    require_gpu();
+    if (m < 1 || ncol < 0 || ld < m) fail("bsn_robust_medians: dimensions");
+    if (ncol == 0) return;
+    if (!med_out) fail("bsn_robust_medians: no output vector");
+    Scratch w;
+    DevBuf<double> d_centre;
+    w.med.ensure((size_t)ncol);
+    if (centre) BSN_HIP(hipMemcpy(d_centre.ensure((size_t)ncol), centre, (size_t)ncol * 8, hipMemcpyHostToDevice));
+    select_medians(w, d_X, m, ld, ncol, centre ? d_centre.p : nullptr, w.med.p, nullptr);
+    BSN_HIP(hipMemcpy(med_out, w.med.p, (size_t)ncol * 8, hipMemcpyDeviceToHost));
+  });
+}
+
 int bsn_robust_pair_scales(const double *d_Z, int64_t m, int64_t ld, int32_t p, double c1, double c2, double *s_sum_out, double *s_diff_out) {
   return guarded([&] {
     require_gpu();

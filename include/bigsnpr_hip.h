@@ -495,6 +495,9 @@ int bsn_clumping_chr_cached(bsn_bed *bed, const int64_t *ind_row, int64_t n, con
  * an R shim would keep bigutilsr's own).  Small host vectors in and out. */
 /* robustbase::scaleTau2(x, c1, c2, mu.too = TRUE, consistency = TRUE) of every column: mu_out / s_out [ncol] (either may be NULL) */
 int bsn_robust_scale_tau2(const double *d_X, int64_t m, int64_t ld, int32_t ncol, double c1, double c2, double *mu_out, double *s_out);
+/* the medians those scales start from, on their own: median of every column (centre NULL) or of |x - centre[c]| (the MAD
+ * step), both middle order statistics averaged for an even m.  centre: host [ncol] or NULL; med_out: host [ncol] */
+int bsn_robust_medians(const double *d_X, int64_t m, int64_t ld, int32_t ncol, const double *centre, double *med_out);
 /* the same scale of Z_i + Z_j and Z_i - Z_j for every pair i > j of the p <= 64 columns, pairs in the order
  * (1,0), (2,0), (2,1), (3,0) ...: s_sum_out / s_diff_out [p (p - 1) / 2] */
 int bsn_robust_pair_scales(const double *d_Z, int64_t m, int64_t ld, int32_t p, double c1, double c2, double *s_sum_out, double *s_diff_out);
