@@ -22,6 +22,7 @@ from .gwas import big_univLinReg, big_univLogReg  # noqa: F401,E402
 from .impute import snp_fastImputeSimple  # noqa: F401,E402
 from .sct import seq_log, snp_grid_clumping, snp_grid_PRS  # noqa: F401,E402
 from .lassosum2 import SFBM, as_SFBM, snp_lassosum2  # noqa: F401,E402
+from .ldsplit import snp_ldsplit  # noqa: F401,E402
 from .ldpred2 import (coef_to_liab, ld_scores_sfbm, snp_ldpred2_auto, snp_ldpred2_grid, snp_ldpred2_inf,  # noqa: F401,E402
                       snp_ldsc, snp_ldsc2, sp_colSumsSq_sym, sp_cprodVec, sp_prodVec, sp_solve_sym)
 

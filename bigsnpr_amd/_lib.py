@@ -153,6 +153,8 @@ SIGNATURES = {
     "bsn_sfbm_ld_scores": (C.c_int, [vp, i64p, i64, f64p]),
     "bsn_sfbm_solve_sym": (C.c_int, [vp, f64p, f64p, i64p, i64, C.c_double, C.c_int32, f64p, i32p, f64p]),
     "bsn_sfbm_last_ms": (C.c_int, [vp, f64p]),
+    "bsn_sfbm_ldsplit": (C.c_int, [vp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, f64p, f64p, i32p,
+                                   f64p, f64p, f64p, i32p, i32p, i32p, f64p]),
     "bsn_malloc": (C.c_int, [C.POINTER(vp), i64]),
     "bsn_free": (C.c_int, [vp]),
     "bsn_host_alloc": (C.c_int, [C.POINTER(vp), i64]),

@@ -349,6 +349,17 @@ struct bsn_bed {
   unsigned stage_next = 0;
 };
 
+// a sparse LD matrix resident in HBM (sparse_ld.hip builds it, ldsplit.hip reads it)
+struct bsn_sfbm {
+  int64_t m2 = 0, nnz = 0;
+  bsn::DevBuf<int64_t> p;   // [m2 + 1] full columns
+  bsn::DevBuf<int32_t> i;   // [nnz] ascending in each column
+  bsn::DevBuf<double> x;    // [nnz]
+  std::vector<int32_t> lo, hi;   // row span of each column (lo > hi: empty column)
+  int64_t bandwidth = 0;         // max over columns of max(j - lo, hi - j)
+  std::vector<int64_t> hp;       // p on the host: the column lengths choose the kernel of each column (plan_columns)
+  double last_ms = 0;            // device time of the last product / LD-score / solve call (bsn_sfbm_last_ms)
+};
 
 namespace bsn {
 

@@ -35,6 +35,9 @@ class SFBM:
         check(L.bsn_sfbm_ncol(h, *[C.byref(v) for v in info]))
         self.ncol, self.nnz, self.bandwidth = (v.value for v in info)
         self.shape = (self.ncol, self.ncol)
+        # crossprod(tril(corr)@x): what snp_ldsplit clamps max_cost with, taken while the entries are on the host
+        from .ldsplit import lower_sumsq
+        self.sumsq_lower = lower_sumsq(p, i, x, m2, upper)
 
     def close(self):
         self._fin()

@@ -612,6 +612,24 @@ int bsn_sfbm_solve_sym(bsn_sfbm *s, const double *b, const double *add_to_diag, 
 /* device milliseconds (HIP events, host copies excluded) of the last of the three calls above on this handle */
 int bsn_sfbm_last_ms(const bsn_sfbm *s, double *ms_out);
 
+/* ---- snp_ldsplit (R/split-LD.R, src/split-LD.cpp): optimal LD block splitting over the resident matrix -------------------
+ * Works on the lower triangle of `corr`, whose every column must store a non-zero diagonal.  thr_r2: squared correlations
+ * below it are ignored; max_r2: no pair above it may be split; block sizes min_size .. max_size; K = 1 .. max_K blocks;
+ * max_cost (may be +Inf) as get_C takes it, the caller clamps; pos_scaled [m] ascending (NULL: all 0).
+ * Outputs, any may be NULL: C_out [m * max_K] column-major, the reference's C (+Inf where no split exists);
+ * best_ind_out [m * max_K], the reference's best_ind: the 0-based first row of the next block, -1 for NA;
+ * cost_out [max_K] = C(0, K - 1); n_block_ok_out [max_K]: 1 where K blocks were reconstructed (cost <= max_cost and a
+ * path exists); cost2_out [max_K] the sum of squared block sizes (+Inf where not reconstructed); perc_kept_out [max_K]
+ * get_perc (-1 where not reconstructed); all_last_out [max_K * max_K], K entries from (K - 1) * max_K on: best_ind along
+ * the path, the rest -1; levels_run_out: the levels computed before the reference's early stop; seconds_out [3]: device
+ * seconds of E (with the suffix sums), of the levels and of the epilogue.  Every result equals the reference's sequential
+ * loops bit for bit.  min_size < 1, max_size < min_size, max_size > m, max_K < 1, a pos_scaled that is not ascending and
+ * a column without a non-zero diagonal are refused by name, and the tables must fit the free device memory. */
+int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t min_size, int32_t max_size, int32_t max_K,
+                     double max_cost, const double *pos_scaled, double *C_out, int32_t *best_ind_out, double *cost_out,
+                     double *cost2_out, double *perc_kept_out, int32_t *n_block_ok_out, int32_t *all_last_out,
+                     int32_t *levels_run_out, double *seconds_out);
+
 /* ---- device memory + timing helpers for hosts without a HIP binding -------- */
 int bsn_malloc(void **d_ptr, int64_t bytes);
 int bsn_free(void *d_ptr);
