@@ -20,7 +20,8 @@ from .plink_io import bed_to_bytes, snp_readBed, snp_writeBed  # noqa: F401,E402
 from .pcadapt import bed_pcadapt, multLinReg, snp_pcadapt  # noqa: F401,E402
 from .gwas import big_univLinReg, big_univLogReg  # noqa: F401,E402
 from .impute import snp_fastImputeSimple  # noqa: F401,E402
-from .sct import seq_log, snp_grid_clumping, snp_grid_PRS  # noqa: F401,E402
+from .sct import seq_log, snp_grid_clumping, snp_grid_PRS, snp_grid_stacking  # noqa: F401,E402
+from .plr import BigSpReg, big_spLinReg, big_spLogReg  # noqa: F401,E402
 from .lassosum2 import SFBM, as_SFBM, snp_lassosum2  # noqa: F401,E402
 from .ldsplit import snp_ldsplit  # noqa: F401,E402
 from .ldpred2 import (coef_to_liab, ld_scores_sfbm, snp_ldpred2_auto, snp_ldpred2_grid, snp_ldpred2_inf,  # noqa: F401,E402

@@ -50,6 +50,14 @@ class SvdInfo(C.Structure):
                 ("early_ritz", C.c_int32 * 2)]
 
 
+class PlrOptions(C.Structure):
+    _fields_ = [("family", C.c_int32), ("nlambda", C.c_int32), ("nlam_min", C.c_int32), ("n_abort", C.c_int32),
+                ("dfmax", C.c_int32), ("max_iter", C.c_int32), ("eps", C.c_double), ("lambda_min_ratio", C.c_double)]
+
+
+_PLR_TAIL = [f64p, f64p, i64, f64p, i32p, C.c_int32, f64p, C.c_int32, C.POINTER(PlrOptions), f64p, f64p, f64p, f64p, f64p,
+             i32p, i32p, i32p, i32p, i32p]
+
 # name -> (restype, argtypes); kept in one table so tests can check that every symbol
 # declared in include/bigsnpr_hip.h is exported and bound.
 SIGNATURES = {
@@ -108,6 +116,9 @@ SIGNATURES = {
     "bsn_mult_lin_reg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
     "bsn_univ_linreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p, f64p]),
     "bsn_univ_logreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, C.c_double, C.c_int32, f64p, f64p, i32p]),
+    "bsn_bed_sp_reg": (C.c_int, [vp, i64p, i64, i64p, i64] + _PLR_TAIL),
+    "bsn_dense_sp_reg": (C.c_int, [vp, C.c_int, i64, i64, i64] + _PLR_TAIL),
+    "bsn_plr_last_stats": (C.c_int, [f64p]),
     "bsn_impute_simple": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp), u8p, i64p]),
     "bsn_impute_last_ms": (C.c_int, [f64p]),
     "bsn_bed_to_fbm": (C.c_int, [vp, i64p, i64, i64p, i64, u8p]),

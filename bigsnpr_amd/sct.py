@@ -9,8 +9,8 @@ snp_grid_PRS: the reference runs one snp_PRS (R/PRS.R:36-76) per clumping set; h
 of a chromosome and all thresholds come out of one sweep over the union of the kept columns,
 as n x C int8-MFMA GEMMs per threshold bin (bsn_snp_grid_prs).
 
-snp_grid_stacking (R/SCT.R:278-319) is bigstatsr::big_spLogReg / big_spLinReg (external
-penalised regression, not under /root/reference/src) plus index arithmetic: out of scope.
+snp_grid_stacking (R/SCT.R:266-304): big_spLogReg / big_spLinReg (bigsnpr_amd/plr.py) on the score matrix, then
+the stacking weights mapped back onto the variants by index arithmetic on the host.
 Indices are 0-based."""
 import ctypes as C
 
@@ -171,3 +171,38 @@ def snp_grid_PRS(G, all_keep, betas, lpS, n_thr_lpS=50, grid_lpS_thr=None, ind_r
         scores[:, ic0 * T:(ic0 + Cn) * T] = unsorted.reshape(ir.size, Cn * T, order="F")
         ic0 += Cn
     return MultiPRS(scores, lpS, thr, betas, all_keep)
+
+
+def stacking_coef(beta_stacking, lpS, grid_lpS_thr, all_keep, n_var):
+    """R/SCT.R:287-296: the weight of every variant, summed over the clumping sets: within a set, the stacking weights of
+    all the thresholds that the variant's lpS exceeds"""
+    lpS_thr = np.asarray(grid_lpS_thr, dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        ind_last_thr = (np.asarray(lpS, dtype=np.float64)[:, None] > lpS_thr[None, :]).sum(axis=1)   # (0-based into b2)
+    coef = np.zeros(n_var)
+    T = lpS_thr.size
+    ind = 0
+    for sets in all_keep:
+        for ind_keep in sets:
+            ind_keep = np.asarray(ind_keep, dtype=np.int64)
+            b2 = np.r_[0.0, np.cumsum(beta_stacking[ind:ind + T])]
+            coef[ind_keep] = coef[ind_keep] + b2[ind_last_thr[ind_keep]]
+            ind += T
+    return coef
+
+
+def snp_grid_stacking(multi_PRS, y_train, alphas=(1, 0.01, 0.0001), ncores=1, **kw):
+    """R/SCT.R:266-304.  Returns dict(intercept, beta_G, beta_covar, mod); `mod` is the BigSpReg."""
+    import warnings
+    from .plr import big_spLinReg, big_spLogReg
+    fit = big_spLogReg if np.unique(np.asarray(y_train)).size == 2 else big_spLinReg
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                         # suppressWarnings(), R/SCT.R:275
+        mod = fit(multi_PRS, y_train, alphas=alphas, ncores=ncores, **kw)
+    best = mod.summary(best_only=True)[0]
+    ind_col = mod.ind_col
+    beta_stacking = np.zeros(multi_PRS.shape[1])
+    beta_stacking[ind_col] = best["beta"][:ind_col.size]
+    beta_gwas = np.asarray(multi_PRS.betas, dtype=np.float64)
+    coef = stacking_coef(beta_stacking, multi_PRS.lpS, multi_PRS.grid_lpS_thr, multi_PRS.all_keep, beta_gwas.size)
+    return dict(intercept=best["intercept"], beta_G=coef * beta_gwas, beta_covar=best["beta"][ind_col.size:], mod=mod)

@@ -164,6 +164,42 @@ int bsn_univ_logreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64
                     const double *covar, int64_t q, double tol, int32_t maxiter, double *estim, double *std_err,
                     int32_t *niter);
 
+/* bigstatsr::big_spLinReg / big_spLogReg: elastic-net paths on individual-level data with cross-model selection and
+ * averaging; the statement is DESIGN.md 3.5i (bigsnpr_amd/csrc/plr_step.hpp).  One chain per (alpha a, fold k),
+ * c = a K + k, all chains resident on the device for the whole call.  Rows are the n rows of the selection; row i is a
+ * validation row of chain (a, k) when fold[i] == k.  Columns are the m selected ones followed by the q covariates
+ * (covar: n x q column-major, may be NULL when q = 0); pf [m + q] are the penalty factors (0: unpenalised).
+ * Outputs, per chain c: intercept [C] and beta [(m + q) x C] of the chain's best model on the original scale;
+ * lambda / loss / loss_val / iter / nb_active [nlambda x C] (entry 0 is the unpenalised start; NaN / 0 past n_done);
+ * n_done [C] lambdas closed, best [C] the index of the best one, status [C]: 1 "No more improvement", 2 "Too many
+ * variables", 3 "Model saturated", 4 "Complete path".  A missing value among the selection is refused.
+ * bsn_bed_sp_reg: a resident 2-bit image or a byte image on a grid.  bsn_dense_sp_reg: a dense host matrix, column-major
+ * with leading dimension ld, type 4 (float) or 7 (double) as in bsn_snp_grid_prs. */
+typedef struct bsn_plr_options {
+  int32_t family;          /* 0 linear, 1 logistic (y in {0, 1}) */
+  int32_t nlambda;         /* length of the lambda grid, >= 2 */
+  int32_t nlam_min;        /* no early stop before this many lambdas */
+  int32_t n_abort;         /* lambdas without a better validation loss before "No more improvement" */
+  int32_t dfmax;           /* non-zero coefficients at which a chain stops with "Too many variables" */
+  int32_t max_iter;        /* coordinate passes per lambda */
+  double eps;              /* convergence threshold relative to the null loss */
+  double lambda_min_ratio; /* last lambda / first lambda */
+} bsn_plr_options;
+int bsn_bed_sp_reg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const double *y,
+                   const double *covar, int64_t q, const double *pf, const int32_t *fold, int32_t K, const double *alphas,
+                   int32_t n_alpha, const bsn_plr_options *opt, double *intercept, double *beta, double *lambda,
+                   double *loss, double *loss_val, int32_t *iter, int32_t *nb_active, int32_t *n_done, int32_t *best,
+                   int32_t *status);
+int bsn_dense_sp_reg(const void *X, int type, int64_t ld, int64_t n, int64_t m, const double *y, const double *covar,
+                     int64_t q, const double *pf, const int32_t *fold, int32_t K, const double *alphas, int32_t n_alpha,
+                     const bsn_plr_options *opt, double *intercept, double *beta, double *lambda, double *loss,
+                     double *loss_val, int32_t *iter, int32_t *nb_active, int32_t *n_done, int32_t *best, int32_t *status);
+/* the last bsn_*_sp_reg call of this process, device time from events: out[0] ms in sweeps, [1] ms in scans (scan, flag,
+ * commit), [2] turns of the host loop, [3] coordinate updates (passes x active columns over all chains), [4] ms before the
+ * first turn (statistics, start fit, lambda_max), [5] their sum.  One record per process, written without a lock (like
+ * bsn_impute_last_ms): not meaningful when two host threads run bsn_*_sp_reg at the same time. */
+int bsn_plr_last_stats(double *out /* 6 */);
+
 /* _bigsnpr_impute (3 args) src/impute-simple.cpp:10-73 + R/impute.R:189-203 — R: snp_fastImputeSimple.
  * `src` is any resident 2-bit handle and is not modified; *out receives a NEW handle (the reference rewrites the FBM's
  * file in place and returns it under another decode table).  method: 0 zero, 1 mode, 2 mean0, 3 mean2, 4 random — the
