@@ -147,7 +147,7 @@ struct Chain {
   }
 
   void run(double *intercept, double *beta_out, double *lambda, double *loss_o, double *lossv_o, int32_t *iter_o,
-           int32_t *nb_o, int32_t *n_done, int32_t *best, int32_t *status) {
+           int32_t *nb_o, int32_t *n_done, int32_t *best, int32_t *status, int32_t *turns) {
     p = m + q;
     mk.resize(n);
     nt = 0;
@@ -193,7 +193,7 @@ struct Chain {
     book_init(bk);
     std::vector<double> best_beta(p, 0.0);
     double best_b0 = b0;
-    int l = 0, st;
+    int l = 0, st, nturn = 0;
     for (;;) {
       bool improved;
       loss_o[l] = loss;
@@ -211,6 +211,7 @@ struct Chain {
       iter = 0;
       for (;;) {
         sweep(lambda[l], iter);
+        nturn++;
         epilogue(loss, loss_val);
         int added = 0;
         for (int64_t j = 0; j < p; j++)
@@ -224,6 +225,7 @@ struct Chain {
     *n_done = l + 1;
     *best = bk.best_l;
     *status = st;
+    if (turns) *turns = nturn;
     double b = best_b0;
     for (int64_t j = 0; j < p; j++) {
       beta_out[j] = best_beta[j] * isd[j];
@@ -240,11 +242,13 @@ extern "C" {
 // X: n x m column-major; covar: n x q column-major (NULL when q = 0); pf [m + q]; fold [n] in 0 .. K - 1; chain
 // c = a K + k.  opt_i: family (0 linear, 1 logistic), nlambda, nlam_min, n_abort, dfmax, max_iter; opt_d: eps,
 // lambda_min_ratio.  exact != 0: the columns of X hold values whose sums are exact integers (a decoded 2-bit image).
-// Outputs as bsn_bed_sp_reg's (include/bigsnpr_hip.h).
+// Outputs as bsn_bed_sp_reg's (include/bigsnpr_hip.h); turns [C] (may be NULL): the calls of sweep inside the lambda loop,
+// which is the number of turns of the device's host loop in which the chain is live.
 void plr_ref_fit(const double *X, int64_t n, int64_t m, const double *y, const double *covar, int q, const double *pf,
                  const int32_t *fold, int K, const double *alphas, int n_alpha, const int32_t *opt_i, const double *opt_d,
                  int exact, int reverse, int nthreads, double *intercept, double *beta, double *lambda, double *loss,
-                 double *loss_val, int32_t *iter, int32_t *nb_active, int32_t *n_done, int32_t *best, int32_t *status) {
+                 double *loss_val, int32_t *iter, int32_t *nb_active, int32_t *n_done, int32_t *best, int32_t *status,
+                 int32_t *turns) {
   const Opt o{opt_i[0], opt_i[1], opt_i[2], opt_i[3], opt_i[4], opt_i[5], opt_d[0], opt_d[1]};
   const int C = K * n_alpha;
   const int64_t p = m + q;
@@ -273,7 +277,7 @@ void plr_ref_fit(const double *X, int64_t n, int64_t m, const double *y, const d
     ch.rev = reverse != 0;
     const int64_t L = (int64_t)o.nlambda * c;
     ch.run(intercept + c, beta + p * c, lambda + L, loss + L, loss_val + L, iter + L, nb_active + L, n_done + c, best + c,
-           status + c);
+           status + c, turns ? turns + c : nullptr);
   }
 }
 

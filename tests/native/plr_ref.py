@@ -37,7 +37,7 @@ def load():
         lib = C.CDLL(build())
         lib.plr_ref_fit.restype = None
         lib.plr_ref_fit.argtypes = [f64p, C.c_int64, C.c_int64, f64p, f64p, C.c_int, f64p, i32p, C.c_int, f64p, C.c_int, i32p,
-                                    f64p, C.c_int, C.c_int, C.c_int] + [f64p] * 5 + [i32p] * 5
+                                    f64p, C.c_int, C.c_int, C.c_int] + [f64p] * 5 + [i32p] * 6
         _lib = lib
     return _lib
 
@@ -49,7 +49,8 @@ def _p(a, t=f64p):
 def fit(X, y, fold, K, alphas=(1.0,), covar=None, pf=None, family="linear", nlambda=200, lambda_min_ratio=None, nlam_min=50,
         n_abort=10, dfmax=50000, eps=1e-5, max_iter=1000, exact=True, reverse=False, nthreads=0):
     """dict of the raw outputs, chain c = a K + k in the last axis: intercept [C], beta [m + q, C], lambda / loss /
-    loss_val / iter / nb_active [nlambda, C], n_done, best, status [C]"""
+    loss_val / iter / nb_active [nlambda, C], n_done, best, status [C], turns [C] (the sweeps after l = 0: the turns of the
+    device's host loop in which the chain is live)"""
     X = np.asfortranarray(X, dtype=np.float64)
     X = X[:, None] if X.ndim == 1 else X
     n, m = X.shape
@@ -70,10 +71,11 @@ def fit(X, y, fold, K, alphas=(1.0,), covar=None, pf=None, family="linear", nlam
         out[k] = np.empty((nlambda, Cn), order="F")
     for k in ("iter", "nb_active"):
         out[k] = np.empty((nlambda, Cn), dtype=np.int32, order="F")
-    for k in ("n_done", "best", "status"):
+    for k in ("n_done", "best", "status", "turns"):
         out[k] = np.empty(Cn, dtype=np.int32)
     load().plr_ref_fit(_p(X), n, m, _p(y), _p(cov) if q else None, q, _p(pf), _p(fold, i32p), int(K), _p(alphas), alphas.size,
                        _p(oi, i32p), _p(od), int(bool(exact)), int(bool(reverse)), int(nthreads), _p(out["intercept"]),
                        _p(out["beta"]), _p(out["lambda"]), _p(out["loss"]), _p(out["loss_val"]), _p(out["iter"], i32p),
-                       _p(out["nb_active"], i32p), _p(out["n_done"], i32p), _p(out["best"], i32p), _p(out["status"], i32p))
+                       _p(out["nb_active"], i32p), _p(out["n_done"], i32p), _p(out["best"], i32p), _p(out["status"], i32p),
+                       _p(out["turns"], i32p))
     return out

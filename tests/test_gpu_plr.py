@@ -13,7 +13,6 @@ measured by tests/test_plr_cpu.py on the example data (517 x 1500, four folds, n
               "No more improvement" at l = 19, best l = 6, 5, 7, 6"""
 import os
 import sys
-import warnings
 
 import numpy as np
 import pytest
@@ -22,14 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
-import plr_ref as ref  # noqa: E402
 import plr_inputs as inp  # noqa: E402
 import dosage_inputs as dos  # noqa: E402
+from plr_check import _fit, _raw, _same  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 PATH = inp.PATH
-EPS64 = 2.2e-16
 
 
 @pytest.fixture(scope="module")
@@ -43,54 +41,6 @@ def ex(ba, orc, golden_dir, example_bed):
     d = dict(inp.example_case(orc, golden_dir, example_bed))
     d["gb"] = ba.bed(os.path.join(golden_dir, "example.bed"))
     return d
-
-
-def _raw(mod):
-    """a BigSpReg as the raw arrays of the statement, chain c = a K + k in the last axis"""
-    chains = [mo for mods in mod for mo in mods]
-    NL = max(mo["lambda"].size for mo in chains)
-    out = dict(intercept=np.array([mo["intercept"] for mo in chains]), beta=np.column_stack([mo["beta"] for mo in chains]),
-               n_done=np.array([mo["iter"].size for mo in chains]), best=np.array([mo["best"] for mo in chains]),
-               status=np.array([ref.MESSAGES.index(mo["message"]) for mo in chains]))
-    for k in ("loss", "loss_val", "iter", "nb_active"):
-        out[k] = [mo[k] for mo in chains]
-    return out
-
-
-def _same(mod, X, y, fold, K, where, **kw):
-    """the device's model against the statement; the tolerance is measured from the statement's two orders"""
-    f = ref.fit(X, y, fold, K, **kw)
-    r = ref.fit(X, y, fold, K, reverse=True, **kw)
-    got = _raw(mod)
-    for k in ("status", "n_done", "best"):
-        assert np.array_equal(f[k], r[k]), (where, k)
-        assert np.array_equal(got[k], f[k]), (where, k, got[k], f[k])
-    bmax = np.abs(f["beta"]).max()
-    sb = max(np.abs(f["beta"] - r["beta"]).max() / bmax, EPS64) if bmax > 0 else EPS64
-    si = max(np.abs(f["intercept"] / r["intercept"] - 1).max(), EPS64)
-    db = np.abs(got["beta"] - f["beta"]).max() / (bmax if bmax > 0 else 1.0)
-    di = np.abs(got["intercept"] / f["intercept"] - 1).max()
-    sl = sv = dl = dv = 0.0
-    for c in range(f["n_done"].size):
-        d = f["n_done"][c]
-        assert np.array_equal(got["iter"][c], f["iter"][:d, c]), (where, c, got["iter"][c], f["iter"][:d, c])
-        assert np.array_equal(got["nb_active"][c], f["nb_active"][:d, c]), (where, c)
-        sl = max(sl, np.abs(f["loss"][:d, c] / r["loss"][:d, c] - 1).max())
-        sv = max(sv, np.abs(f["loss_val"][:d, c] / r["loss_val"][:d, c] - 1).max())
-        dl = max(dl, np.abs(got["loss"][c] / f["loss"][:d, c] - 1).max())
-        dv = max(dv, np.abs(got["loss_val"][c] / f["loss_val"][:d, c] - 1).max())
-    sl, sv = max(sl, EPS64), max(sv, EPS64)
-    print("%s: beta %.3g (spread %.3g) of max|beta| %.3g, intercept %.3g (%.3g), loss %.3g (%.3g), loss_val %.3g (%.3g); "
-          "status %s, n_done %s, best %s" % (where, db, sb, bmax, di, si, dl, sl, dv, sv, f["status"], f["n_done"], f["best"]))
-    assert np.array_equal(got["beta"] != 0, f["beta"] != 0), where
-    assert db <= 1000 * sb and di <= 1000 * si and dl <= 1000 * sl and dv <= 1000 * sv, where
-    return f
-
-
-def _fit(ba, family, *a, **kw):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        return (ba.big_spLinReg if family == "linear" else ba.big_spLogReg)(*a, **kw)
 
 
 @pytest.mark.parametrize("family", ["linear", "logistic"])
