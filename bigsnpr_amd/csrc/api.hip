@@ -633,6 +633,97 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
   }
 }
 
+// ---- counts of the codes per group of rows (bsn_bed_group_counts; the table stays on the device for popstat.hip) ----------
+// d_table: 4 x G x m int32, table[4 * (G * j + g) + c].  Reads and writes neither counts_cache nor stats_cache: the
+// cached selections of the single-group calls stay as they are.
+void group_counts_device(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *group, int32_t G,
+                         const int64_t *ind_col, int64_t m, DevBuf<int32_t> &d_table, double ms_out[3]) {
+  require_gpu();
+  if (!bed) fail("bed_counts_by_group: no genotype handle");
+  if (G < 1) fail("bed_counts_by_group: the number of groups should be at least 1 (got %d).", (int)G);
+  if (n <= 0 || m <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
+  if (!group) fail("bed_counts_by_group: no group labels");
+  require_bits(bed, 2, "bed_counts_by_group");
+  refuse_generic(bed, "bed_counts_by_group");
+  if ((double)G * (double)m * 4.0 >= 9.0e15) fail("bed_counts_by_group: the table of %d groups x %lld variants is too large", (int)G, (long long)m);
+  BSN_HIP(hipSetDevice(bed->device));
+  // ---- the labels: range, group sizes, and whether one digit holds every multiplicity ----
+  const std::vector<int32_t> rows = to_i32(ind_row, n, bed->n, "ind.row");
+  std::vector<int64_t> size64((size_t)G, 0);
+  for (int64_t i = 0; i < n; i++) {
+    const int32_t g = group[i];
+    if (g < -1 || g >= G)
+      fail("bed_counts_by_group: label %d of row %lld is outside -1 .. %d (-1: in no group).", (int)g, (long long)i, (int)(G - 1));
+    if (g >= 0) size64[(size_t)g]++;
+  }
+  std::vector<int32_t> gsize((size_t)G);
+  for (int32_t g = 0; g < G; g++) {
+    if (size64[(size_t)g] > (int64_t)INT32_MAX)
+      fail("bed_counts_by_group: group %d holds %lld rows, more than a 32-bit count.", (int)g, (long long)size64[(size_t)g]);
+    gsize[(size_t)g] = (int32_t)size64[(size_t)g];
+  }
+  // (how often a file row was selected at all bounds its multiplicity under any one group: the pairs are only sorted
+  // when that bound exceeds a digit)
+  int64_t max_mult = 1;
+  if (ind_row) {
+    std::vector<int32_t> per_row((size_t)bed->n, 0);
+    int32_t top = 0;
+    for (int64_t i = 0; i < n; i++)
+      if (group[i] >= 0) top = std::max(top, ++per_row[(size_t)rows[(size_t)i]]);
+    max_mult = top;
+    if (top > 127) {
+      std::vector<int64_t> key;
+      key.reserve((size_t)n);
+      for (int64_t i = 0; i < n; i++)
+        if (group[i] >= 0) key.push_back((int64_t)rows[(size_t)i] * G + group[i]);
+      std::sort(key.begin(), key.end());
+      max_mult = 0;
+      for (size_t a = 0; a < key.size();) {
+        size_t e = a;
+        while (e < key.size() && key[e] == key[a]) e++;
+        max_mult = std::max<int64_t>(max_mult, (int64_t)(e - a));
+        a = e;
+      }
+    }
+  }
+  // (the four signed base-256 digits hold up to 0x7F7F7F7F)
+  if (max_mult > 0x7F7F7F7FLL) fail("bed_counts_by_group: one row is selected %lld times under one group.", (long long)max_mult);
+  const bool one_digit = max_mult <= 127;
+
+  DevBuf<int32_t> d_rows, d_group, d_gsize;
+  d_table.ensure((size_t)4 * G * m);
+  auto upload = [&](bsn_bed *on) {
+    if (ind_row) copy_h2d(on, d_rows.ensure((size_t)n), rows.data(), (size_t)n * 4);
+    copy_h2d(on, d_group.ensure((size_t)n), group, (size_t)n * 4);
+    copy_h2d(on, d_gsize.ensure((size_t)G), gsize.data(), (size_t)G * 4);
+  };
+  if (bed->streamed()) {
+    // slab by slab, exactly as counts_host walks: a slab's table comes back to the host, the whole one goes up once
+    std::vector<int32_t> table((size_t)4 * G * m), part;
+    DevBuf<int32_t> d_part;
+    SlabWalk W(bed);
+    upload(W.img);
+    W.run(ind_col, m, [&](bsn_bed *sb, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
+      const int64_t m_slab = (int64_t)local.size();
+      bsn_op op;
+      fill_op(&op, sb, nullptr, sb->n, local.data(), m_slab, nullptr, nullptr, true);
+      counts_grouped(&op, ind_row ? d_rows.p : nullptr, d_group.p, n, G, d_gsize.p, one_digit, d_part.ensure((size_t)4 * G * m_slab),
+                     ms_out);
+      part.resize((size_t)4 * G * m_slab);
+      copy_d2h(sb, part.data(), d_part.p, part.size() * 4);
+      for (size_t k = 0; k < P.size(); k++)
+        std::memcpy(table.data() + (size_t)4 * G * P[k], part.data() + (size_t)4 * G * k, (size_t)16 * G);
+    });
+    copy_h2d(W.img, d_table.p, table.data(), table.size() * 4);
+    BSN_HIP(hipStreamSynchronize(W.img->stream));
+    return;
+  }
+  upload(bed);
+  bsn_op op;
+  fill_op(&op, bed, nullptr, bed->n, ind_col, m, nullptr, nullptr, true);
+  counts_grouped(&op, ind_row ? d_rows.p : nullptr, d_group.p, n, G, d_gsize.p, one_digit, d_table.p, ms_out);
+}
+
 // ---- the handle's device-resident code counts over all samples (bsn_bed::stats_cache) ---------------------------------
 // to_cache: cache[variant of j] = counts[j]; else counts[j] = cache[variant of j].  One int4 per variant.
 __global__ void k_stats_cache_copy(int32_t *cache, int32_t *counts, const int32_t *cols, int64_t col0, int64_t m, int to_cache) {

@@ -510,6 +510,15 @@ void op_row_sums_sq(bsn_op *op, double *d_out);
 void op_row_counts(bsn_op *op, double *d_out);  // n doubles: sum_j A~[i, j]^2
 // weighted code counts: d_w = per-file-row integer weights (n_file doubles); out 4 x m
 void counts_weighted(bsn_op *op, const double *d_w, int64_t n_sub, int32_t *d_counts);
+// code counts per group of rows over the operator's variants: d_rows (n file rows, NULL = 0 .. n - 1) and d_group (n labels,
+// 0 .. G - 1 or -1) build the multiplicity panel on the device; d_gsize: rows per group; one_digit: no multiplicity exceeds
+// 127; d_table: 4 x G x m, table[4 * (G * j + g) + c].  ms_out (may be NULL) += device ms of panel, streaming launches,
+// finalising kernels.  Synchronises the handle's stream.
+void counts_grouped(bsn_op *op, const int32_t *d_rows, const int32_t *d_group, int64_t n, int32_t G, const int32_t *d_gsize,
+                    bool one_digit, int32_t *d_table, double ms_out[3]);
+// api.hip: the same from host lists, checked (labels, group sizes), resident or out of core; the table stays on the device
+void group_counts_device(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *group, int32_t G,
+                         const int64_t *ind_col, int64_t m, DevBuf<int32_t> &d_table, double ms_out[3]);
 void selftest();
 // event helpers around a streaming launch (no-ops unless op->profile)
 // roctx ranges (BSN_ROCTX=1: the roctx library is dlopen'ed on first use; otherwise, or when it is absent, no-ops):

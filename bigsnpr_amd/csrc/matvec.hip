@@ -2024,6 +2024,132 @@ void counts_weighted(bsn_op *op, const double *d_w, int64_t n_sub, int32_t *d_co
   BSN_HIP(hipGetLastError());
 }
 
+// ---- counts of the codes per GROUP of rows (bsn_bed_group_counts) ----------------------------------------
+// The counting pass above fills one of the 16 digit columns of a column block; here every column carries a group: the
+// n_file x G panel of row multiplicities (how often file row k was selected under group g) takes the place of the one
+// multiplicity vector, one int8 digit per group while no multiplicity exceeds 127 (16 groups per column block, 32 per
+// two-block launch), the four digits of counts_weighted otherwise (4 and 8).
+//
+// mult[v * n_file + rows[i]] += 1 for every selected row i whose group is g0 + v, v < gb.  Integer atomics: exact and
+// order-independent.  (rows == NULL: row i itself)
+__global__ void k_group_scatter(const int32_t *__restrict__ rows, const int32_t *__restrict__ group, int64_t n, int g0, int gb,
+                                int64_t n_file, int32_t *mult) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int v = group[i] - g0;
+  if (v < 0 || v >= gb) return;
+  const int64_t k = rows ? (int64_t)rows[i] : i;
+  if (k < 0 || k >= n_file) return;   // (the host has checked the list; a store outside the panel must not happen)
+  atomicAdd(&mult[(int64_t)v * n_file + k], 1);
+}
+
+// The digit panel of `gb` groups in the layout k_cprod reads (k_quant, PERM = 1, one plane): the 16 samples of block kb
+// under digit column col = v * S + s are the 16 bytes at q[(kb * ncol + col) * 16], sample e at byte (e % 4) * 4 + e / 4.
+// Signed base-256 digits, as k_quant cuts them.  One thread per (16-block, group); samples at or past n_file are zero.
+template <int S>
+__global__ __launch_bounds__(256) void k_group_digits(const int32_t *__restrict__ mult, int64_t n_file, int64_t nblk, int gb,
+                                                      int ncol, int8_t *__restrict__ q) {
+  const int64_t kb = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int v = blockIdx.y;
+  if (kb >= nblk || v >= gb) return;
+  uint32_t pk[S][4];
+#pragma unroll
+  for (int s = 0; s < S; s++)
+#pragma unroll
+    for (int w = 0; w < 4; w++) pk[s][w] = 0;
+#pragma unroll
+  for (int e = 0; e < 16; e++) {
+    const int64_t k = kb * 16 + e;
+    long long A = k < n_file ? (long long)mult[(int64_t)v * n_file + k] : 0;
+    const int pos = (e & 3) * 4 + (e >> 2);
+#pragma unroll
+    for (int s = 0; s < S; s++) {
+      const int8_t da = (int8_t)(A & 0xFF);
+      A = (A - da) >> 8;
+      pk[s][pos >> 2] |= (uint32_t)(uint8_t)da << (8 * (pos & 3));
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < S; s++)
+    *(uint4 *)(q + ((kb * ncol) + v * S + s) * 16) = uint4{pk[s][0], pk[s][1], pk[s][2], pk[s][3]};
+}
+
+// table[4 * (G * j + g0 + v) + c] from the three plane sums of group column v (Horner over its digits, as in
+// k_counts_final); code 0 is the group's size less the other three.  One thread per (variant, group of the launch).
+__global__ void k_group_counts_final(const int32_t *acc, int64_t m, int ncol, int S, int g0, int gb, int G,
+                                     const int32_t *__restrict__ gsize, int32_t *table) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= m * gb) return;
+  const int64_t j = idx / gb;
+  const int v = (int)(idx - j * gb);
+  const long long n2 = (long long)horner(acc + j * ncol + v * S, S);
+  const long long n1 = (long long)horner(acc + (m + j) * ncol + v * S, S);
+  const long long na = (long long)horner(acc + (2 * m + j) * ncol + v * S, S);
+  *(int4 *)(table + 4 * ((int64_t)G * j + g0 + v)) =
+      int4{(int32_t)((long long)gsize[g0 + v] - n1 - n2 - na), (int32_t)n1, (int32_t)n2, (int32_t)na};
+}
+
+void counts_grouped(bsn_op *op, const int32_t *d_rows, const int32_t *d_group, int64_t n, int32_t G, const int32_t *d_gsize,
+                    bool one_digit, int32_t *d_table, double ms_out[3]) {
+  require_bits(op->bed, 2, "bed_counts_by_group");
+  op->preq_X = nullptr;
+  bsn_bed *b = op->bed;
+  hipStream_t st = b->stream;
+  const int S = one_digit ? 1 : 4, per_block = 16 / S;
+  const int64_t npad = n_padded(b), nblk = npad / 16;
+  const int gmax = G < 2 * per_block ? G : 2 * per_block;   // groups of the largest launch
+  DevBuf<int32_t> mult;
+  mult.ensure((size_t)b->n * gmax);
+  int8_t *q = op->d_q.ensure((size_t)npad * 32);
+  int32_t *acc = op->d_acc.ensure((size_t)3 * op->m * 32);
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (ms_out)
+    for (auto &e : ev) BSN_HIP(hipEventCreate(&e));
+  float ms[3] = {0.f, 0.f, 0.f};
+  auto finish = [&] {
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e), e = nullptr;
+  };
+  try {
+    for (int g0 = 0; g0 < G;) {
+      const int left = G - g0;
+      const int NB = left > per_block ? 2 : 1;   // two column blocks where they save a launch
+      const int gb = left < NB * per_block ? left : NB * per_block, ncol = 16 * NB;
+      if (ms_out) BSN_HIP(hipEventRecord(ev[0], st));
+      BSN_HIP(hipMemsetAsync(mult.p, 0, (size_t)b->n * gb * sizeof(int32_t), st));
+      hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_rows, d_group, n, g0, gb,
+                         b->n, mult.p);
+      const dim3 qgrid((unsigned)((nblk + 255) / 256), (unsigned)gb);
+      if (S == 1) hipLaunchKernelGGL(k_group_digits<1>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
+      else hipLaunchKernelGGL(k_group_digits<4>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
+      BSN_HIP(hipGetLastError());
+      if (ms_out) BSN_HIP(hipEventRecord(ev[1], st));
+      launch_cprod<3, false, false>(op, NB, q, acc, kLutHom2, kLutHet, kLutNA);
+      if (ms_out) BSN_HIP(hipEventRecord(ev[2], st));
+      hipLaunchKernelGGL(k_group_counts_final, dim3((unsigned)((op->m * gb + 255) / 256)), dim3(256), 0, st, acc, op->m, ncol,
+                         S, g0, gb, G, d_gsize, d_table);
+      BSN_HIP(hipGetLastError());
+      if (ms_out) {
+        BSN_HIP(hipEventRecord(ev[3], st));
+        BSN_HIP(hipEventSynchronize(ev[3]));
+        for (int k = 0; k < 3; k++) {
+          float t = 0.f;
+          BSN_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
+          ms[k] += t;
+        }
+      }
+      g0 += gb;
+    }
+    BSN_HIP(hipStreamSynchronize(st));   // `mult` is released on return
+  } catch (...) {
+    finish();
+    throw;
+  }
+  finish();
+  if (ms_out)
+    for (int k = 0; k < 3; k++) ms_out[k] += (double)ms[k];
+}
+
 // ---------------------------------------------------------------------------
 // Instruction-level self test: v_perm_b32 source order and i8 MFMA layouts.
 __global__ void k_selftest(int *out) {

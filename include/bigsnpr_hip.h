@@ -225,6 +225,42 @@ int bsn_impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, ui
  * image, [2] the kernels that write the FBM bytes (0 when none were asked for) */
 int bsn_impute_last_ms(double *ms_out);
 
+/* ---- per-group genotype counts, snp_fst, snp_MAX3 ------------------------------------------------------
+ * Counts of the four codes of every selected variant, split by a label on the selected rows, in ONE pass over the image
+ * (the reference, and bsn_bed_col_counts, need one pass per group): res[4 * (G * j + g) + c] is the number of rows i with
+ * group[i] == g whose code at variant ind_col[j] is c — c = 0, 1, 2, 3 (NA), the row order of bsn_bed_col_counts.
+ * group[i] is 0 .. G - 1, or -1 for a row in no group; rows count as often as ind_row lists them, and a file row may be
+ * listed under several groups.  The multiplicity panel (file rows x groups) is built on the device with integer atomics
+ * and fills the digit columns of the streaming crossproduct kernel: 16 groups per column block while no multiplicity
+ * exceeds 127, 4 otherwise; two column blocks per launch where that saves one.  Resident and out-of-core handles (slabs,
+ * like bsn_bed_col_counts); the streaming-layout copy is read when the handle has one.  Refused with a message: G < 1, a
+ * label outside -1 .. G - 1, a group of more than INT32_MAX rows, a byte (dosage) image.  The counts that
+ * bsn_bed_col_counts keeps on the handle are neither read nor changed. */
+int bsn_bed_group_counts(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *group /* [n] */, int32_t G,
+                         const int64_t *ind_col, int64_t m, int32_t *res /* 4 x G x m */);
+/* R: snp_fst (R/Fst.R:47-85), Weir & Cockerham's Fst from per-population allele frequencies.  af, N: r x m, population
+ * p's vector (the `af` and `N` of bed_MAF) at p * m.  fst (m, may be NULL): a / (a + b + c) per variant, NaN where the
+ * variant is not kept (p_bar outside (min_maf, 1 - min_maf), or NaN).  overall (3, may be NULL): sum a / sum (a + b + c)
+ * over the kept variants, then the two sums; they are taken in a fixed order (blocks of 256 variants by a binary tree,
+ * block sums in index order), so the result does not depend on the launch.  Errors, the reference's: "You should
+ * provide frequencies for at least 2 populations.", "Parameter 'min_maf' should be in range [0, 0.45]." */
+int bsn_fst(const double *af, const double *N, int64_t r, int64_t m, double min_maf, double *fst /* or NULL */,
+            double *overall /* or NULL */);
+/* the same from the genotypes: bsn_bed_group_counts, allele frequencies as bed_MAF forms them and the statistic, all on the
+ * device; only fst / overall come back.  Bit-identical to bsn_fst on the frequencies of the same groups. */
+int bsn_bed_fst(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *group /* [n] */, int32_t G,
+                const int64_t *ind_col, int64_t m, double min_maf, double *fst /* or NULL */, double *overall /* or NULL */);
+/* R: snp_MAX3 (R/MAX3.R:3-28,81-107).  y01[i]: 0 = control, 1 = case (anything else is an error).  score[j] = max over
+ * x in val[0 .. L - 1] of Z_CATT(x)^2 with genotype scores (0, x, 1), from the counts of 0 / 1 / 2 among cases and
+ * controls (missing genotypes are left out); a NaN statistic counts as 0.  val = (0, 0.5, 1): MAX3; (0.5): the Armitage
+ * trend test. */
+int bsn_snp_max3(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *y01 /* [n] */, const int64_t *ind_col,
+                 int64_t m, const double *val, int32_t L, double *score /* [m] */);
+/* device milliseconds (HIP events) of the last of the four calls above in this process: ms_out[0] the multiplicity and
+ * digit panels, [1] the streaming launches, [2] the finalising kernels, [3] the statistic (0 for bsn_bed_group_counts).
+ * One record per process, written without a lock, like bsn_impute_last_ms. */
+int bsn_popstat_last_ms(double *ms_out /* 4 */);
+
 /* _bigsnpr_prod_and_rowSumsSq (6 args) src/bed-fun.cpp:103-133 (the kernel of
  * bed_projectSelfPCA, R/bed-projectPCA.R:45-59): XV[n x K] = A~ V[m x K] and
  * rowSumsSq[i] = sum_j A~[i, j]^2, column-major host buffers. */
