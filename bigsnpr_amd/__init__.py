@@ -13,9 +13,11 @@ from .comm import Comm, negotiate as negotiate_exchange, set_exchange_mode  # no
 from .ld import (CODE_012, CODE_DOSAGE, CODE_IMPUTE_PRED, FBM_code256, bed_clumping, bed_cor,  # noqa: F401,E402
                  bed_ld_scores, big_cprodVec, big_prodVec, big_randomSVD, snp_clumping, snp_fake, snp_colstats, snp_cor, snp_ld_scores, snp_MAF, snp_scaleAlpha,
                  snp_scaleBinom)
-from .prs import (bed_projectSelfPCA, bed_tcrossprodSelf, prod_and_rowSumsSq,  # noqa: F401,E402
-                  prod_and_rowSumsSq2, prodVecRev, snp_PRS, snp_projectSelfPCA)
+from .prs import (bed_projectSelfPCA, bed_tcrossprodSelf, pca_OADP_proj2, pca_OADP_proj_device,  # noqa: F401,E402
+                  prod_and_rowSumsSq, prod_and_rowSumsSq2, prodVecRev, project_pca, snp_PRS, snp_projectSelfPCA)
 from .autosvd import bed_autoSVD, snp_autoSVD  # noqa: F401,E402
+from .match import same_ref, snp_match  # noqa: F401,E402
+from .project import bed_projectPCA  # noqa: F401,E402
 from .plink_io import bed_to_bytes, snp_readBed, snp_writeBed  # noqa: F401,E402
 from .pcadapt import bed_pcadapt, multLinReg, snp_pcadapt  # noqa: F401,E402
 from .gwas import big_univLinReg, big_univLogReg  # noqa: F401,E402

@@ -113,7 +113,10 @@ SIGNATURES = {
     "bsn_bed_cprod_planes": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p, f64p]),
     "bsn_bed_prod_and_rowsumssq": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, f64p, f64p]),
     "bsn_snp_prod_and_rowsumssq2": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, f64p, f64p]),
-    "bsn_mult_lin_reg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
+    "bsn_pca_oadp_proj": (C.c_int, [f64p, f64p, f64p, i64, i64, f64p]),
+    "bsn_bed_project_pca": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, f64p, f64p, f64p, f64p]),
+    "bsn_project_last_ms": (C.c_int, [f64p]),
+    "bsn_mult_lin_reg":(C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
     "bsn_univ_linreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p, f64p]),
     "bsn_univ_logreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, C.c_double, C.c_int32, f64p, f64p, i32p]),
     "bsn_bed_sp_reg": (C.c_int, [vp, i64p, i64, i64p, i64] + _PLR_TAIL),

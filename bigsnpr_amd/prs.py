@@ -126,15 +126,69 @@ def pca_OADP_proj2(XV, X_norm, sval):
     return rho[:, None] * np.einsum("nk,nkj->nj", new_aug, R)
 
 
-def bed_projectSelfPCA(obj_svd, obj_bed, ind_row, ind_col=None, ncores=1):
+def pca_OADP_proj_device(XV, X_norm, sval):
+    """pca_OADP_proj2 on the device (bsn_pca_oadp_proj: one group of lanes per sample, csrc/oadp_step.hpp).  A row with
+    a NaN or an infinity comes back NaN; `sval` must be finite and positive, at most 60 values."""
+    XV = np.asfortranarray(np.asarray(XV, dtype=np.float64))
+    X_norm = as_f64(np.ravel(X_norm))
+    sval = as_f64(np.ravel(sval))
+    if XV.ndim != 2 or sval.size != XV.shape[1] or X_norm.size != XV.shape[0]:
+        raise ValueError("Incompatibility between dimensions.")
+    out = np.empty(XV.shape, dtype=np.float64, order="F")
+    check(_lib.load().bsn_pca_oadp_proj(XV.ctypes.data_as(f64p), ptr(X_norm, f64p), ptr(sval, f64p), XV.shape[0],
+                                        XV.shape[1], out.ctypes.data_as(f64p)))
+    return out
+
+
+def project_pca(obj_bed, ind_row, ind_col, center, scale, V, sval):
+    """(X V, rowSums(X^2), OADP projection) of the scaled sub-matrix X in one call (bsn_bed_project_pca): the three
+    stay on the device between the passes.  A negative scale is a variant whose alleles are reversed in `obj_bed`."""
+    ir, ic = _args(obj_bed, ind_row, ind_col)
+    center, scale = as_f64(np.ravel(center)), as_f64(np.ravel(scale))
+    V = np.asfortranarray(np.asarray(V, dtype=np.float64))
+    if V.ndim == 1:
+        V = V[:, None]
+    sval = as_f64(np.ravel(sval))
+    if V.shape[0] != ic.size or sval.size != V.shape[1]:
+        raise ValueError("Incompatibility between dimensions.")
+    assert_lengths(center, ic); assert_lengths(scale, ic)
+    XV = np.empty((ir.size, V.shape[1]), dtype=np.float64, order="F")
+    oadp = np.empty((ir.size, V.shape[1]), dtype=np.float64, order="F")
+    rs = np.empty(ir.size)
+    check(_lib.load().bsn_bed_project_pca(obj_bed.handle, ptr(ir, i64p), ir.size, ptr(ic, i64p), ic.size,
+                                          ptr(center, f64p), ptr(scale, f64p), V.ctypes.data_as(f64p), V.shape[1],
+                                          ptr(sval, f64p), XV.ctypes.data_as(f64p), ptr(rs, f64p),
+                                          oadp.ctypes.data_as(f64p)))
+    return XV, rs, oadp
+
+
+def project_last_ms():
+    """device milliseconds of the last pca_OADP_proj_device / project_pca call of this process: [the product and
+    row-norm passes, the OADP launch]"""
+    ms = np.zeros(2)
+    check(_lib.load().bsn_project_last_ms(ptr(ms, f64p)))
+    return ms
+
+
+def _check_oadp(oadp):
+    if oadp not in ("host", "device"):
+        raise ValueError("'oadp' should be \"host\" or \"device\".")
+
+
+def bed_projectSelfPCA(obj_svd, obj_bed, ind_row, ind_col=None, ncores=1, oadp="host"):
     """R/bed-projectPCA.R:196-227: simple projection X V of new rows on the PCs of `obj_svd`, the squared
-    row norms, and the OADP projection computed from them (pca_OADP_proj2 above)."""
+    row norms, and the OADP projection computed from them: oadp = "host" by pca_OADP_proj2 above, "device" by the
+    kernel, in one call with the product (project_pca)."""
+    _check_oadp(oadp)
     ind_col = obj_svd["subset"] if ind_col is None and "subset" in obj_svd else ind_col
     if ind_col is None:
         raise ValueError("'ind.col' can't be `NULL`.")     # check_args(), test-2-pca-project.R:16-17
     ir, ic = _args(obj_bed, ind_row, ind_col)
     if np.asarray(obj_svd["v"]).shape[0] != ic.size:
         raise ValueError("Incompatibility between dimensions.")
+    if oadp == "device":
+        XV, X_norm, proj = project_pca(obj_bed, ir, ic, obj_svd["center"], obj_svd["scale"], obj_svd["v"], obj_svd["d"])
+        return dict(obj_svd_ref=obj_svd, simple_proj=XV, X_norm=X_norm, OADP_proj=proj)
     XV, X_norm = prod_and_rowSumsSq(obj_bed, ir, ic, obj_svd["center"], obj_svd["scale"], obj_svd["v"])
     return dict(obj_svd_ref=obj_svd, simple_proj=XV, X_norm=X_norm,
                 OADP_proj=pca_OADP_proj2(XV, X_norm, obj_svd["d"]))
@@ -160,16 +214,20 @@ def prod_and_rowSumsSq2(G, ind_row, ind_col, center, scale, V):
     return XV, rs
 
 
-def snp_projectSelfPCA(obj_svd, G, ind_row, ind_col=None, ncores=1):
-    """R/bed-projectPCA.R:252-281 (a row with a missing value is NaN in all three outputs, as in the reference)"""
+def snp_projectSelfPCA(obj_svd, G, ind_row, ind_col=None, ncores=1, oadp="host"):
+    """R/bed-projectPCA.R:252-281 (a row with a missing value is NaN in all three outputs, as in the reference).
+    oadp = "device": the OADP step by the kernel (pca_OADP_proj_device), which answers a NaN row with a NaN row."""
+    _check_oadp(oadp)
     ind_col = obj_svd["subset"] if ind_col is None and "subset" in obj_svd else ind_col
     if ind_col is None:
         raise ValueError("'ind.col' can't be `NULL`.")
     im, ir, ic = _ind(G, ind_row, ind_col)
     assert_lengths(np.arange(np.asarray(obj_svd["v"]).shape[0]), ic)
     XV, X_norm = prod_and_rowSumsSq2(im, ir, ic, obj_svd["center"], obj_svd["scale"], obj_svd["v"])
+    if oadp == "device":
+        return dict(obj_svd_ref=obj_svd, simple_proj=XV, OADP_proj=pca_OADP_proj_device(XV, X_norm, obj_svd["d"]))
     ok = ~(np.isnan(X_norm) | np.isnan(XV).any(axis=1))
-    oadp = np.full(XV.shape, np.nan)
+    proj = np.full(XV.shape, np.nan)
     if ok.any():
-        oadp[ok] = pca_OADP_proj2(XV[ok], X_norm[ok], obj_svd["d"])
-    return dict(obj_svd_ref=obj_svd, simple_proj=XV, OADP_proj=oadp)
+        proj[ok] = pca_OADP_proj2(XV[ok], X_norm[ok], obj_svd["d"])
+    return dict(obj_svd_ref=obj_svd, simple_proj=XV, OADP_proj=proj)

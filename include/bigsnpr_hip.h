@@ -274,6 +274,25 @@ int bsn_snp_prod_and_rowsumssq2(bsn_bed *bed, const int64_t *ind_row, int64_t n,
                                 int64_t m, const double *center, const double *scale, const double *V,
                                 int64_t K, double *XV, double *rowSumsSq);
 
+/* OADP_proj of R/bed-projectPCA.R:62-67 (bigutilsr::pca_OADP_proj2, external to the reference tree): the Online
+ * Augmentation - Decomposition - Procrustes projection of n new samples from their simple projections XV[n x K], their
+ * squared norms X_norm[n] and the K singular values sval of the reference PCA; out[n x K].  Column-major host buffers.
+ * One group of lanes per sample, two one-sided Jacobi decompositions of order K + 1 and K in LDS (csrc/oadp_step.hpp).
+ * 1 <= K <= 60; sval must be finite and positive (checked before any launch).  A row that holds a NaN or an infinity in
+ * XV or X_norm comes back NaN. */
+int bsn_pca_oadp_proj(const double *XV, const double *X_norm, const double *sval, int64_t n, int64_t K, double *out);
+
+/* bed_projectPCA / bed_projectSelfPCA (R/bed-projectPCA.R:147-171, 214-226) in one call on a resident image: what
+ * bsn_bed_prod_and_rowsumssq does, followed by the OADP kernel on the device buffers; XV[n x K], rowSumsSq[n] and
+ * OADP[n x K] come back together.  A negative entry of scale is accepted: it is a variant whose alleles are reversed in
+ * the target (centre' = (centre - 1) beta + 1, scale' = scale beta with beta = -1). */
+int bsn_bed_project_pca(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
+                        const double *center, const double *scale, const double *V, int64_t K, const double *sval,
+                        double *XV, double *rowSumsSq, double *OADP);
+/* device milliseconds (HIP events) of the last of the two calls above in this process: ms_out[0] the product and row-norm
+ * passes (0 for bsn_pca_oadp_proj), [1] the OADP launch.  One record per process, written without a lock. */
+int bsn_project_last_ms(double *ms_out /* 2 */);
+
 /* The genotype-touching part of snp_grid_PRS (R/SCT.R:201-262), which in the
  * reference is one snp_PRS call (R/PRS.R:36-76 -> bigstatsr::big_prodVec) per clumping set:
  * scores for C column sets x T thresholds in a single sweep, one n x C GEMM per threshold bin.
