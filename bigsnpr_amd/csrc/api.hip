@@ -1,78 +1,16 @@
-// api.hip — the extern "C" surface declared in include/bigsnpr_hip.h.
-#include <dlfcn.h>
-#include <fcntl.h>
-#include <pthread.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <cerrno>
-#include <cmath>
-#include <condition_variable>
-#include <chrono>
-#include <cstring>
-#include <limits>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <sched.h>
-#include <atomic>
-#include <thread>
-
-#include <cstdlib>
-
-#include "bsn_internal.hpp"
+// api.hip — the operator over a sub-view, the code counts and their caches, and the one-shot .Call replacements declared
+// in include/bigsnpr_hip.h.  The process-level plumbing is runtime.hip, the handle as an object handle.hip.
 #include <cxxabi.h>
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+
+#include "bsn_internal.hpp"
+
 namespace bsn {
-
-// ---- roctx (optional) ------------------------------------------------------------------------------------------
-namespace {
-struct Roctx {
-  int (*push)(const char *) = nullptr;
-  int (*pop)() = nullptr;
-  Roctx() {
-    if (!getenv("BSN_ROCTX")) return;
-    void *h = nullptr;
-    for (const char *name : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"})
-      if ((h = dlopen(name, RTLD_NOW | RTLD_GLOBAL))) break;
-    if (!h) return;
-    push = (int (*)(const char *))dlsym(h, "roctxRangePushA");
-    pop = (int (*)())dlsym(h, "roctxRangePop");
-    if (!push || !pop) push = nullptr, pop = nullptr;
-  }
-};
-Roctx &roctx() {
-  static Roctx r;
-  return r;
-}
-}  // namespace
-void roctx_push(const char *name) {
-  if (roctx().push) roctx().push(name);
-}
-void roctx_pop() {
-  if (roctx().pop) roctx().pop();
-}
-
-static thread_local std::string g_err;
-void set_error(const char *msg) { g_err = msg ? msg : ""; }
-void fail(const char *fmt, ...) {
-  char buf[1024];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  throw Error(buf);
-}
-
-void require_gpu() {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess || n <= 0)
-    fail("no HIP device available: libbigsnpr_hip has no CPU fallback (%s)",
-         e == hipSuccess ? "device count is 0" : hipGetErrorString(e));
-}
 
 // a NULL index list means the first `len` rows / columns, everywhere in this ABI
 static std::vector<int32_t> to_i32(const int64_t *ind, int64_t len, int64_t limit, const char *what) {
@@ -92,314 +30,9 @@ static std::vector<int32_t> to_i32(const int64_t *ind, int64_t len, int64_t limi
   }
   return v;
 }
-
-// ---- cache of released device blocks (bsn_internal.hpp) ---------------------------------
-namespace {
-struct DevCache {
-  std::mutex mu;
-  std::multimap<size_t, void *> free_blocks[16];  // per device, keyed by block size
-  size_t held[16] = {0};
-};
-DevCache &dev_cache() {
-  static DevCache *c = new DevCache();  // never destroyed: blocks may be released during process exit
-  return *c;
-}
-// sizes are rounded to 2^k or 1.5 * 2^k (>= 4 KiB) so that a repeated call finds its blocks again
-size_t size_class(size_t bytes) {
-  size_t c = 4096;
-  while (c < bytes) {
-    if (c + c / 2 >= bytes) return c + c / 2;
-    c *= 2;
-  }
-  return c;
-}
-}  // namespace
-
-void *dev_alloc(size_t bytes, size_t *granted, int *device) {
-  if (bytes == 0) bytes = 1;
-  int dev = 0;
-  BSN_HIP(hipGetDevice(&dev));
-  *device = dev;
-  const bool cached = bytes <= kDevCacheMaxBlock && dev < 16;
-  const size_t want = cached ? size_class(bytes) : bytes;
-  if (cached) {
-    DevCache &c = dev_cache();
-    std::lock_guard<std::mutex> lk(c.mu);
-    auto it = c.free_blocks[dev].find(want);
-    if (it != c.free_blocks[dev].end()) {
-      void *p = it->second;
-      c.free_blocks[dev].erase(it);
-      c.held[dev] -= want;
-      *granted = want;
-      return p;
-    }
-  }
-  static const bool trace = getenv("BSN_ALLOC_TRACE") != nullptr;  // every real allocation on stderr
-  void *p = nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
-  hipError_t e = hipMalloc(&p, want);
-  if (trace)
-    std::fprintf(stderr, "[bsn alloc] hipMalloc %zu bytes (asked %zu): %.2f ms\n", want, bytes,
-                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-  if (e == hipErrorOutOfMemory) {  // give the cached blocks back and try once more
-    (void)hipGetLastError();
-    dev_cache_flush();
-    e = hipMalloc(&p, want);
-  }
-  if (e != hipSuccess) fail("HIP error %s allocating %zu bytes of device memory", hipGetErrorString(e), want);
-  *granted = want;
-  return p;
-}
-
-void dev_release(void *p, size_t granted, int dev) {
-  if (!p) return;
-  DevCache &c = dev_cache();
-  if (granted <= kDevCacheMaxBlock && dev >= 0 && dev < 16 && size_class(granted) == granted) {
-    // hipFree's ordering: nothing on the device still uses the block once it can be handed out again
-    int cur = dev;
-    (void)hipGetDevice(&cur);
-    if (cur != dev) (void)hipSetDevice(dev);
-    (void)hipDeviceSynchronize();
-    if (cur != dev) (void)hipSetDevice(cur);
-    std::lock_guard<std::mutex> lk(c.mu);
-    if (c.held[dev] + granted <= kDevCacheMaxTotal) {
-      c.free_blocks[dev].emplace(granted, p);
-      c.held[dev] += granted;
-      return;
-    }
-  }
-  static const bool trace = getenv("BSN_ALLOC_TRACE") != nullptr;
-  if (trace) std::fprintf(stderr, "[bsn alloc] hipFree %zu bytes\n", granted);
-  (void)hipFree(p);
-}
-
-size_t dev_cache_held() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
-  DevCache &c = dev_cache();
-  std::lock_guard<std::mutex> lk(c.mu);
-  return c.held[dev];
-}
-
-void dev_cache_flush() {
-  DevCache &c = dev_cache();
-  std::lock_guard<std::mutex> lk(c.mu);
-  for (int d = 0; d < 16; d++) {
-    for (auto &kv : c.free_blocks[d]) (void)hipFree(kv.second);
-    c.free_blocks[d].clear();
-    c.held[d] = 0;
-  }
-}
-
-constexpr size_t kStagePiece = 32u << 20;
-
-void stage_init(bsn_bed *b) {
-  for (int i = 0; i < 2; i++) {
-    if (!b->h_stage[i]) BSN_HIP(hipHostMalloc((void **)&b->h_stage[i], kStagePiece, hipHostMallocDefault));
-    if (!b->ev_stage[i]) BSN_HIP(hipEventCreateWithFlags(&b->ev_stage[i], hipEventDisableTiming));
-  }
-}
-
-// Helper threads that live as long as the process (created on first use, re-created in a forked child) take their
-// share of a host copy of 256 KB or more: the three m-vectors of a one-shot product at BASELINE config 2 — x, centre,
-// scale, 1.6 MB each — cost 0.12 ms apiece through one core, a third of the call's time outside its streaming kernel;
-// threads created per copy (round 2's way for pieces of 8 MB and more) cost more than they save at this size.  A
-// helper that has just finished a share polls for the next one for some tens of microseconds before it goes to
-// sleep: the copies of one call follow each other within that time, so only the first pays a wake-up.
-namespace {
-struct CopyJob {
-  void *dst = nullptr;
-  const void *src = nullptr;
-  size_t len = 0;
-};
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-  __builtin_ia32_pause();
-#elif defined(__aarch64__)
-  __asm__ __volatile__("yield");
-#else
-  std::this_thread::yield();
-#endif
-}
-struct CopyPool {
-  static constexpr int kMaxHelpers = 6;
-  int nh = 2;
-  std::mutex mu;
-  std::condition_variable cv_go;
-  CopyJob job[kMaxHelpers];
-  std::atomic<unsigned long long> seq{0};
-  std::atomic<int> pending{0}, sleepers{0};
-  pid_t owner = 0;
-  void start() {
-    owner = getpid();
-    cpu_set_t set;
-    int cpus = (int)std::thread::hardware_concurrency();
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) cpus = std::min(cpus > 0 ? cpus : 1, CPU_COUNT(&set));
-    nh = std::max(1, std::min(kMaxHelpers, cpus / 2 - 1));
-    if (const char *e = getenv("BSN_COPY_THREADS")) nh = std::max(1, std::min(kMaxHelpers, atoi(e) - 1));
-    for (int h = 0; h < nh; h++)
-      std::thread([this, h] {
-        unsigned long long seen = 0;
-        for (;;) {
-          int spins = 0;
-          while (seq.load(std::memory_order_acquire) == seen) {
-            if (++spins < 4000) {
-              cpu_relax();
-              continue;
-            }
-            std::unique_lock<std::mutex> lk(mu);
-            sleepers.fetch_add(1);
-            cv_go.wait(lk, [&] { return seq.load() != seen; });
-            sleepers.fetch_sub(1);
-          }
-          seen = seq.load(std::memory_order_acquire);   // (the caller waits for every share before the next copy)
-          const CopyJob j = job[h];
-          if (j.len) std::memcpy(j.dst, j.src, j.len);
-          pending.fetch_sub(1, std::memory_order_release);
-        }
-      }).detach();
-  }
-  void copy(void *dst, const void *src, size_t len) {
-    const size_t part = (len / (size_t)(nh + 1) + 63) & ~(size_t)63;
-    for (int h = 0; h < nh; h++) {
-      const size_t lo = part * (size_t)(h + 1), hi = h + 1 == nh ? len : std::min(len, lo + part);
-      job[h] = lo < hi ? CopyJob{(uint8_t *)dst + lo, (const uint8_t *)src + lo, hi - lo} : CopyJob{};
-    }
-    pending.store(nh, std::memory_order_relaxed);
-    seq.fetch_add(1);
-    if (sleepers.load() > 0) {
-      { std::lock_guard<std::mutex> lk(mu); }
-      cv_go.notify_all();
-    }
-    std::memcpy(dst, src, std::min(part, len));
-    while (pending.load(std::memory_order_acquire) != 0) cpu_relax();
-  }
-};
-CopyPool *g_pool = nullptr;
-// one copy at a time goes through the pool (calls on different handles may be concurrent: the others copy on their own
-// thread instead of queueing behind it).  A raw pointer, so that the child of a fork can start from a fresh mutex: the
-// parent's may have been held by a thread that does not exist in the child.
-std::mutex *g_pool_mu = new std::mutex();
-void pool_atfork_child() {
-  g_pool_mu = new std::mutex();   // (the parent's mutex and pool object are abandoned in the child, not freed)
-  g_pool = nullptr;
-}
-const int g_pool_atfork = pthread_atfork(nullptr, nullptr, pool_atfork_child);
-}  // namespace
-
-// host copy between caller memory and a staging buffer
-static void host_copy(void *dst, const void *src, size_t len) {
-  static const bool pool_off = [] {
-    const char *e = getenv("BSN_COPY_THREADS");  // 1: every copy on the calling thread
-    return e && atoi(e) <= 1;
-  }();
-  if (len < (256u << 10) || pool_off) {
-    std::memcpy(dst, src, len);
-    return;
-  }
-  std::unique_lock<std::mutex> lk(*g_pool_mu, std::try_to_lock);
-  if (!lk.owns_lock()) {   // another thread's copy is in the pool: do not queue behind it
-    std::memcpy(dst, src, len);
-    return;
-  }
-  if (!g_pool || g_pool->owner != getpid()) {   // first use, or a forked child (threads do not survive a fork)
-    g_pool = new CopyPool();
-    g_pool->start();
-  }
-  g_pool->copy(dst, src, len);
-}
-
-// Host -> device through the two pinned staging buffers, ordered on the handle's stream.  Returns as
-// soon as the caller's memory has been read (the last pieces may still be on their way: whatever uses
-// d_dst is queued behind them on the same stream).
-void copy_h2d(bsn_bed *b, void *d_dst, const void *src, size_t bytes, hipStream_t stream) {
-  if (!stream) stream = b->stream;
-  stage_init(b);
-  for (size_t off = 0; off < bytes; off += kStagePiece) {
-    const size_t len = std::min(kStagePiece, bytes - off);
-    const int s = (int)(b->stage_next++ & 1);
-    if (b->stage_busy[s]) BSN_HIP(hipEventSynchronize(b->ev_stage[s]));  // its previous piece has left the buffer
-    host_copy(b->h_stage[s], (const uint8_t *)src + off, len);
-    BSN_HIP(hipMemcpyAsync((uint8_t *)d_dst + off, b->h_stage[s], len, hipMemcpyHostToDevice, stream));
-    BSN_HIP(hipEventRecord(b->ev_stage[s], stream));
-    b->stage_busy[s] = true;
-  }
-}
-
-// the handle's second stream: uploads that may run beside the kernels of the main one (op_cprod's centre / scale)
-hipStream_t upload_stream(bsn_bed *b) {
-  if (!b->stream_up) {
-    BSN_HIP(hipStreamCreateWithFlags(&b->stream_up, hipStreamNonBlocking));
-    BSN_HIP(hipEventCreateWithFlags(&b->ev_up, hipEventDisableTiming));
-  }
-  return b->stream_up;
-}
-
-// true when the runtime knows `p` as page-locked host memory (bsn_host_alloc, or registered by the
-// caller): the DMA engines can reach it directly, no staging
-bool host_is_pinned(const void *p) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();   // an ordinary pointer is reported as an error: not one
-    return false;
-  }
-  return at.type == hipMemoryTypeHost;
-}
-
-// Device -> host; complete when it returns.
-void copy_d2h(bsn_bed *b, void *dst, const void *d_src, size_t bytes) {
-  if (bytes >= (1u << 20) && host_is_pinned(dst)) {   // page-locked destination: one DMA, no host copy
-    BSN_HIP(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, b->stream));
-    BSN_HIP(hipStreamSynchronize(b->stream));
-    return;
-  }
-  stage_init(b);
-  if (b->stream_up)   // an upload on the second stream may still be reading a staging buffer
-    for (int i = 0; i < 2; i++)
-      if (b->stage_busy[i]) BSN_HIP(hipEventSynchronize(b->ev_stage[i]));
-  const size_t npiece = (bytes + kStagePiece - 1) / kStagePiece;
-  for (size_t k = 0; k <= npiece; k++) {
-    if (k < npiece) {  // launch piece k (stream order puts it behind any upload still reading the buffer)
-      const size_t off = k * kStagePiece, len = std::min(kStagePiece, bytes - off);
-      BSN_HIP(hipMemcpyAsync(b->h_stage[k & 1], (const uint8_t *)d_src + off, len, hipMemcpyDeviceToHost, b->stream));
-      BSN_HIP(hipEventRecord(b->ev_stage[k & 1], b->stream));
-    }
-    if (k >= 1) {  // drain piece k - 1 while piece k is on its way
-      const size_t off = (k - 1) * kStagePiece, len = std::min(kStagePiece, bytes - off);
-      BSN_HIP(hipEventSynchronize(b->ev_stage[(k - 1) & 1]));
-      host_copy((uint8_t *)dst + off, b->h_stage[(k - 1) & 1], len);
-    }
-  }
-  b->stage_busy[0] = b->stage_busy[1] = false;  // every event recorded so far has completed
-}
-
-static void free_bed(bsn_bed *b) { bed_free(b); }
-void bed_free(bsn_bed *b) {
-  if (!b) return;
-  for (int i = 0; i < 2; i++) {
-    if (b->h_stage[i]) (void)hipHostFree(b->h_stage[i]);
-    if (b->ev_stage[i]) (void)hipEventDestroy(b->ev_stage[i]);
-  }
-  if (b->smaj_job) {   // a background build of the sample-major copy reads d_img: let it end before the image goes
-    try { image_smaj_wait(b); } catch (...) {}
-  }
-  if (b->d_img) (void)hipFree(b->d_img);
-  if (b->map_base) (void)munmap(b->map_base, b->map_len);
-  if (b->fd_file >= 0) (void)close(b->fd_file);
-  if (b->slab_stage) delete (bsn::FileStage *)b->slab_stage;
-  if (b->slab_img) bed_free(b->slab_img);
-  if (b->sub) bed_free(b->sub);
-  if (b->d_tiled) (void)hipFree(b->d_tiled);
-  if (b->d_smaj) (void)hipFree(b->d_smaj);
-  if (b->d_lut) (void)hipFree(b->d_lut);
-  if (b->h_na_blocks) (void)hipHostFree(b->h_na_blocks);
-  if (b->d_na_blocks) (void)hipFree(b->d_na_blocks);
-  if (b->ev0) (void)hipEventDestroy(b->ev0);
-  if (b->ev1) (void)hipEventDestroy(b->ev1);
-  if (b->ev_up) (void)hipEventDestroy(b->ev_up);
-  if (b->stream_up) (void)hipStreamDestroy(b->stream_up);
-  if (b->stream && !b->stream_borrowed) (void)hipStreamDestroy(b->stream);
-  delete b;
+// a checked list on the device, uploaded through the handle `on` (its staging buffers, its stream)
+static void upload_list(bsn_bed *on, DevBuf<int32_t> &d, const std::vector<int32_t> &v) {
+  copy_h2d(on, d.ensure(v.size()), v.data(), v.size() * 4);
 }
 
 __global__ void k_fill_f64(double *p, int64_t n, double v) {
@@ -424,10 +57,7 @@ void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
     for (int64_t i = 0; ident && i < n; i++) ident = (ind_row[i] == i);
   }
   op->rows_identity = ident;
-  if (!ident) {
-    auto r = to_i32(ind_row, n, bed->n, "ind.row");
-    copy_h2d(bed, op->d_rows.ensure((size_t)n), r.data(), (size_t)n * 4);
-  }
+  if (!ident) upload_list(bed, op->d_rows, to_i32(ind_row, n, bed->n, "ind.row"));
   // cols
   bool contig = true;
   int64_t c0 = ind_col ? ind_col[0] : 0;
@@ -440,9 +70,8 @@ void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
   op->col0 = contig ? c0 : 0;
   if (!contig) {
     auto c = to_i32(ind_col, m, bed->m, "ind.col");
-    int64_t m_pad = bsn::round_up(m, 64);
-    c.resize((size_t)m_pad, c[0]);
-    copy_h2d(bed, op->d_cols.ensure((size_t)m_pad), c.data(), (size_t)m_pad * 4);
+    c.resize((size_t)bsn::round_up(m, 64), c[0]);
+    upload_list(bed, op->d_cols, c);
   }
   // missing-value knowledge (BSN_FORCE_NA_PLANE=1 keeps the general kernels, for A/B tests)
   op->no_na = false;
@@ -474,7 +103,7 @@ void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
 void counts_device(bsn_op *op, const int64_t *ind_row, int64_t n, int32_t *d_counts) {
   bsn_bed *bed = op->bed;
   if (op->rows_identity) {
-    counts_all_rows(bed, op->cols_contig ? nullptr : op->d_cols.p, op->col0, op->m, d_counts);
+    counts_all_rows(bed, op->cols(), op->col0, op->m, d_counts);
   } else {
     std::vector<double> w((size_t)bed->n, 0.0);
     for (int64_t i = 0; i < n; i++) w[(size_t)(ind_row ? ind_row[i] : i)] += 1.0;
@@ -485,99 +114,9 @@ void counts_device(bsn_op *op, const int64_t *ind_row, int64_t n, int32_t *d_cou
   }
 }
 
-// the same into a host 4 x m int32 array
-void require_resident(const bsn_bed *b, const char *what) {
-  if (b->streamed())
-    fail("%s needs the genotype image resident on the device: this handle streams its file (%.1f GB do not fit the device "
-         "memory that was free when it was opened); bed_prodVec, bed_cprodVec, counts / colstats / MAF / scaleBinom and the "
-         "`[` accessor are served out of core",
-         what, (double)b->m * (double)b->pitch / 1e9);
-}
-
-// ---- out-of-core handles: the resident slab image --------------------------------------------------------------------
-// One image of slab_cols variants lives on the handle (with its page-locked staging buffers) and is filled with one
-// slab of the file at a time.  It works on the HANDLE's stream: whatever the caller queues there — the kernels of a
-// one-shot entry point, the passes of a solve (svd.hip) — is ordered with the uploads without further ado.
-bsn_bed *slab_image(bsn_bed *b) {
-  BSN_HIP(hipSetDevice(b->device));
-  if (!b->slab_img) {
-    std::unique_ptr<bsn_bed, void (*)(bsn_bed *)> im(new bsn_bed(), bed_free);
-    image_alloc(im.get(), b->n, b->slab_cols);
-    (void)hipStreamDestroy(im->stream);
-    im->stream = b->stream;
-    im->stream_borrowed = true;
-    b->slab_img = im.release();
-  }
-  if (!b->slab_stage) b->slab_stage = new FileStage();
-  return b->slab_img;
-}
-int64_t slab_count(const bsn_bed *b) { return (b->m + b->slab_cols - 1) / b->slab_cols; }
-// slab sl of the file into the slab image (pread into pinned buffers, double-buffered against the DMA, recode, zero
-// pad rows); returns its number of variants, *j0 = its first variant
-void slab_upload_range(bsn_bed *b, int64_t j0, int64_t cnt) {
-  bsn_bed *img = slab_image(b);
-  if (j0 < 0 || cnt <= 0 || j0 + cnt > b->m || cnt > b->slab_cols)
-    fail("internal: variants %lld .. %lld into a slab image of %lld", (long long)j0, (long long)(j0 + cnt), (long long)b->slab_cols);
-  img->m = cnt;
-  img->na_cnt.clear();
-  img->forget_counts();
-  image_from_file(img, b->fd_file, 3 + j0 * b->n_byte, b->n_byte, (FileStage *)b->slab_stage);
-}
-int64_t slab_upload(bsn_bed *b, int64_t sl, int64_t *j0_out) {
-  const int64_t j0 = sl * b->slab_cols, cnt = std::min(b->slab_cols, b->m - j0);
-  if (cnt <= 0) fail("internal: slab %lld of %lld", (long long)sl, (long long)slab_count(b));
-  slab_upload_range(b, j0, cnt);
-  if (j0_out) *j0_out = j0;
-  return cnt;
-}
-
-// ---- out-of-core handles: the one-shot entry points over slabs of variants --------------------------------------
-// The selected variants are grouped by slab (order inside a slab = order in ind_col); `f(slab image, positions in
-// ind_col, local variant indices)` runs per non-empty slab on a resident image of that slab, in ascending slab order.
-namespace {
-struct SlabWalk {
-  bsn_bed *bed;
-  bsn_bed *img;        // the resident slab image: kept on the handle between calls, like its staging buffers
-  FileStage *stage;
-  SlabWalk(bsn_bed *b) : bed(b) {
-    img = slab_image(b);
-    stage = (FileStage *)b->slab_stage;
-  }
-  template <class F>
-  void run(const int64_t *ind_col, int64_t m, F f) {
-    const int64_t nslab = (bed->m + bed->slab_cols - 1) / bed->slab_cols;
-    std::vector<std::vector<int64_t>> pos((size_t)nslab);
-    for (int64_t p = 0; p < m; p++) {
-      const int64_t c = ind_col ? ind_col[p] : p;
-      if (c < 0 || c >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)c, (long long)bed->m);
-      pos[(size_t)(c / bed->slab_cols)].push_back(p);
-    }
-    std::vector<int64_t> local;
-    for (int64_t sl = 0; sl < nslab; sl++) {
-      const std::vector<int64_t> &P = pos[(size_t)sl];
-      if (P.empty()) continue;
-      const int64_t j0 = sl * bed->slab_cols;
-      slab_upload(bed, sl);
-      local.resize(P.size());
-      for (size_t k = 0; k < P.size(); k++) local[k] = (ind_col ? ind_col[P[k]] : P[k]) - j0;
-      f(img, P, local);
-    }
-  }
-};
-}  // namespace
-
-void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
-                 int64_t m, int32_t *res) {
-  if (bed->streamed()) {
-    SlabWalk W(bed);
-    std::vector<int32_t> part;
-    W.run(ind_col, m, [&](bsn_bed *sb, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
-      part.resize(4 * P.size());
-      counts_host(sb, ind_row, n, local.data(), (int64_t)local.size(), part.data());
-      for (size_t k = 0; k < P.size(); k++) std::memcpy(res + 4 * P[k], part.data() + 4 * k, 16);
-    });
-    return;
-  }
+// the same into a host 4 x m int32 array, from a resident image
+static void counts_resident(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                            int64_t m, int32_t *res) {
   // the counts as an earlier call left them (BSN_NO_COUNTS_CACHE=1: always count).  All samples in file order: the
   // handle's device-resident counts, which the solves feed and read too (bsn_bed::stats_cache); any other row
   // selection: the host copy of the last one
@@ -610,7 +149,7 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
   DevBuf<int32_t> d_counts;
   d_counts.ensure((size_t)4 * m);
   const bool device_cache = op.rows_identity && stats_cache_enabled(bed);
-  const StatsCols sel{op.cols_contig ? nullptr : ind_col, op.cols_contig ? nullptr : op.d_cols.p, op.col0, m};
+  const StatsCols sel{op.cols_contig ? nullptr : ind_col, op.cols(), op.col0, m};
   if (device_cache && use_cache && stats_cache_known(bed, sel)) {
     stats_cache_load(bed, sel, d_counts.p, bed->stream);
     copy_d2h(bed, res, d_counts.p, (size_t)4 * m * 4);
@@ -631,6 +170,18 @@ void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t 
     }
     for (int64_t j = 0; j < m; j++) std::memcpy(&cc.cnt[(size_t)4 * (ind_col ? ind_col[j] : j)], res + 4 * j, 16);
   }
+}
+
+// ... resident, or slab by slab of an out-of-core handle
+void counts_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                 int64_t m, int32_t *res) {
+  if (!bed->streamed()) return counts_resident(bed, ind_row, n, ind_col, m, res);
+  std::vector<int32_t> part;
+  slab_walk(bed, ind_col, m, [&](const SlabPart &s) {
+    part.resize((size_t)4 * s.P.size());
+    counts_resident(s.img, ind_row, n, s.local.data(), s.count(), part.data());
+    s.place(res, part.data(), 16);
+  });
 }
 
 // ---- counts of the codes per group of rows (bsn_bed_group_counts; the table stays on the device for popstat.hip) ----------
@@ -693,7 +244,7 @@ void group_counts_device(bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
   DevBuf<int32_t> d_rows, d_group, d_gsize;
   d_table.ensure((size_t)4 * G * m);
   auto upload = [&](bsn_bed *on) {
-    if (ind_row) copy_h2d(on, d_rows.ensure((size_t)n), rows.data(), (size_t)n * 4);
+    if (ind_row) upload_list(on, d_rows, rows);
     copy_h2d(on, d_group.ensure((size_t)n), group, (size_t)n * 4);
     copy_h2d(on, d_gsize.ensure((size_t)G), gsize.data(), (size_t)G * 4);
   };
@@ -701,21 +252,20 @@ void group_counts_device(bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
     // slab by slab, exactly as counts_host walks: a slab's table comes back to the host, the whole one goes up once
     std::vector<int32_t> table((size_t)4 * G * m), part;
     DevBuf<int32_t> d_part;
-    SlabWalk W(bed);
-    upload(W.img);
-    W.run(ind_col, m, [&](bsn_bed *sb, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
-      const int64_t m_slab = (int64_t)local.size();
+    bsn_bed *img = slab_image(bed);
+    upload(img);
+    slab_walk(bed, ind_col, m, [&](const SlabPart &s) {
+      const int64_t m_slab = s.count();
       bsn_op op;
-      fill_op(&op, sb, nullptr, sb->n, local.data(), m_slab, nullptr, nullptr, true);
+      fill_op(&op, s.img, nullptr, s.img->n, s.local.data(), m_slab, nullptr, nullptr, true);
       counts_grouped(&op, ind_row ? d_rows.p : nullptr, d_group.p, n, G, d_gsize.p, one_digit, d_part.ensure((size_t)4 * G * m_slab),
                      ms_out);
       part.resize((size_t)4 * G * m_slab);
-      copy_d2h(sb, part.data(), d_part.p, part.size() * 4);
-      for (size_t k = 0; k < P.size(); k++)
-        std::memcpy(table.data() + (size_t)4 * G * P[k], part.data() + (size_t)4 * G * k, (size_t)16 * G);
+      copy_d2h(s.img, part.data(), d_part.p, part.size() * 4);
+      s.place(table.data(), part.data(), (size_t)16 * G);
     });
-    copy_h2d(W.img, d_table.p, table.data(), table.size() * 4);
-    BSN_HIP(hipStreamSynchronize(W.img->stream));
+    copy_h2d(img, d_table.p, table.data(), table.size() * 4);
+    BSN_HIP(hipStreamSynchronize(img->stream));
     return;
   }
   upload(bed);
@@ -833,294 +383,10 @@ using namespace bsn;
 
 extern "C" {
 
-const char *bsn_last_error(void) { return g_err.c_str(); }
-int bsn_version(void) { return 100; }
-
-int bsn_device_count(int *count) {
-  return guarded([&] {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    *count = (e == hipSuccess) ? n : 0;
-  });
-}
-
-int bsn_set_device(int device) {
-  return guarded([&] {
-    require_gpu();
-    BSN_HIP(hipSetDevice(device));
-  });
-}
-
 int bsn_selftest(void) {
   return guarded([&] {
     require_gpu();
     selftest();
-  });
-}
-
-int bsn_bed_from_host(const uint8_t *payload, int64_t n, int64_t m, int64_t n_byte, bsn_bed **out) {
-  return guarded([&] {
-    require_gpu();
-    if (n_byte < (n + 3) / 4) fail("n or p does not match the dimensions of the file.");
-    std::unique_ptr<bsn_bed, void (*)(bsn_bed *)> b(new bsn_bed(), free_bed);
-    image_alloc(b.get(), n, m);
-    image_from_host(b.get(), payload, n_byte);
-    *out = b.release();
-  });
-}
-
-int bsn_bed_open(const char *path, int64_t n, int64_t m, bsn_bed **out) {
-  return guarded([&] {
-    // validation order and messages of src/bed-acc-xptr.cpp:14-35 (the reference maps the file;
-    // here it is read once into the device image, so the header is checked with a 3-byte read)
-    int fd = open(path, O_RDONLY);
-    if (fd < 0) fail("Error when mapping file:\n  %s.\n", strerror(errno));
-    struct Close {
-      int fd;
-      ~Close() { close(fd); }
-    } closer{fd};
-    struct stat st;
-    if (fstat(fd, &st) != 0) fail("Error when mapping file:\n  %s.\n", strerror(errno));
-    const size_t size = (size_t)st.st_size;
-    uint8_t f[3] = {0, 0, 0};
-    if (size == 0) fail("Error when mapping file:\n  %s.\n", strerror(EINVAL));  // mmap of an empty file
-    const ssize_t got = pread(fd, f, 3, 0);
-    if (got < 0) fail("Error when mapping file:\n  %s.\n", strerror(errno));
-    if (size < 3 || !(f[0] == 0x6C && f[1] == 0x1B)) fail("File is not a binary PED file.");
-    if (f[2] != 0x01) fail("Variant-major is the only mode supported.");
-    int64_t n_byte = (n + 3) / 4;
-    if (n <= 0 || m <= 0 || (size_t)(3 + n_byte * m) != size)
-      fail("n or p does not match the dimensions of the file.");
-    require_gpu();
-    std::unique_ptr<bsn_bed, void (*)(bsn_bed *)> b(new bsn_bed(), free_bed);
-    // does the image fit?  free device memory less 2 GB of working room, or BSN_IMAGE_BUDGET (bytes)
-    const int64_t pitch = round_up(n_byte, 256);
-    const double image_bytes = (double)(m + 64) * (double)pitch;
-    size_t free_b = 0, total_b = 0;
-    BSN_HIP(hipMemGetInfo(&free_b, &total_b));
-    double budget = (double)(free_b + dev_cache_held()) - 2e9;
-    const char *forced = getenv("BSN_IMAGE_BUDGET");
-    if (forced) budget = atof(forced);
-    // The resident image is tried first whenever it could fit at all: a device that other handles have filled to
-    // within the 2 GB of working room must not turn a small file into a streamed handle, which most entry points
-    // refuse.  Only an allocation that really fails — or a file beyond the budget — goes out of core.
-    bool resident = image_bytes <= budget;
-    if (!resident && !forced && image_bytes <= (double)(free_b + dev_cache_held())) resident = true;
-    if (resident) {
-      bool ok = true;
-      try {
-        image_alloc(b.get(), n, m);
-      } catch (const std::exception &) {
-        if (forced || image_bytes <= budget - 8e9) throw;   // (not a matter of room)
-        (void)hipGetLastError();
-        ok = false;
-        b.reset(new bsn_bed());
-      }
-      if (ok) {
-        image_from_file(b.get(), fd, 3, n_byte);
-        *out = b.release();
-        return;
-      }
-    }
-    // out-of-core: keep the file mapped, walk it in slabs (bsn_internal.hpp)
-    void *map = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-    if (map == MAP_FAILED) fail("Error when mapping file:\n  %s.\n", strerror(errno));
-    image_alloc(b.get(), n, 1);   // stream, events, geometry; no variants resident
-    (void)hipFree(b->d_img);
-    b->d_img = nullptr;
-    b->m = m;
-    b->map_base = map;
-    b->map_len = size;
-    b->h_map = (const uint8_t *)map + 3;
-    b->fd_file = dup(fd);
-    if (b->fd_file < 0) fail("Error when mapping file:\n  %s.\n", strerror(errno));
-    // one resident slab image, kept on the handle between calls (bsn_bed_release_workspace frees it): a slab of at most
-    // 16 GB — PCIe paces the walk, a larger slab buys nothing and would pin the device memory other handles need
-    b->slab_cols = std::max<int64_t>(64, (int64_t)(std::min(std::max(budget, 0.0), 16e9) / (double)pitch) / 64 * 64 - 64);
-    if (b->slab_cols > m) b->slab_cols = round_up(m, 64);
-    if (getenv("BSN_VERBOSE"))
-      std::fprintf(stderr, "[bsn] %s: image of %.1f GB does not fit (%.1f GB available): out-of-core handle, slabs of %lld variants\n",
-                   path, image_bytes / 1e9, budget / 1e9, (long long)b->slab_cols);
-    *out = b.release();
-  });
-}
-
-int bsn_bed_is_streamed(const bsn_bed *bed) { return bed->streamed() ? 1 : 0; }
-
-// FBM.code256 -> device image.  The 256 decoded values decide the image kind:
-//   all of them in {0, 1, 2, NA}          -> 2-bit image (CODE_012, CODE_IMPUTE_PRED, ...): every entry point
-//   on a grid v_off + v_step k, |k| <= 127 -> byte image (CODE_DOSAGE: 0.00 .. 2.00 by 0.01): colstats and
-//                                             the products (and what is built on them: PRS, SVD)
-//   anything else                          -> refused (there is no exact integer image of it)
-static void fbm_open(const uint8_t *bytes, int64_t n, int64_t m, int64_t ld, const double *code256, bsn_bed **out) {
-  require_gpu();
-  if (ld < n) fail("Incompatibility between dimensions.");
-  bool calls = true;
-  double vmin = 0, vmax = 0;
-  int nval = 0;
-  for (int c = 0; c < 256; c++) {
-    const double v = code256[c];
-    if (std::isnan(v)) continue;
-    if (!(v == 0.0 || v == 1.0 || v == 2.0)) calls = false;
-    if (nval == 0 || v < vmin) vmin = v;
-    if (nval == 0 || v > vmax) vmax = v;
-    nval++;
-  }
-  if (nval == 0) fail("'code256' holds no value");
-  uint8_t lut[256];
-  std::unique_ptr<bsn_bed, void (*)(bsn_bed *)> b(new bsn_bed(), free_bed);
-  if (calls) {
-    for (int c = 0; c < 256; c++) lut[c] = std::isnan(code256[c]) ? 3 : (uint8_t)code256[c];
-    image_alloc(b.get(), n, m, 2);
-    image_from_fbm(b.get(), bytes, ld, lut);
-    // FBMs of imputed data have no missing value: one count pass settles it for every later operator
-    std::vector<int32_t> cnt((size_t)4 * m);
-    counts_host(b.get(), nullptr, n, nullptr, m, cnt.data());
-  } else {
-    // smallest positive difference between two values as the step, mid-range as the offset; the grid is then
-    // SNAPPED to the range (step = range / number of steps): the raw difference of two rounded decimals, e.g.
-    // 0.00999999999999979 for CODE_DOSAGE, would bias every decoded value by up to 4e-14
-    double step = 0;
-    for (int a = 0; a < 256; a++)
-      for (int c = 0; c < 256; c++) {
-        const double d = code256[a] - code256[c];
-        if (d > 1e-12 * (std::fabs(vmax) + std::fabs(vmin) + 1) && (step == 0 || d < step)) step = d;
-      }
-    double off = vmin;
-    bool ok = step > 0 && (vmax - vmin) / step <= 254.5;
-    if (ok) {
-      const double nsteps = std::round((vmax - vmin) / step);
-      step = (vmax - vmin) / nsteps;
-      off = vmin + std::round(nsteps / 2.0) * step;
-    }
-    for (int c = 0; c < 256 && ok; c++) {
-      if (std::isnan(code256[c])) {
-        lut[c] = 0x80;
-        continue;
-      }
-      // values like 0.07 are not exactly k * 0.01 in binary: the decoded value must reproduce the table entry to
-      // a few units in the last place of the table's range
-      const double kr = std::round((code256[c] - off) / step);
-      // 16 units in the last place of the table's range: off + step * kr carries three roundings and the table was
-      // written by other arithmetic (i * 0.01, seq(0, 2, by = 0.01), a decimal parser ...) — one ulp of slack (round 3)
-      // sent such tables to the slow generic image for nothing; an entry really off the grid misses by ~step
-      if (kr < -127 || kr > 127 ||
-          std::fabs(off + step * kr - code256[c]) > 16 * 2.220446049250313e-16 * (std::fabs(vmax) + std::fabs(vmin) + step))
-        ok = false;
-      lut[c] = (uint8_t)(int8_t)kr;
-    }
-    if (!ok) {
-      // any other table: the FBM's own bytes + the table, served by the fp64 look-up kernels only
-      if (getenv("BSN_VERBOSE"))
-        std::fprintf(stderr, "[bsn] code256 is neither calls nor a regular grid of <= 255 steps: generic look-up image "
-                             "(colstats / prodVec / cprodVec only)\n");
-      for (int c = 0; c < 256; c++) lut[c] = (uint8_t)c;
-      image_alloc(b.get(), n, m, 8);
-      b->generic = true;
-      BSN_HIP(hipMalloc((void **)&b->d_lut, 256 * sizeof(double)));
-      BSN_HIP(hipMemcpy(b->d_lut, code256, 256 * sizeof(double), hipMemcpyHostToDevice));
-      image_from_fbm(b.get(), bytes, ld, lut);
-      // missing values: which codes are NaN, counted per variant on the host from the caller's bytes would
-      // cost a pass; the look-up kernels propagate NaN on their own, so only "some / none" is recorded
-      bool any_nan = false;
-      for (int c = 0; c < 256; c++) any_nan = any_nan || std::isnan(code256[c]);
-      if (!any_nan) b->na_cnt.assign((size_t)m, 0);
-      *out = b.release();
-      return;
-    }
-    image_alloc(b.get(), n, m, 8);
-    b->v_off = off;
-    b->v_step = step;
-    image_from_fbm(b.get(), bytes, ld, lut);
-    // which variants are complete (no missing value): the products then skip the missing-value plane
-    DevBuf<long long> d_st;
-    stats8(b.get(), nullptr, n, nullptr, 0, m, d_st.ensure((size_t)3 * m));
-    std::vector<long long> st((size_t)3 * m);
-    copy_d2h(b.get(), st.data(), d_st.p, st.size() * 8);
-    b->na_cnt.resize((size_t)m);
-    for (int64_t j = 0; j < m; j++) b->na_cnt[(size_t)j] = (int32_t)st[(size_t)(3 * j + 2)];
-  }
-  *out = b.release();
-}
-
-int bsn_bed_from_fbm(const uint8_t *bytes, int64_t n, int64_t m, int64_t ld, bsn_bed **out) {
-  return guarded([&] {
-    double code[256];
-    for (int c = 0; c < 256; c++) code[c] = c < 3 ? (double)c : std::numeric_limits<double>::quiet_NaN();
-    fbm_open(bytes, n, m, ld, code, out);  // CODE_012, R/bigSNP-class.R:7
-  });
-}
-
-int bsn_fbm_open(const uint8_t *bytes, int64_t n, int64_t m, int64_t ld, const double *code256, bsn_bed **out) {
-  return guarded([&] { fbm_open(bytes, n, m, ld, code256, out); });
-}
-
-int bsn_bed_bits(const bsn_bed *bed) { return bed->bits; }
-
-int64_t bsn_bed_na_known(const bsn_bed *bed) {
-  if ((int64_t)bed->na_cnt.size() != bed->m) return -1;
-  int64_t tot = 0;
-  for (int32_t c : bed->na_cnt) {
-    if (c < 0) return -1;
-    tot += c;
-  }
-  return tot;
-}
-
-int bsn_bed_synthetic(int64_t n, int64_t m, uint32_t seed, uint32_t npop, uint32_t na16,
-                      int64_t j_begin, bsn_bed **out) {
-  return guarded([&] {
-    require_gpu();
-    std::unique_ptr<bsn_bed, void (*)(bsn_bed *)> b(new bsn_bed(), free_bed);
-    image_alloc(b.get(), n, m);
-    image_generate(b.get(), seed, npop ? npop : 1, na16, j_begin);
-    if (na16 == 0) b->na_cnt.assign((size_t)m, 0);  // the generator draws no missing value then
-    *out = b.release();
-  });
-}
-
-int bsn_bed_close(bsn_bed *bed) {
-  return guarded([&] {
-    if (bed) {
-      (void)hipSetDevice(bed->device);
-      free_bed(bed);
-    }
-  });
-}
-
-int bsn_bed_tile(bsn_bed *bed, int *built) {
-  return guarded([&] {
-    BSN_HIP(hipSetDevice(bed->device));
-    const bool ok = image_tile(bed);
-    if (built) *built = ok ? 1 : 0;
-  });
-}
-
-// Names (demangled, without the argument list: rocprofv3's Kernel_Name up to the parenthesis) of the streaming
-// kernels the LAST profiled solve on this handle launched, one "kind=name" per line for the kinds cprod / prod /
-// cprod_stats / warm.  Lets a measurement record be tied to the kernels of the running build.
-int bsn_bed_streaming_kernels(bsn_bed *bed, char *buf, int64_t len) {
-  return guarded([&] {
-    if (!buf || len < 1) fail("bsn_bed_streaming_kernels: no buffer");
-    buf[0] = 0;
-    if (bed->last_solve_on_sub && bed->sub) bed = bed->sub;   // the last solve ran on the compacted copy: its operator lives there
-    if (!bed->svd_op) return;
-    static const char *kinds[kProfKinds] = {"cprod", "prod", "cprod_stats", "warm", "cprod_wide", "prod_wide"};
-    std::string out;
-    for (int k = 0; k < kProfKinds; k++) {
-      const void *fn = bed->svd_op->prof_kernel[k];
-      if (!fn) continue;
-      const char *mangled = hipKernelNameRefByPtr(fn, bed->stream);
-      if (!mangled) continue;
-      int status = 1;
-      char *dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
-      std::string name = (status == 0 && dem) ? dem : mangled;
-      free(dem);
-      const size_t par = name.find('(');
-      if (par != std::string::npos) name.resize(par);
-      out += std::string(kinds[k]) + "=" + name + "\n";
-    }
-    snprintf(buf, (size_t)len, "%s", out.c_str());
   });
 }
 
@@ -1139,68 +405,6 @@ int bsn_op_last_kernel(bsn_op *op, char *buf, int64_t len) {
     const size_t par = name.find('(');
     if (par != std::string::npos) name.resize(par);
     snprintf(buf, (size_t)len, "%s", name.c_str());
-  });
-}
-
-int bsn_bed_sample_major(bsn_bed *bed, int *built) {
-  return guarded([&] {
-    BSN_HIP(hipSetDevice(bed->device));
-    const bool ok = image_smaj(bed);
-    if (built) *built = ok ? 1 : 0;
-  });
-}
-
-int bsn_bed_release_workspace(bsn_bed *bed) {
-  return guarded([&] {
-    BSN_HIP(hipSetDevice(bed->device));
-    BSN_HIP(hipStreamSynchronize(bed->stream));
-    bed->svd_op.reset();
-    bed->svd_ws.reset();
-    if (bed->d_tiled) {  // the streaming-layout copy is rebuilt by the next solve if there is room again
-      BSN_HIP(hipFree(bed->d_tiled));
-      bed->d_tiled = nullptr;
-    }
-    bed->tiled_tried = false;
-    image_smaj_wait(bed);   // (a build in flight is adopted first, then freed with the rest)
-    if (bed->d_smaj) {  // likewise the sample-major copy
-      BSN_HIP(hipFree(bed->d_smaj));
-      bed->d_smaj = nullptr;
-    }
-    bed->smaj_tried = false;
-    bed->smaj_cap = 0;
-    if (bed->sub) {     // the compacted sub-image of the last solve over a column list (and everything IT holds)
-      bed_free(bed->sub);
-      bed->sub = nullptr;
-      bed->sub_key = 0;
-      bed->sub_cols.clear();
-      bed->sub_rows.clear();
-      bed->last_solve_on_sub = false;
-    }
-    bed->stats_cache.release();   // the code counts over all samples (16 B per variant): counted again when next needed
-    if (bed->slab_img) {   // out-of-core handle: the resident slab image and its page-locked staging buffers
-      bed_free(bed->slab_img);
-      bed->slab_img = nullptr;
-    }
-    if (bed->slab_stage) {
-      delete (bsn::FileStage *)bed->slab_stage;
-      bed->slab_stage = nullptr;
-    }
-    dev_cache_flush();
-  });
-}
-
-int64_t bsn_bed_nrow(const bsn_bed *bed) { return bed->n; }
-int64_t bsn_bed_ncol(const bsn_bed *bed) { return bed->m; }
-int64_t bsn_bed_bytes(const bsn_bed *bed) { return bed->pitch * bed->m; }
-
-int bsn_bed_download(bsn_bed *bed, uint8_t *payload_out) {
-  return guarded([&] {
-    BSN_HIP(hipSetDevice(bed->device));
-    if (bed->streamed()) {   // the payload is the mapped file itself
-      std::memcpy(payload_out, bed->h_map, (size_t)bed->n_byte * (size_t)bed->m);
-      return;
-    }
-    image_download(bed, payload_out);
   });
 }
 
@@ -1249,38 +453,9 @@ int bsn_op_sync(bsn_op *op) {
 }
 
 // ---- .Call replacements ------------------------------------------------------------
-static void matvec_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
-                        int64_t m, const double *center, const double *scale, const double *x,
-                        double *out, bool transpose, bsn_comm *comm = nullptr) {
-  if (bed->streamed()) {
-    // out of core: A~' x slab by slab is the result slab by slab; A~ x is the sum of the slabs' products (added on the
-    // host in ascending slab order: deterministic)
-    if (comm) fail("sharded products are not available for an out-of-core handle");
-    SlabWalk W(bed);
-    std::vector<double> ce, sc, xs, part;
-    if (!transpose) std::fill(out, out + n, 0.0);
-    W.run(ind_col, m, [&](bsn_bed *sb, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
-      const int64_t k = (int64_t)P.size();
-      if (center) { ce.resize((size_t)k); for (int64_t t = 0; t < k; t++) ce[(size_t)t] = center[P[(size_t)t]]; }
-      if (scale) { sc.resize((size_t)k); for (int64_t t = 0; t < k; t++) sc[(size_t)t] = scale[P[(size_t)t]]; }
-      if (transpose) {
-        part.resize((size_t)k);
-        matvec_host(sb, ind_row, n, local.data(), k, center ? ce.data() : nullptr, scale ? sc.data() : nullptr, x,
-                    part.data(), true);
-        BSN_HIP(hipStreamSynchronize(sb->stream));
-        for (int64_t t = 0; t < k; t++) out[P[(size_t)t]] = part[(size_t)t];
-      } else {
-        xs.resize((size_t)k);
-        for (int64_t t = 0; t < k; t++) xs[(size_t)t] = x[P[(size_t)t]];
-        part.resize((size_t)n);
-        matvec_host(sb, ind_row, n, local.data(), k, center ? ce.data() : nullptr, scale ? sc.data() : nullptr, xs.data(),
-                    part.data(), false);
-        BSN_HIP(hipStreamSynchronize(sb->stream));
-        for (int64_t i = 0; i < n; i++) out[i] += part[(size_t)i];
-      }
-    });
-    return;
-  }
+static void matvec_resident(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                            int64_t m, const double *center, const double *scale, const double *x,
+                            double *out, bool transpose, bsn_comm *comm = nullptr) {
   bsn_op op;
   // A~' x needs centre / scale only in its finalize kernel: their upload is queued on the second stream and runs
   // beside the streaming kernel (2-bit image; the byte and look-up kernels read them earlier)
@@ -1301,7 +476,7 @@ static void matvec_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const i
   copy_h2d(bed, d_in.ensure((size_t)nin), x, (size_t)nin * 8);
   d_out.ensure((size_t)nout);
   if (bed->generic) {   // arbitrary decode table: fp64 look-up kernels
-    const int32_t *rows = op.rows_identity ? nullptr : op.d_rows.p, *cols = op.cols_contig ? nullptr : op.d_cols.p;
+    const int32_t *rows = op.rows(), *cols = op.cols();
     if (comm) fail("sharded products are not available for a generic decode table");
     if (transpose)
       lut_cprod(bed, rows, n, cols, op.col0, m, center ? op.d_center.p : nullptr, scale ? op.d_scale.p : nullptr,
@@ -1322,6 +497,26 @@ static void matvec_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const i
     comm_allreduce_sum(comm, d_out.p, nout, bed->stream);
   }
   copy_d2h(bed, out, d_out.p, (size_t)nout * 8);
+}
+
+static void matvec_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                        int64_t m, const double *center, const double *scale, const double *x,
+                        double *out, bool transpose, bsn_comm *comm = nullptr) {
+  if (!bed->streamed()) return matvec_resident(bed, ind_row, n, ind_col, m, center, scale, x, out, transpose, comm);
+  // out of core: A~' x slab by slab is the result slab by slab; A~ x is the sum of the slabs' products (added on the
+  // host in ascending slab order: deterministic)
+  if (comm) fail("sharded products are not available for an out-of-core handle");
+  std::vector<double> ce, sc, xs, part;
+  if (!transpose) std::fill(out, out + n, 0.0);
+  slab_walk(bed, ind_col, m, [&](const SlabPart &s) {
+    part.resize((size_t)(transpose ? s.count() : n));
+    matvec_resident(s.img, ind_row, n, s.local.data(), s.count(), s.gather(center, ce), s.gather(scale, sc),
+                    transpose ? x : s.gather(x, xs), part.data(), transpose);
+    BSN_HIP(hipStreamSynchronize(s.img->stream));
+    if (transpose) s.place(out, part.data(), 8);
+    else
+      for (int64_t i = 0; i < n; i++) out[i] += part[(size_t)i];
+  });
 }
 
 int bsn_bed_prodvec(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
@@ -1399,8 +594,7 @@ int bsn_snp_colstats(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int6
       bsn_op op;
       fill_op(&op, bed, ind_row, n, ind_col, m, nullptr, nullptr);
       DevBuf<double> d_st;
-      lut_colstats(bed, op.rows_identity ? nullptr : op.d_rows.p, n, op.cols_contig ? nullptr : op.d_cols.p, op.col0, m,
-                   d_st.ensure((size_t)2 * m));
+      lut_colstats(bed, op.rows(), n, op.cols(), op.col0, m, d_st.ensure((size_t)2 * m));
       std::vector<double> st((size_t)2 * m);
       copy_d2h(bed, st.data(), d_st.p, st.size() * 8);
       for (int64_t j = 0; j < m; j++) {
@@ -1413,8 +607,7 @@ int bsn_snp_colstats(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int6
       bsn_op op;
       fill_op(&op, bed, ind_row, n, ind_col, m, nullptr, nullptr);
       DevBuf<long long> d_st;
-      stats8(bed, op.rows_identity ? nullptr : op.d_rows.p, n, op.cols_contig ? nullptr : op.d_cols.p, op.col0, m,
-             d_st.ensure((size_t)3 * m));
+      stats8(bed, op.rows(), n, op.cols(), op.col0, m, d_st.ensure((size_t)3 * m));
       std::vector<long long> st((size_t)3 * m);
       copy_d2h(bed, st.data(), d_st.p, st.size() * 8);
       const double a = bed->v_off, h = bed->v_step;
@@ -1441,37 +634,13 @@ int bsn_snp_colstats(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int6
   });
 }
 
-static void read_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
-                      int64_t m, const double *center, const double *scale, int32_t na_val,
-                      int32_t *out_i, double *out_d) {
-  if (n <= 0 || m <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
-  BSN_HIP(hipSetDevice(bed->device));
-  if (bed->streamed()) {   // out of core: the columns of every slab, placed where ind.col has them
-    SlabWalk W(bed);
-    std::vector<int32_t> pi;
-    std::vector<double> pd, ce, sc;
-    W.run(ind_col, m, [&](bsn_bed *sb, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
-      const int64_t k = (int64_t)P.size();
-      if (center) { ce.resize((size_t)k); for (int64_t t = 0; t < k; t++) ce[(size_t)t] = center[P[(size_t)t]]; }
-      if (scale) { sc.resize((size_t)k); for (int64_t t = 0; t < k; t++) sc[(size_t)t] = scale[P[(size_t)t]]; }
-      if (out_i) pi.resize((size_t)(n * k));
-      if (out_d) pd.resize((size_t)(n * k));
-      read_host(sb, ind_row, n, local.data(), k, center ? ce.data() : nullptr, scale ? sc.data() : nullptr, na_val,
-                out_i ? pi.data() : nullptr, out_d ? pd.data() : nullptr);
-      BSN_HIP(hipStreamSynchronize(sb->stream));
-      for (int64_t t = 0; t < k; t++) {
-        if (out_i) std::memcpy(out_i + P[(size_t)t] * n, pi.data() + t * n, (size_t)n * 4);
-        if (out_d) std::memcpy(out_d + P[(size_t)t] * n, pd.data() + t * n, (size_t)n * 8);
-      }
-    });
-    return;
-  }
-  auto r = to_i32(ind_row, n, bed->n, "ind.row");
-  auto c = to_i32(ind_col, m, bed->m, "ind.col");
+static void read_resident(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                          int64_t m, const double *center, const double *scale, int32_t na_val,
+                          int32_t *out_i, double *out_d) {
   DevBuf<int32_t> d_r, d_c, d_oi;
   DevBuf<double> d_ce, d_sc, d_od;
-  copy_h2d(bed, d_r.ensure((size_t)n), r.data(), (size_t)n * 4);
-  copy_h2d(bed, d_c.ensure((size_t)m), c.data(), (size_t)m * 4);
+  upload_list(bed, d_r, to_i32(ind_row, n, bed->n, "ind.row"));
+  upload_list(bed, d_c, to_i32(ind_col, m, bed->m, "ind.col"));
   if (out_d) {
     copy_h2d(bed, d_ce.ensure((size_t)m), center, (size_t)m * 8);
     copy_h2d(bed, d_sc.ensure((size_t)m), scale, (size_t)m * 8);
@@ -1485,6 +654,25 @@ static void read_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int
     copy_d2h(bed, out_d, d_od.p, (size_t)n * m * 8);
   else
     copy_d2h(bed, out_i, d_oi.p, (size_t)n * m * 4);
+}
+
+static void read_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                      int64_t m, const double *center, const double *scale, int32_t na_val,
+                      int32_t *out_i, double *out_d) {
+  if (n <= 0 || m <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
+  BSN_HIP(hipSetDevice(bed->device));
+  if (!bed->streamed()) return read_resident(bed, ind_row, n, ind_col, m, center, scale, na_val, out_i, out_d);
+  // out of core: the columns of every slab, placed where ind.col has them
+  std::vector<uint8_t> part;
+  std::vector<double> ce, sc;
+  const size_t col_bytes = (size_t)n * (out_d ? 8 : 4);
+  slab_walk(bed, ind_col, m, [&](const SlabPart &s) {
+    part.resize(col_bytes * (size_t)s.count());
+    read_resident(s.img, ind_row, n, s.local.data(), s.count(), s.gather(center, ce), s.gather(scale, sc), na_val,
+                  out_d ? nullptr : (int32_t *)part.data(), out_d ? (double *)part.data() : nullptr);
+    BSN_HIP(hipStreamSynchronize(s.img->stream));
+    s.place(out_d ? (void *)out_d : (void *)out_i, part.data(), col_bytes);
+  });
 }
 
 int bsn_bed_read(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
@@ -1656,41 +844,12 @@ int bsn_snp_grid_prs(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int6
   });
 }
 
-static void convert_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
-                         int64_t m, uint8_t *out, bool packed) {
-  if (n <= 0 || m <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
-  BSN_HIP(hipSetDevice(bed->device));
-  if (bed->streamed()) {
-    // (round 6) out of core: a column of the result depends on ONE variant, so the selected variants are served slab by
-    // slab of the file (the reference maps the file and walks it: src/read-plink.cpp:61-80, src/write-plink.cpp:13-52);
-    // every slab's columns go to their places in the caller's array — byte-identical to the resident conversion
-    auto r = to_i32(ind_row, n, bed->n, "ind.row");
-    const size_t col_bytes = packed ? (size_t)((n + 3) / 4) : (size_t)n;
-    SlabWalk walk(bed);
-    DevBuf<int32_t> d_r, d_c;
-    DevBuf<uint8_t> d_o;
-    std::vector<uint8_t> h_o;
-    copy_h2d(bed, d_r.ensure((size_t)n), r.data(), (size_t)n * 4);
-    walk.run(ind_col, m, [&](bsn_bed *img, const std::vector<int64_t> &P, const std::vector<int64_t> &local) {
-      const int64_t ml = (int64_t)P.size();
-      auto c = to_i32(local.data(), ml, img->m, "ind.col");
-      copy_h2d(bed, d_c.ensure((size_t)ml), c.data(), (size_t)ml * 4);
-      d_o.ensure(col_bytes * (size_t)ml);
-      if (packed) subset_pack(img, d_r.p, n, d_c.p, ml, d_o.p);
-      else to_bytes(img, d_r.p, n, d_c.p, ml, d_o.p);
-      h_o.resize(col_bytes * (size_t)ml);
-      copy_d2h(bed, h_o.data(), d_o.p, h_o.size());
-      BSN_HIP(hipStreamSynchronize(bed->stream));
-      for (int64_t t = 0; t < ml; t++) std::memcpy(out + (size_t)P[(size_t)t] * col_bytes, h_o.data() + (size_t)t * col_bytes, col_bytes);
-    });
-    return;
-  }
-  auto r = to_i32(ind_row, n, bed->n, "ind.row");
-  auto c = to_i32(ind_col, m, bed->m, "ind.col");
+static void convert_resident(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                             int64_t m, uint8_t *out, bool packed) {
   DevBuf<int32_t> d_r, d_c;
   DevBuf<uint8_t> d_o;
-  copy_h2d(bed, d_r.ensure((size_t)n), r.data(), (size_t)n * 4);
-  copy_h2d(bed, d_c.ensure((size_t)m), c.data(), (size_t)m * 4);
+  upload_list(bed, d_r, to_i32(ind_row, n, bed->n, "ind.row"));
+  upload_list(bed, d_c, to_i32(ind_col, m, bed->m, "ind.col"));
   const size_t bytes = packed ? (size_t)((n + 3) / 4) * m : (size_t)n * m;
   d_o.ensure(bytes);
   if (packed)
@@ -1699,6 +858,34 @@ static void convert_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const 
     to_bytes(bed, d_r.p, n, d_c.p, m, d_o.p);
   copy_d2h(bed, out, d_o.p, bytes);
   BSN_HIP(hipStreamSynchronize(bed->stream));
+}
+
+static void convert_host(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
+                         int64_t m, uint8_t *out, bool packed) {
+  if (n <= 0 || m <= 0) fail("'ind.row' and 'ind.col' can't be empty.");
+  BSN_HIP(hipSetDevice(bed->device));
+  if (!bed->streamed()) return convert_resident(bed, ind_row, n, ind_col, m, out, packed);
+  // (round 6) out of core: a column of the result depends on ONE variant, so the selected variants are served slab by
+  // slab of the file (the reference maps the file and walks it: src/read-plink.cpp:61-80, src/write-plink.cpp:13-52);
+  // every slab's columns go to their places in the caller's array — byte-identical to the resident conversion.  The row
+  // list goes up once and every transfer runs through the HANDLE's staging buffers, so the slabs do not call the
+  // resident body
+  const size_t col_bytes = packed ? (size_t)((n + 3) / 4) : (size_t)n;
+  DevBuf<int32_t> d_r, d_c;
+  DevBuf<uint8_t> d_o;
+  std::vector<uint8_t> h_o;
+  upload_list(bed, d_r, to_i32(ind_row, n, bed->n, "ind.row"));
+  slab_walk(bed, ind_col, m, [&](const SlabPart &s) {
+    const int64_t ml = s.count();
+    upload_list(bed, d_c, to_i32(s.local.data(), ml, s.img->m, "ind.col"));
+    d_o.ensure(col_bytes * (size_t)ml);
+    if (packed) subset_pack(s.img, d_r.p, n, d_c.p, ml, d_o.p);
+    else to_bytes(s.img, d_r.p, n, d_c.p, ml, d_o.p);
+    h_o.resize(col_bytes * (size_t)ml);
+    copy_d2h(bed, h_o.data(), d_o.p, h_o.size());
+    BSN_HIP(hipStreamSynchronize(bed->stream));
+    s.place(out, h_o.data(), col_bytes);
+  });
 }
 
 int bsn_bed_to_fbm(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
@@ -1713,16 +900,12 @@ int bsn_bed_readbina(bsn_bed *bed, const uint8_t *tab, uint8_t *out) {
     DevBuf<uint8_t> d_tab, d_o;
     copy_h2d(bed, d_tab.ensure(1024), tab, 1024);
     if (bed->streamed()) {   // (round 6) out of core: slab by slab of the file, each slab's n x cnt bytes to its place
-      const int64_t nslab = slab_count(bed);
-      for (int64_t sl = 0; sl < nslab; sl++) {
-        int64_t j0 = 0;
-        const int64_t cnt = slab_upload(bed, sl, &j0);
-        bsn_bed *img = slab_image(bed);
-        const size_t bytes = (size_t)bed->n * (size_t)cnt;
-        readbina_bytes(img, d_tab.p, d_o.ensure(bytes));
-        copy_d2h(bed, out + (size_t)j0 * (size_t)bed->n, d_o.p, bytes);
+      slab_walk(bed, nullptr, bed->m, [&](const SlabPart &s) {   // (every variant: a slab's positions are one run)
+        const size_t bytes = (size_t)bed->n * (size_t)s.count();
+        readbina_bytes(s.img, d_tab.p, d_o.ensure(bytes));
+        copy_d2h(bed, out + (size_t)s.P[0] * (size_t)bed->n, d_o.p, bytes);
         BSN_HIP(hipStreamSynchronize(bed->stream));
-      }
+      });
       return;
     }
     const size_t bytes = (size_t)bed->n * (size_t)bed->m;
@@ -1735,47 +918,6 @@ int bsn_bed_readbina(bsn_bed *bed, const uint8_t *tab, uint8_t *out) {
 int bsn_bed_subset_payload(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
                            int64_t m, uint8_t *payload_out) {
   return guarded([&] { convert_host(bed, ind_row, n, ind_col, m, payload_out, true); });
-}
-
-// ---- helpers ---------------------------------------------------------------------------
-int bsn_malloc(void **d_ptr, int64_t bytes) {
-  return guarded([&] {
-    require_gpu();
-    BSN_HIP(hipMalloc(d_ptr, (size_t)bytes));
-  });
-}
-int bsn_free(void *d_ptr) {
-  return guarded([&] { BSN_HIP(hipFree(d_ptr)); });
-}
-int bsn_host_alloc(void **h_ptr, int64_t bytes) {
-  return guarded([&] {
-    require_gpu();
-    BSN_HIP(hipHostMalloc(h_ptr, (size_t)bytes, hipHostMallocDefault));
-  });
-}
-int bsn_host_free(void *h_ptr) {
-  return guarded([&] { BSN_HIP(hipHostFree(h_ptr)); });
-}
-int bsn_memcpy_h2d(void *d_dst, const void *src, int64_t bytes) {
-  return guarded([&] { BSN_HIP(hipMemcpy(d_dst, src, (size_t)bytes, hipMemcpyHostToDevice)); });
-}
-int bsn_memcpy_d2h(void *dst, const void *d_src, int64_t bytes) {
-  return guarded([&] { BSN_HIP(hipMemcpy(dst, d_src, (size_t)bytes, hipMemcpyDeviceToHost)); });
-}
-int bsn_device_sync(void) {
-  return guarded([&] { BSN_HIP(hipDeviceSynchronize()); });
-}
-int bsn_timer_start(bsn_bed *bed) {
-  return guarded([&] { BSN_HIP(hipEventRecord(bed->ev0, bed->stream)); });
-}
-int bsn_timer_stop(bsn_bed *bed, double *ms) {
-  return guarded([&] {
-    BSN_HIP(hipEventRecord(bed->ev1, bed->stream));
-    BSN_HIP(hipEventSynchronize(bed->ev1));
-    float t = 0;
-    BSN_HIP(hipEventElapsedTime(&t, bed->ev0, bed->ev1));
-    *ms = t;
-  });
 }
 
 }  // extern "C"

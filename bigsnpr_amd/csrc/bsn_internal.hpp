@@ -35,7 +35,7 @@ struct Error : std::runtime_error {
 };
 void set_error(const char *msg);
 [[noreturn]] void fail(const char *fmt, ...);
-void require_gpu();   // api.hip: fails ("no CPU fallback") without a HIP device
+void require_gpu();   // runtime.hip: fails ("no CPU fallback") without a HIP device
 
 #define BSN_HIP(expr)                                                             \
   do {                                                                            \
@@ -63,7 +63,7 @@ int guarded(F &&f) {
 }
 
 // ---- device buffer ------------------------------------------------------------
-// Work buffers come from a small per-device cache of released blocks (api.hip): a one-shot entry such
+// Work buffers come from a small per-device cache of released blocks (runtime.hip): a one-shot entry such
 // as bsn_bed_prodvec needs about ten of them, and hipMalloc / hipFree pairs cost more than its kernel
 // on a matrix of a few GB.  A release keeps hipFree's ordering (the device is idle when the block
 // changes hands); blocks above kDevCacheMaxBlock bypass the cache.
@@ -98,6 +98,30 @@ struct DevBuf {
       n = count;
     }
     return p;
+  }
+};
+
+// ---- timing events of one call ---------------------------------------------------
+// N HIP events that live as long as the object: mark(i, stream) records event i, ms(a, b) is the device time between
+// two marks (both have completed: the caller synchronised the stream, or event b itself).  What the *_last_ms entries
+// report comes from these.
+template <int N>
+struct EventMarks {
+  hipEvent_t e[N] = {};
+  EventMarks() {
+    for (auto &x : e) BSN_HIP(hipEventCreate(&x));
+  }
+  ~EventMarks() {
+    for (auto x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  EventMarks(const EventMarks &) = delete;
+  EventMarks &operator=(const EventMarks &) = delete;
+  void mark(int i, hipStream_t st) { BSN_HIP(hipEventRecord(e[i], st)); }
+  double ms(int a, int b) const {
+    float t = 0.f;
+    BSN_HIP(hipEventElapsedTime(&t, e[a], e[b]));
+    return (double)t;
   }
 };
 
@@ -195,6 +219,9 @@ struct bsn_op {
   }
   bsn::DevBuf<int32_t> d_rows;   // n (gather list) when !rows_identity
   bsn::DevBuf<int32_t> d_cols;   // m_pad (padded by repeating a valid column)
+  // the sub-view as the kernels take it: the device list, or NULL for all rows in file order / the run col0 .. col0 + m - 1
+  const int32_t *rows() const { return rows_identity ? nullptr : d_rows.p; }
+  const int32_t *cols() const { return cols_contig ? nullptr : d_cols.p; }
   bsn::DevBuf<double> d_center, d_scale;  // m
   // workspaces (grow-only)
   bsn::DevBuf<double> d_xfull;   // scattered / padded input panel
@@ -255,7 +282,7 @@ struct bsn_bed {
   size_t map_len = 0;
   int64_t slab_cols = 0;
   int fd_file = -1;                 // the open file: slabs are read through the pinned double-buffered upload of image_from_file
-  bsn_bed *slab_img = nullptr;      // the resident slab image and its staging buffers, kept between calls (api.hip, SlabWalk)
+  bsn_bed *slab_img = nullptr;      // the resident slab image and its staging buffers, kept between calls (handle.hip, slab_walk)
   void *slab_stage = nullptr;       // bsn::FileStage
   bool streamed() const { return d_img == nullptr && h_map != nullptr; }
   uint8_t *d_smaj = nullptr;
@@ -365,8 +392,8 @@ namespace bsn {
 
 // image.hip
 void image_alloc(bsn_bed *b, int64_t n, int64_t m, int bits = 2);
-void stage_init(bsn_bed *b);   // api.hip: the two page-locked staging buffers of copy_h2d / copy_d2h (made with a large image, else on first use)
-void bed_free(bsn_bed *b);  // api.hip: everything a handle owns
+void stage_init(bsn_bed *b);   // runtime.hip: the two page-locked staging buffers of copy_h2d / copy_d2h (made with a large image, else on first use)
+void bed_free(bsn_bed *b);  // handle.hip: everything a handle owns
 // a new handle holding the sub-matrix [ind_row, ind_col] (rows in list order, repeats allowed), same coding
 // `reuse`: a handle made by an earlier call whose allocation holds the new sub-matrix (same number of samples, at
 // least m variants): gathered into in place, its sample-major copy rebuilt if it has one
@@ -443,7 +470,7 @@ void readbina_bytes(bsn_bed *b, const uint8_t *d_tab, uint8_t *d_out);
 void subset_pack(bsn_bed *b, const int32_t *d_rows, int64_t n, const int32_t *d_cols, int64_t m,
                  uint8_t *d_out);
 
-// api.hip: transfers between caller memory (pageable) and the device, staged through the handle's two
+// runtime.hip: transfers between caller memory (pageable) and the device, staged through the handle's two
 // pinned buffers in 32-MB pieces (host copy of piece k+1, on a few threads, overlaps the DMA of piece k);
 // synchronous.
 // The runtime's own handling of pageable buffers was measured to leave every later stream
@@ -458,12 +485,26 @@ bool host_is_pinned(const void *p);   // the runtime knows `p` as page-locked ho
 void fill_op(bsn_op *op, bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
              int64_t m, const double *center, const double *scale, bool defer_scale = false,
              bool allow_streamed = false);
-// api.hip: the resident slab image of an out-of-core handle (on the handle's stream), the number of slabs, and the
+// handle.hip: the resident slab image of an out-of-core handle (on the handle's stream), the number of slabs, and the
 // upload of one slab into it (returns its number of variants)
 bsn_bed *slab_image(bsn_bed *b);
 int64_t slab_count(const bsn_bed *b);
 int64_t slab_upload(bsn_bed *b, int64_t sl, int64_t *j0_out = nullptr);
 void slab_upload_range(bsn_bed *b, int64_t j0, int64_t cnt);   // any run of at most slab_cols variants
+// handle.hip: the one-shot entry points of an out-of-core handle.  slab_walk groups the selected variants (ind_col, NULL =
+// the first m) by slab, uploads every non-empty slab in ascending order and hands `f` the slab's part of the selection:
+// a resident body runs on `img` over the variants `local`, its per-variant inputs and outputs sit at the positions P.
+struct SlabPart {
+  bsn_bed *img;                        // the resident slab image, on the handle's stream
+  const std::vector<int64_t> &P;       // positions in ind_col of the slab's variants, in the order of ind_col
+  const std::vector<int64_t> &local;   // the same variants as indices into the slab image
+  int64_t count() const { return (int64_t)P.size(); }
+  // src[P[k]] for every k, in buf; NULL for a NULL src (the entry's default)
+  const double *gather(const double *src, std::vector<double> &buf) const;
+  // column k of `part` to column P[k] of `out`, col_bytes each
+  void place(void *out, const void *part, size_t col_bytes) const;
+};
+void slab_walk(bsn_bed *bed, const int64_t *ind_col, int64_t m, const std::function<void(const SlabPart &)> &f);
 
 // comm.hip: RCCL collectives on device buffers of doubles, enqueued on `st`
 // (exchange timing) a pair of events around `what` on `st`, filed under class cls; no-ops unless c->timing
@@ -532,7 +573,7 @@ struct RoctxRange {
   RoctxRange(const RoctxRange &) = delete;
   RoctxRange &operator=(const RoctxRange &) = delete;
 };
-// api.hip: fails with the reason when `b` is an out-of-core handle (bsn_bed::streamed)
+// handle.hip: fails with the reason when `b` is an out-of-core handle (bsn_bed::streamed)
 void require_resident(const bsn_bed *b, const char *what);
 void prof_begin(bsn_op *op, int kind, bool more = false);
 void prof_end(bsn_op *op);

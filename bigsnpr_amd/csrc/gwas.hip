@@ -287,8 +287,7 @@ int bsn_univ_linreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64
       counts_device(&op, ind_row, n, d_counts.ensure((size_t)4 * m));
       op_cprod_raw(&op, d_X.p, n, nvec, d_Z.p, d_Q.ensure((size_t)m * nvec), m);
     } else {
-      stats8(bed, op.rows_identity ? nullptr : op.d_rows.p, n, op.cols_contig ? nullptr : op.d_cols.p, op.col0, m,
-             d_st.ensure((size_t)3 * m));
+      stats8(bed, op.rows(), n, op.cols(), op.col0, m, d_st.ensure((size_t)3 * m));
       op_cprod(&op, d_X.p, n, nvec, d_Z.p, m);
     }
     d_out.ensure((size_t)2 * m);
@@ -327,8 +326,8 @@ int bsn_univ_logreg(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64
     a.bits = bed->bits;
     a.v_off = bed->v_off;
     a.v_step = bed->v_step;
-    a.rows = op.rows_identity ? nullptr : op.d_rows.p;
-    a.cols = op.cols_contig ? nullptr : op.d_cols.p;
+    a.rows = op.rows();
+    a.cols = op.cols();
     a.col0 = op.col0;
     a.n = n;
     a.covar = d_cov.p;

@@ -25,25 +25,6 @@ constexpr int64_t kBytesGroups = 1024;     // FBM bytes: workgroups over the sam
 // device milliseconds of the last call of this process (bsn_impute_last_ms): counts + rule, rewrite, FBM bytes
 double g_last_ms[3] = {0.0, 0.0, 0.0};
 
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  EventPair() {
-    BSN_HIP(hipEventCreate(&a));
-    BSN_HIP(hipEventCreate(&b));
-  }
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  EventPair(const EventPair &) = delete;
-  EventPair &operator=(const EventPair &) = delete;
-  double ms() const {   // (both events have completed: the caller synchronised the stream)
-    float t = 0.f;
-    BSN_HIP(hipEventElapsedTime(&t, a, b));
-    return (double)t;
-  }
-};
-
 // ---- per variant: counts -> value -------------------------------------------------------------------------------------
 // counts: 4 x m (codes 0, 1, 2, missing) over all n samples.  n_all receives the number of variants without a call.
 __global__ void k_impute_rule(const int32_t *__restrict__ counts, int64_t m, int64_t n, int method, int32_t *val,
@@ -198,9 +179,9 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
   DevBuf<double> d_af;
   DevBuf<unsigned long long> d_nall;
   d_counts.ensure((size_t)4 * m);
-  EventPair ev_rule, ev_write;
+  EventMarks<2> ev_rule, ev_write;
   g_last_ms[0] = g_last_ms[1] = g_last_ms[2] = 0.0;
-  BSN_HIP(hipEventRecord(ev_rule.a, st));
+  ev_rule.mark(0, st);
   const StatsCols sel{nullptr, nullptr, 0, m};
   const bool cache = stats_cache_enabled(src);
   if (cache && stats_cache_known(src, sel)) {
@@ -215,12 +196,12 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
   hipLaunchKernelGGL(k_impute_rule, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, d_counts.p, m, n, method, d_val.p,
                      d_af.p, d_nall.p);
   BSN_HIP(hipGetLastError());
-  BSN_HIP(hipEventRecord(ev_rule.b, st));
+  ev_rule.mark(1, st);
 
   // ---- the rewrite ------------------------------------------------------------------------------------------------------
   if (res) {
     bsn_bed *r = res.get();
-    BSN_HIP(hipEventRecord(ev_write.a, st));
+    ev_write.mark(0, st);
     if (bits == 2) {
       if (r->pitch != src->pitch) fail("internal: pitch of the imputed image");
       const dim3 grid = rewrite_grid(r->pitch / 16, m);
@@ -234,7 +215,7 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
                          r->pitch, n, m, d_val.p);
     }
     BSN_HIP(hipGetLastError());
-    BSN_HIP(hipEventRecord(ev_write.b, st));
+    ev_write.mark(1, st);
     BSN_HIP(hipMemsetAsync(r->d_img + m * r->pitch, 0, (size_t)(64 * r->pitch), st));   // the pad variants
   }
 
@@ -245,8 +226,8 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
   copy_d2h(src, &nall, d_nall.p, sizeof(nall));
   BSN_HIP(hipStreamSynchronize(st));
   if (n_all_missing) *n_all_missing = (int64_t)nall;
-  g_last_ms[0] = ev_rule.ms();
-  if (res) g_last_ms[1] = ev_write.ms();
+  g_last_ms[0] = ev_rule.ms(0, 1);
+  if (res) g_last_ms[1] = ev_write.ms(0, 1);
   if (res) {
     res->na_cnt.resize((size_t)m);
     for (int64_t j = 0; j < m; j++) res->na_cnt[(size_t)j] = val[(size_t)j] < 0 ? (int32_t)n : 0;
@@ -262,14 +243,14 @@ void impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, uint8
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, kBytesGroups));
     for (int64_t j0 = 0; j0 < m; j0 += cols_per) {
       const int64_t cnt = std::min(cols_per, m - j0);
-      BSN_HIP(hipEventRecord(ev_write.a, st));
+      ev_write.mark(0, st);
       hipLaunchKernelGGL(k_impute_bytes, dim3(gx, (unsigned)cnt), dim3(256), 0, st, src->d_img, src->pitch, n, j0, method,
                          d_val.p, d_af.p, seed, tmp.p);
       BSN_HIP(hipGetLastError());
-      BSN_HIP(hipEventRecord(ev_write.b, st));
+      ev_write.mark(1, st);
       copy_d2h(src, fbm_bytes_out + j0 * n, tmp.p, (size_t)cnt * (size_t)n);
       BSN_HIP(hipStreamSynchronize(st));
-      g_last_ms[2] += ev_write.ms();
+      g_last_ms[2] += ev_write.ms(0, 1);
     }
   }
   if (out) *out = res.release();

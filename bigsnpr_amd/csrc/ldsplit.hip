@@ -215,17 +215,6 @@ __global__ __launch_bounds__(kThreads) void k_outside(const int64_t *__restrict_
 
 unsigned blocks_for(int64_t n, int per) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
 
-struct Events {
-  hipEvent_t e[4] = {};
-  Events() {
-    for (auto &v : e) BSN_HIP(hipEventCreate(&v));
-  }
-  ~Events() {
-    for (auto v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
 }  // namespace
 }  // namespace bsn
 
@@ -294,14 +283,14 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
     if (pos_scaled) BSN_HIP(hipMemcpy(d_pos.ensure((size_t)m), pos_scaled, (size_t)m * 8, hipMemcpyHostToDevice));
     const double *pos = pos_scaled ? d_pos.p : nullptr;
 
-    Events ev;
-    BSN_HIP(hipEventRecord(ev.e[0], nullptr));
+    EventMarks<4> ev;
+    ev.mark(0, nullptr);
     k_suffix<<<blocks_for(m, kThreads), kThreads>>>(s->p.p, s->x.p, d_diag.p, m, thr_r2, max_r2, d_S.p);
     BSN_HIP(hipGetLastError());
     k_E<<<blocks_for(m, kThreads), kThreads>>>(s->p.p, s->i.p, d_S.p, d_diag.p, pos, m, min_size, max_size, max_cost, d_E.p,
                                                d_len.p);
     BSN_HIP(hipGetLastError());
-    BSN_HIP(hipEventRecord(ev.e[1], nullptr));
+    ev.mark(1, nullptr);
 
     k_fill<<<blocks_for(m * max_K, kThreads), kThreads>>>(d_C1.p, m * max_K, std::numeric_limits<double>::infinity());
     BSN_HIP(hipGetLastError());
@@ -325,7 +314,7 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
       }
       c_prev = c_k;
     }
-    BSN_HIP(hipEventRecord(ev.e[2], nullptr));
+    ev.mark(2, nullptr);
 
     BSN_HIP(hipMemsetAsync(d_out.p, 0, (size_t)max_K * 8, nullptr));
     k_paths<<<blocks_for(max_K, kThreads), kThreads>>>(d_C1.p, d_best.p, m, max_K, levels, max_cost, d_cost.p, d_cost2.p, d_ok.p,
@@ -340,7 +329,7 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
         BSN_HIP(hipGetLastError());
       }
     }
-    BSN_HIP(hipEventRecord(ev.e[3], nullptr));
+    ev.mark(3, nullptr);
     BSN_HIP(hipEventSynchronize(ev.e[3]));
 
     std::vector<int32_t> ok((size_t)max_K);
@@ -360,11 +349,7 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
     }
     if (levels_run_out) *levels_run_out = levels;
     if (seconds_out)
-      for (int q = 0; q < 3; q++) {
-        float ms = 0;
-        BSN_HIP(hipEventElapsedTime(&ms, ev.e[q], ev.e[q + 1]));
-        seconds_out[q] = ms * 1e-3;
-      }
+      for (int q = 0; q < 3; q++) seconds_out[q] = ev.ms(q, q + 1) * 1e-3;
   });
 }
 

@@ -1669,7 +1669,7 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
     prof_begin(op, op->stats_pending ? 2 : NB == 3 ? 4 : 0);  // the pass that carries the code counts is timed apart
     if (b->bits == 8) {
       const dim3 grid8((unsigned)((op->m + 127) / 128), (unsigned)nslice);
-      const int32_t *cols8 = op->cols_contig ? nullptr : op->d_cols.p;
+      const int32_t *cols8 = op->cols();
 #define BSN_CPROD8(NBV, NAV, CV)                                                                          \
   BSN_KLAUNCH((k_cprod8<NBV, NAV, CV>), grid8, dim3(512), 0, b->stream, b->d_img, b->pitch, cols8, \
                      op->col0, op->m, q, acc, op->m, (int)(kSliceBytes / 256))
@@ -1887,7 +1887,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
     prof_end(op);
     op->last_kernel = g_last_kernel;
     op->passes++;
-    launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, op->rows_identity ? nullptr : op->d_rows.p, op->n,
+    launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, op->rows(), op->n,
                       d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta, 0);
   }
 }
@@ -2102,52 +2102,33 @@ void counts_grouped(bsn_op *op, const int32_t *d_rows, const int32_t *d_group, i
   mult.ensure((size_t)b->n * gmax);
   int8_t *q = op->d_q.ensure((size_t)npad * 32);
   int32_t *acc = op->d_acc.ensure((size_t)3 * op->m * 32);
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (ms_out)
-    for (auto &e : ev) BSN_HIP(hipEventCreate(&e));
-  float ms[3] = {0.f, 0.f, 0.f};
-  auto finish = [&] {
-    for (auto &e : ev)
-      if (e) (void)hipEventDestroy(e), e = nullptr;
-  };
-  try {
-    for (int g0 = 0; g0 < G;) {
-      const int left = G - g0;
-      const int NB = left > per_block ? 2 : 1;   // two column blocks where they save a launch
-      const int gb = left < NB * per_block ? left : NB * per_block, ncol = 16 * NB;
-      if (ms_out) BSN_HIP(hipEventRecord(ev[0], st));
-      BSN_HIP(hipMemsetAsync(mult.p, 0, (size_t)b->n * gb * sizeof(int32_t), st));
-      hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_rows, d_group, n, g0, gb,
-                         b->n, mult.p);
-      const dim3 qgrid((unsigned)((nblk + 255) / 256), (unsigned)gb);
-      if (S == 1) hipLaunchKernelGGL(k_group_digits<1>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
-      else hipLaunchKernelGGL(k_group_digits<4>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
-      BSN_HIP(hipGetLastError());
-      if (ms_out) BSN_HIP(hipEventRecord(ev[1], st));
-      launch_cprod<3, false, false>(op, NB, q, acc, kLutHom2, kLutHet, kLutNA);
-      if (ms_out) BSN_HIP(hipEventRecord(ev[2], st));
-      hipLaunchKernelGGL(k_group_counts_final, dim3((unsigned)((op->m * gb + 255) / 256)), dim3(256), 0, st, acc, op->m, ncol,
-                         S, g0, gb, G, d_gsize, d_table);
-      BSN_HIP(hipGetLastError());
-      if (ms_out) {
-        BSN_HIP(hipEventRecord(ev[3], st));
-        BSN_HIP(hipEventSynchronize(ev[3]));
-        for (int k = 0; k < 3; k++) {
-          float t = 0.f;
-          BSN_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-          ms[k] += t;
-        }
-      }
-      g0 += gb;
+  std::unique_ptr<EventMarks<4>> ev(ms_out ? new EventMarks<4>() : nullptr);   // (no events unless the times are asked for)
+  for (int g0 = 0; g0 < G;) {
+    const int left = G - g0;
+    const int NB = left > per_block ? 2 : 1;   // two column blocks where they save a launch
+    const int gb = left < NB * per_block ? left : NB * per_block, ncol = 16 * NB;
+    if (ev) ev->mark(0, st);
+    BSN_HIP(hipMemsetAsync(mult.p, 0, (size_t)b->n * gb * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_group_scatter, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_rows, d_group, n, g0, gb,
+                       b->n, mult.p);
+    const dim3 qgrid((unsigned)((nblk + 255) / 256), (unsigned)gb);
+    if (S == 1) hipLaunchKernelGGL(k_group_digits<1>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
+    else hipLaunchKernelGGL(k_group_digits<4>, qgrid, dim3(256), 0, st, mult.p, b->n, nblk, gb, ncol, q);
+    BSN_HIP(hipGetLastError());
+    if (ev) ev->mark(1, st);
+    launch_cprod<3, false, false>(op, NB, q, acc, kLutHom2, kLutHet, kLutNA);
+    if (ev) ev->mark(2, st);
+    hipLaunchKernelGGL(k_group_counts_final, dim3((unsigned)((op->m * gb + 255) / 256)), dim3(256), 0, st, acc, op->m, ncol,
+                       S, g0, gb, G, d_gsize, d_table);
+    BSN_HIP(hipGetLastError());
+    if (ev) {
+      ev->mark(3, st);
+      BSN_HIP(hipEventSynchronize(ev->e[3]));
+      for (int k = 0; k < 3; k++) ms_out[k] += ev->ms(k, k + 1);
     }
-    BSN_HIP(hipStreamSynchronize(st));   // `mult` is released on return
-  } catch (...) {
-    finish();
-    throw;
+    g0 += gb;
   }
-  finish();
-  if (ms_out)
-    for (int k = 0; k < 3; k++) ms_out[k] += (double)ms[k];
+  BSN_HIP(hipStreamSynchronize(st));   // `mult` is released on return
 }
 
 // ---------------------------------------------------------------------------

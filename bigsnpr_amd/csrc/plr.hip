@@ -603,17 +603,9 @@ void run(Cols X, double v_off, double v_step, int64_t n, int64_t m, const double
   BSN_HIP(hipMemset(A.o_nb, 0, (size_t)NL * C * 4));
   BSN_HIP(hipMemset(A.P, 0, (size_t)p * C * 8));
 
-  hipEvent_t ev[4];
-  for (auto &e : ev) BSN_HIP(hipEventCreate(&e));
-  struct EvGuard {
-    hipEvent_t *e;
-    ~EvGuard() {
-      for (int i = 0; i < 4; i++) (void)hipEventDestroy(e[i]);
-    }
-  } ev_guard{ev};
+  EventMarks<4> ev;
   double ms_sweep = 0, ms_scan = 0;
-  float ms = 0;
-  BSN_HIP(hipEventRecord(ev[3], 0));
+  ev.mark(3, 0);
   hipLaunchKernelGGL(k_plr_stats<KIND>, dim3((unsigned)p, (unsigned)K), dim3(kScanThreads), 0, 0, A, v_off, v_step);
   BSN_HIP(hipGetLastError());
   int32_t err = 0;
@@ -640,30 +632,27 @@ void run(Cols X, double v_off, double v_step, int64_t n, int64_t m, const double
   BSN_HIP(hipGetLastError());
   // every turn closes a lambda or grows an active set (or uses up max_iter): at most NL (p + 2) turns per chain
   const int64_t max_turns = (int64_t)NL * (p + 2) + 2;
-  BSN_HIP(hipEventRecord(ev[0], 0));
-  BSN_HIP(hipEventSynchronize(ev[0]));
-  BSN_HIP(hipEventElapsedTime(&ms, ev[3], ev[0]));
-  const double ms_start = ms;
+  ev.mark(0, 0);
+  BSN_HIP(hipEventSynchronize(ev.e[0]));
+  const double ms_start = ev.ms(3, 0);
   int64_t turn = 0;
   for (;; turn++) {
     BSN_HIP(hipMemcpy(st.data(), A.st, (size_t)C * sizeof(ChainState), hipMemcpyDeviceToHost));
     if (turn > 0) {   // (the copy waited for the turn's kernels)
-      BSN_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-      ms_sweep += ms;
-      BSN_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-      ms_scan += ms;
+      ms_sweep += ev.ms(0, 1);
+      ms_scan += ev.ms(1, 2);
     }
     bool any = false;
     for (int c = 0; c < C; c++) any |= st[(size_t)c].status == kLive;
     if (!any) break;
     if (turn >= max_turns) fail("%s: internal: the chains did not end", what);
-    BSN_HIP(hipEventRecord(ev[0], 0));
+    ev.mark(0, 0);
     launch_sweep<KIND>(A);
-    BSN_HIP(hipEventRecord(ev[1], 0));
+    ev.mark(1, 0);
     launch_scan<KIND>(A, 0);
     hipLaunchKernelGGL(k_plr_commit, dim3((unsigned)C), dim3(kSweepThreads), 0, 0, A, 0);
     BSN_HIP(hipGetLastError());
-    BSN_HIP(hipEventRecord(ev[2], 0));
+    ev.mark(2, 0);
   }
   long long updates = 0;
   for (int c = 0; c < C; c++) updates += st[(size_t)c].updates;

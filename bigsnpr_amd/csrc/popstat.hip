@@ -87,25 +87,6 @@ __global__ void k_max3(const int32_t *__restrict__ table, int64_t m, const doubl
 
 #pragma clang fp contract(on)
 
-struct EventPair {
-  hipEvent_t a = nullptr, b = nullptr;
-  EventPair() {
-    BSN_HIP(hipEventCreate(&a));
-    BSN_HIP(hipEventCreate(&b));
-  }
-  ~EventPair() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  EventPair(const EventPair &) = delete;
-  EventPair &operator=(const EventPair &) = delete;
-  double ms() const {   // (both events have completed: the caller synchronised the stream)
-    float t = 0.f;
-    BSN_HIP(hipEventElapsedTime(&t, a, b));
-    return (double)t;
-  }
-};
-
 void check_fst_args(int64_t r, double min_maf) {
   if (r < 2) fail("You should provide frequencies for at least 2 populations.");
   if (!(min_maf >= 0.0 && min_maf <= 0.45)) fail("Parameter 'min_maf' should be in range [0, 0.45].");
@@ -120,8 +101,8 @@ double fst_from_device(F first, const double *d_af, const double *d_N, int64_t r
   DevBuf<double> d_fst, d_part, d_out;
   if (fst) d_fst.ensure((size_t)m);
   if (overall) d_part.ensure((size_t)2 * nblk), d_out.ensure(3);
-  EventPair ev;
-  BSN_HIP(hipEventRecord(ev.a, st));
+  EventMarks<2> ev;
+  ev.mark(0, st);
   first();
   hipLaunchKernelGGL(k_fst, dim3((unsigned)nblk), dim3(popstat::kBlock), 0, st, d_af, d_N, r, m, min_maf, fst ? d_fst.p : nullptr,
                      overall ? d_part.p : nullptr);
@@ -130,11 +111,11 @@ double fst_from_device(F first, const double *d_af, const double *d_N, int64_t r
     hipLaunchKernelGGL(k_fst_overall, dim3(1), dim3(64), 0, st, d_part.p, nblk, d_out.p);
     BSN_HIP(hipGetLastError());
   }
-  BSN_HIP(hipEventRecord(ev.b, st));
+  ev.mark(1, st);
   BSN_HIP(hipStreamSynchronize(st));
   if (fst) BSN_HIP(hipMemcpy(fst, d_fst.p, (size_t)m * 8, hipMemcpyDeviceToHost));
   if (overall) BSN_HIP(hipMemcpy(overall, d_out.p, 24, hipMemcpyDeviceToHost));
-  return ev.ms();
+  return ev.ms(0, 1);
 }
 
 void fst_host(const double *af, const double *N, int64_t r, int64_t m, double min_maf, double *fst, double *overall) {
@@ -185,14 +166,14 @@ void snp_max3(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t *y0
   DevBuf<double> d_val, d_score;
   copy_h2d(bed, d_val.ensure((size_t)L), val, (size_t)L * 8);
   d_score.ensure((size_t)m);
-  EventPair ev;
-  BSN_HIP(hipEventRecord(ev.a, st));
+  EventMarks<2> ev;
+  ev.mark(0, st);
   hipLaunchKernelGGL(k_max3, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, d_table.p, m, d_val.p, (int)L, d_score.p);
   BSN_HIP(hipGetLastError());
-  BSN_HIP(hipEventRecord(ev.b, st));
+  ev.mark(1, st);
   copy_d2h(bed, score, d_score.p, (size_t)m * 8);
   BSN_HIP(hipStreamSynchronize(st));
-  g_last_ms[3] = ev.ms();
+  g_last_ms[3] = ev.ms(0, 1);
 }
 
 }  // namespace

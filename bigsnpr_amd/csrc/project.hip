@@ -73,24 +73,6 @@ void oadp_launch(const double *d_XV, const double *d_xnorm, const double *d_sval
   BSN_HIP(hipGetLastError());
 }
 
-struct EventTriple {
-  hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-  EventTriple() {
-    for (auto &x : e) BSN_HIP(hipEventCreate(&x));
-  }
-  ~EventTriple() {
-    for (auto &x : e)
-      if (x) (void)hipEventDestroy(x);
-  }
-  EventTriple(const EventTriple &) = delete;
-  EventTriple &operator=(const EventTriple &) = delete;
-  double ms(int a, int b) const {   // (both events have completed: the caller synchronised the stream)
-    float t = 0.f;
-    BSN_HIP(hipEventElapsedTime(&t, e[a], e[b]));
-    return (double)t;
-  }
-};
-
 void check_oadp_args(int64_t K, const double *sval) {
   if (const char *why = oadp::check_args(K, sval)) fail("%s", why);
 }
@@ -107,10 +89,10 @@ void oadp_host(const double *XV, const double *X_norm, const double *sval, int64
   BSN_HIP(hipMemcpy(d_r.ensure((size_t)n), X_norm, (size_t)n * 8, hipMemcpyHostToDevice));
   BSN_HIP(hipMemcpy(d_s.ensure((size_t)K), sval, (size_t)K * 8, hipMemcpyHostToDevice));
   d_out.ensure((size_t)n * K);
-  EventTriple ev;
-  BSN_HIP(hipEventRecord(ev.e[0], nullptr));
+  EventMarks<2> ev;
+  ev.mark(0, nullptr);
   oadp_launch(d_XV.p, d_r.p, d_s.p, n, (int)K, d_out.p, nullptr);
-  BSN_HIP(hipEventRecord(ev.e[1], nullptr));
+  ev.mark(1, nullptr);
   BSN_HIP(hipStreamSynchronize(nullptr));
   BSN_HIP(hipMemcpy(out, d_out.p, (size_t)n * K * 8, hipMemcpyDeviceToHost));
   g_last_ms[1] = ev.ms(0, 1);
@@ -133,13 +115,13 @@ void bed_project_pca(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int6
   d_XV.ensure((size_t)n * K);
   d_r.ensure((size_t)n);
   d_out.ensure((size_t)n * K);
-  EventTriple ev;
-  BSN_HIP(hipEventRecord(ev.e[0], st));
+  EventMarks<3> ev;
+  ev.mark(0, st);
   op_prod(&op, d_V.p, m, (int)K, d_XV.p, n);
   op_row_sums_sq(&op, d_r.p);
-  BSN_HIP(hipEventRecord(ev.e[1], st));
+  ev.mark(1, st);
   oadp_launch(d_XV.p, d_r.p, d_s.p, n, (int)K, d_out.p, st);
-  BSN_HIP(hipEventRecord(ev.e[2], st));
+  ev.mark(2, st);
   copy_d2h(bed, XV, d_XV.p, (size_t)n * K * 8);
   copy_d2h(bed, rowSumsSq, d_r.p, (size_t)n * 8);
   copy_d2h(bed, OADP, d_out.p, (size_t)n * K * 8);

@@ -931,22 +931,12 @@ void check_ind_sub(const bsn_sfbm *s, const int64_t *ind_sub, int64_t m, bool re
 // HIP events around the device work of one call -> s->last_ms
 struct CallTimer {
   bsn_sfbm *s;
-  hipEvent_t a = nullptr, b = nullptr;
-  explicit CallTimer(bsn_sfbm *s_) : s(s_) {
-    BSN_HIP(hipEventCreate(&a));
-    BSN_HIP(hipEventCreate(&b));
-    BSN_HIP(hipEventRecord(a, nullptr));
-  }
+  EventMarks<2> ev;
+  explicit CallTimer(bsn_sfbm *s_) : s(s_) { ev.mark(0, nullptr); }
   void stop() {
-    float ms = 0;
-    BSN_HIP(hipEventRecord(b, nullptr));
-    BSN_HIP(hipEventSynchronize(b));
-    BSN_HIP(hipEventElapsedTime(&ms, a, b));
-    s->last_ms = ms;
-  }
-  ~CallTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
+    ev.mark(1, nullptr);
+    BSN_HIP(hipEventSynchronize(ev.e[1]));
+    s->last_ms = ev.ms(0, 1);
   }
 };
 

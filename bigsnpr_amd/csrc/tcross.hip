@@ -241,7 +241,7 @@ static void tcross_resident(bsn_bed *bed, const int64_t *ind_row, int64_t n, con
     double *out = d_K.p;
     if (nslab > 1) out = d_part.ensure((size_t)nslab * n * n);
     const dim3 grid((unsigned)pairs.size(), (unsigned)nslab);
-    const int32_t *cols = op.cols_contig ? nullptr : op.d_cols.p;
+    const int32_t *cols = op.cols();
     // BSN_TCROSS_WAVES=4 selects the 4-wave shape (A/B measurements)
     const char *we = abl_getenv("BSN_TCROSS_WAVES");
     const bool w4 = we && atoi(we) == 4;
