@@ -225,6 +225,49 @@ int bsn_impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, ui
  * image, [2] the kernels that write the FBM bytes (0 when none were asked for) */
 int bsn_impute_last_ms(double *ms_out);
 
+/* ---- snp_readBGEN / snp_prodBGEN: inflate and decode BGEN on the device ----------------------------------
+ * BGEN v1.2 files as the UK Biobank ships them (R/read-bgen.R, src/read-bgen.cpp, src/prod-bgen.cpp): layout 2, zlib,
+ * two alleles, unphased, 8 bits per probability.  The probabilities of a variant are one zlib stream of 10 + 3 N bytes;
+ * blocks of variants are uploaded compressed, inflated one wave per stream, and decoded.  The library links no zlib:
+ * the statement of a stream is bigsnpr_amd/csrc/inflate_step.hpp.
+ *
+ * bsn_inflate: K independent zlib streams, stream k = in[in_off[k] .. in_off[k + 1]) into out[out_off[k] .. out_off[k + 1]),
+ * whose length is both the room and the expected length (host buffers; the test seam).  status[k]:
+ *   0 ok   1 bad zlib header   2 input exhausted   3 output would exceed its room   4 invalid block type, stored length
+ *   or code   5 distance before the start of the output   6 Adler-32 mismatch   7 stream ended short of its length
+ * A stream with a non-zero status leaves its part of `out` undefined; the call itself succeeds.
+ *
+ * bsn_bgen_read: the variants whose records start at offsets[0 .. K) of `path` (N samples; the rows ind_row[0 .. n), file
+ * samples from 0, any order, repeats allowed) become columns col0 .. col0 + K - 1 of an n x m_total int8 grid image of
+ * CODE_DOSAGE (v_off = 1, v_step = 0.01), exactly what bsn_fbm_open makes of the same FBM bytes.  *inout NULL: the image
+ * is created (and freed again if the call fails); else it is filled.  dosage != 0: the FBM byte of a sample is
+ * decode[2 p0 + p1] (511 bytes, the reference's 207 - round(0:510 * 100 / 255)); dosage == 0: the call 0 / 1 / 2 (FBM
+ * byte 4 / 5 / 6) drawn with first = 255 u - p0, u from one Philox4x32-10 call keyed by `seed` with the counter
+ * (position in ind_row, global column): not R's generator.  A ploidy byte >= 0x80 is a missing sample (FBM byte 3).
+ * info_out / freq_out (K each, may be NULL): 1 - num 2 nona / (af (coef - af)) and 1 - af / coef from exact integer sums,
+ * in the reference's operation order; NaN for a variant without a non-missing sample.  fbm_bytes_out: n x K column-major.
+ * Errors keep the reference's words: "'%s' is not a BGEN file.", "... is not compressed with zlib.", "... is not using
+ * Layout 2.", "Positions should be positive.", "Only 2 alleles allowed.", "Probabilities should be stored using 8 bits.",
+ * "Problem when uncompressing." followed by the variant's index and the stream's status.  Refused by name: a byte of
+ * `decode` above 207, a result image that does not fit the free device memory.
+ *
+ * bsn_bgen_prod: XY (n x ncol column-major, added to) += X Y with X the n x K matrix of the same variants, never stored:
+ * x = decode[2 p0 + p1] (511 doubles, the reference's 510:0 / 255) or the drawn call, NaN for a missing sample (which
+ * turns that sample's row into NaN); Y is K x ncol with leading dimension ldy.  fp64 throughout.
+ *
+ * bsn_bgen_last_ms: device milliseconds (HIP events) of the last of these calls of this process: [0] the inflate
+ * kernel, [1] the conversion to image rows, [2] the product; a phase that did not run reports exactly 0. */
+int bsn_inflate(const uint8_t *in, const int64_t *in_off /* K+1 */, int64_t K, uint8_t *out, const int64_t *out_off /* K+1 */,
+                int32_t *status /* K */);
+int bsn_bgen_read(const char *path, const int64_t *offsets, int64_t K, int64_t N, const int64_t *ind_row, int64_t n,
+                  const uint8_t *decode /* 511 FBM bytes */, int dosage, uint64_t seed, int64_t col0, int64_t m_total,
+                  int64_t block_variants /* 0: chosen from free memory */, bsn_bed **inout, uint8_t *fbm_bytes_out /* or NULL */,
+                  double *info_out /* K */, double *freq_out /* K */);
+int bsn_bgen_prod(const char *path, const int64_t *offsets, int64_t K, int64_t N, const int64_t *ind_row, int64_t n,
+                  const double *decode /* 511 */, int dosage, uint64_t seed, int64_t col0, const double *Y, int64_t ldy,
+                  int64_t ncol, int64_t block_variants, double *XY /* n x ncol, added to */);
+int bsn_bgen_last_ms(double *ms_out /* 3: inflate, convert, product */);
+
 /* ---- per-group genotype counts, snp_fst, snp_MAX3 ------------------------------------------------------
  * Counts of the four codes of every selected variant, split by a label on the selected rows, in ONE pass over the image
  * (the reference, and bsn_bed_col_counts, need one pass per group): res[4 * (G * j + g) + c] is the number of rows i with

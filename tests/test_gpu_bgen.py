@@ -1,0 +1,380 @@
+"""snp_readBGEN / snp_prodBGEN and bsn_inflate on the device (bigsnpr_amd/csrc/bgen.hip) against the CPU statements
+compiled from the same headers (tests/native/inflate_ref.cpp, bgen_ref.cpp) and against a decode through Python's zlib:
+bytes, statuses, integer sums, info and freq are equalities; the product is held to the standard summation bound.  The
+malformed streams handed to the device are the fixed list that tests/test_inflate_cpu.py has run under the sanitizers —
+nothing random reaches the device."""
+import ctypes as C
+import os
+import sys
+import zlib
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+
+import bgen_inputs as bi  # noqa: E402
+import bgen_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+SEED = 20240611
+EXCLUDED = [17, 18]   # the duplicate IDs that the reference's test excludes too (test-1-readBGEN.R)
+
+
+@pytest.fixture(scope="module")
+def ba():
+    import bigsnpr_amd
+    return bigsnpr_amd
+
+
+def device_inflate(ba, streams, lens):
+    from bigsnpr_amd import _lib
+    inp, in_off, out_off = bi.pack(streams, lens)
+    out = np.zeros(max(int(out_off[-1]), 1), dtype=np.uint8)
+    status = np.full(len(streams), -1, dtype=np.int32)
+    _lib.check(_lib.load().bsn_inflate(_lib.ptr(inp, _lib.u8p), _lib.ptr(in_off, _lib.i64p), len(streams),
+                                       _lib.ptr(out, _lib.u8p), _lib.ptr(out_off, _lib.i64p), _lib.ptr(status, _lib.i32p)))
+    want_out, want_status = ref.inflate(inp, in_off, out_off)
+    return out[:int(out_off[-1])], status, want_out, want_status, out_off
+
+
+def last_ms(ba):
+    from bigsnpr_amd import _lib
+    ms = np.full(3, -1.0)
+    _lib.check(_lib.load().bsn_bgen_last_ms(_lib.ptr(ms, _lib.f64p)))
+    return ms
+
+
+# ---- 1. bsn_inflate against the twin --------------------------------------------------------------------------------------
+def test_inflate_corpus(ba):
+    cases = bi.corpus()
+    out, status, want_out, want_status, off = device_inflate(ba, [c[1] for c in cases], [len(c[2]) for c in cases])
+    assert list(status) == list(want_status) == [0] * len(cases)
+    for k, c in enumerate(cases):
+        assert out[off[k]:off[k + 1]].tobytes() == c[2], c[0]
+    assert np.array_equal(out, want_out)
+    ms = last_ms(ba)
+    assert ms[0] > 0 and ms[1] == 0 and ms[2] == 0
+
+
+@pytest.mark.parametrize("count", [300, 2500])
+def test_inflate_many_streams_in_one_call(ba, count):
+    """300: the issue's case; 2500 small streams: more than one grid-stride turn at four waves on each of 256 compute units"""
+    small = [c for c in bi.corpus() if len(c[2]) <= 6000]
+    rng = np.random.default_rng(count)
+    pick = [small[k] for k in rng.integers(0, len(small), count)]
+    out, status, want_out, want_status, off = device_inflate(ba, [c[1] for c in pick], [len(c[2]) for c in pick])
+    assert not status.any() and not want_status.any()
+    assert np.array_equal(out, want_out)
+    assert out.tobytes() == b"".join(c[2] for c in pick)
+
+
+def test_inflate_malformed_list(ba):
+    """the fixed list only (where room and expected length are one number, as in bsn_inflate's signature), between valid
+    streams that must come out untouched"""
+    bad = [m for m in bi.malformed() if m[2] == m[3]]
+    good = bi.corpus()[1]
+    streams, lens = [good[1]], [len(good[2])]
+    for m in bad:
+        streams += [m[1], good[1]]
+        lens += [m[2], len(good[2])]
+    out, status, want_out, want_status, off = device_inflate(ba, streams, lens)
+    assert list(status) == list(want_status)
+    assert list(status[1::2]) == [m[4] for m in bad] and not status[0::2].any()
+    for k in range(0, len(streams), 2):
+        assert out[off[k]:off[k + 1]].tobytes() == good[2]
+
+
+# ---- 2. snp_readBGEN on the reference's example file ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def ex(ba, tmp_path_factory):
+    """the example file, its index in the index's own row order, the decode through Python's zlib (computed once)"""
+    bgen = bi.example_files(tmp_path_factory.mktemp("bgen"))
+    tab = ba.snp_readBGI(bgen + ".bgi")
+    ids = ["%s_%d_%s_%s" % t for t in zip(tab["chromosome"], tab["position"], tab["allele1"], tab["allele2"])]
+    offs = tab["file_start_position"]
+    cols, dos, vids, sums = bi.decode_file(bgen, offs)
+    d = bi.read_rds_doubles(os.path.join(bi.GOLDEN, "bgen_dosages.rds"))
+    keep = np.setdiff1d(np.arange(199), EXCLUDED)
+    return dict(bgen=bgen, tab=tab, ids=ids, offs=offs, bytes=cols, dos=dos, vids=vids, sums=sums, keep=keep,
+                dosages=d.reshape(199, 500).T)
+
+
+def read_subset(ba, ex, cols, **kw):
+    """snp_readBGEN of the example's variants `cols` (unique IDs only: the two duplicates cannot be asked for by ID)"""
+    return ba.snp_readBGEN(ex["bgen"], [[ex["ids"][j] for j in cols]], return_bytes=True, **kw)
+
+
+def check_against_decode(ba, res, want_bytes, want_sums):
+    assert res.bits == 8 and res.shape == want_bytes.shape
+    assert np.array_equal(res.bytes, want_bytes)
+    info, freq = bi.info_freq(want_sums)
+    for k in range(want_sums.shape[0]):   # bit-equal to the twin, which is bit-equal to the numpy restatement
+        assert np.array_equal(np.array(ref.info_freq(*want_sums[k])), np.array([res.map["info"][k], res.map["freq"][k]]),
+                              equal_nan=True)
+    assert np.array_equal(res.map["info"], info, equal_nan=True) and np.array_equal(res.map["freq"], freq, equal_nan=True)
+    # the image is what bsn_fbm_open makes of the same bytes
+    twin = ba.FBM_code256(res.bytes, ba.CODE_DOSAGE)
+    assert twin.bits == 8 and twin._has_na == res._has_na == bool((want_bytes == 3).any())
+    a, b = ba.snp_colstats(res), ba.snp_colstats(twin)
+    np.testing.assert_array_equal(a["sumX"], b["sumX"])
+    np.testing.assert_array_equal(a["denoX"], b["denoX"])
+    complete = np.flatnonzero(~(want_bytes == 3).any(axis=0))
+    if complete.size:
+        x = np.random.default_rng(1).integers(-3, 4, complete.size).astype(np.float64)
+        got = ba.big_prodVec(res, x, ind_col=complete)
+        np.testing.assert_array_equal(got, ba.big_prodVec(twin, x, ind_col=complete))
+        # and read back column by column through unit vectors: hundredths, exact
+        val = np.rint(100 * np.nan_to_num(ba.CODE_DOSAGE[want_bytes])).astype(np.int64)   # (missing columns are not read)
+        for jj in range(0, complete.size, max(1, complete.size // 6)):
+            e = np.zeros(complete.size)
+            e[jj] = 1.0
+            assert np.array_equal(np.rint(100 * ba.big_prodVec(res, e, ind_col=complete)).astype(np.int64), val[:, complete[jj]])
+    return twin
+
+
+def test_example_file_dosages(ba, ex):
+    keep = ex["keep"]
+    res = read_subset(ba, ex, keep)
+    check_against_decode(ba, res, ex["bytes"][:, keep], ex["sums"][keep])
+    # against the reference's own dosages, rounded as snp_readBGEN rounds them: difference 0.0, both missing values in place
+    val = ba.CODE_DOSAGE[res.bytes]
+    want = np.round(ex["dosages"][:, keep], 2)
+    assert np.isnan(val).sum() == 2 and np.array_equal(np.isnan(val), np.isnan(want))
+    assert np.nanmax(np.abs(val - want)) == 0.0
+    # freq against the image's column means (test-1-readBGEN.R:80)
+    assert np.nanmax(np.abs(res.map["freq"] - np.nanmean(val, axis=0) / 2)) < 2e-4
+    assert res.map["marker.ID"] == [ex["vids"][j] for j in keep] and res.map["rsid"] == [ex["tab"]["rsid"][j] for j in keep]
+    assert list(res.map["physical.pos"]) == [int(ex["tab"]["position"][j]) for j in keep]
+    ms = last_ms(ba)
+    assert ms[0] > 0 and ms[1] > 0 and ms[2] == 0
+
+
+def test_example_file_all_variants_by_offset(ba, ex):
+    """all 199 records, the two with duplicate IDs among them, through the C entry (which takes offsets, not IDs)"""
+    from bigsnpr_amd import _lib
+    from bigsnpr_amd.bgen import DECODE_BYTES
+    n, m = 500, 199
+    rows, offs = np.arange(n, dtype=np.int64), np.ascontiguousarray(ex["offs"], dtype=np.int64)
+    out = np.empty((n, m), dtype=np.uint8, order="F")
+    info, freq = np.empty(m), np.empty(m)
+    h = _lib.vp()
+    _lib.check(_lib.load().bsn_bgen_read(ex["bgen"].encode(), _lib.ptr(offs, _lib.i64p), m, n, _lib.ptr(rows, _lib.i64p), n,
+                                         _lib.ptr(DECODE_BYTES, _lib.u8p), 1, 0, 0, m, 0, C.byref(h), _lib.ptr(out, _lib.u8p),
+                                         _lib.ptr(info, _lib.f64p), _lib.ptr(freq, _lib.f64p)))
+    _lib.load().bsn_bed_close(h)
+    assert np.array_equal(out, ex["bytes"])
+    want_info, want_freq = bi.info_freq(ex["sums"])
+    assert np.array_equal(info, want_info) and np.array_equal(freq, want_freq)
+
+
+def test_subset_in_shuffled_order(ba, ex):
+    cols = np.random.default_rng(5).permutation(ex["keep"])[:40]
+    res = read_subset(ba, ex, cols)
+    check_against_decode(ba, res, ex["bytes"][:, cols], ex["sums"][cols])
+
+
+def test_rows_with_repeats(ba, ex):
+    rows = np.random.default_rng(6).integers(0, 500, 100)
+    assert np.unique(rows).size < 100
+    cols = ex["keep"][::3]
+    res = read_subset(ba, ex, cols, ind_row=rows)
+    want, _, _, sums = bi.decode_file(ex["bgen"], ex["offs"][cols], rows)
+    check_against_decode(ba, res, want, sums)
+
+
+def test_block_of_seven_variants(ba, ex):
+    """197 variants in blocks of 7: 29 blocks, the last one short"""
+    keep = ex["keep"]
+    res = read_subset(ba, ex, keep, block_variants=7)
+    assert np.array_equal(res.bytes, ex["bytes"][:, keep])
+    info, freq = bi.info_freq(ex["sums"][keep])
+    assert np.array_equal(res.map["info"], info) and np.array_equal(res.map["freq"], freq)
+
+
+def three_files(tmp_path, N=85, sizes=(5, 1, 7), seed=40):
+    files, ids, var = [], [], []
+    for f, K in enumerate(sizes):
+        p0, p1, miss = bi.probabilities(N, K, seed=seed + f, missing=0.03)
+        path = str(tmp_path / ("part%d.bgen" % f))
+        v = bi.write_bgen(path, p0, p1, miss, chrom="%02d" % (f + 1))
+        files.append(path)
+        ids.append([x["snp_id"] for x in v])
+        var.append(v)
+    return files, ids, var
+
+
+def test_three_files_into_one_image(ba, tmp_path):
+    files, ids, var = three_files(tmp_path)
+    res = ba.snp_readBGEN(files, ids, return_bytes=True)
+    parts = [bi.decode_file(f, [x["offset"] for x in v]) for f, v in zip(files, var)]
+    check_against_decode(ba, res, np.asfortranarray(np.concatenate([p[0] for p in parts], axis=1)),
+                         np.concatenate([p[3] for p in parts]))
+    assert res.map["chromosome"] == ["01"] * 5 + ["02"] + ["03"] * 7
+    assert res.map["marker.ID"] == sum((p[2] for p in parts), [])
+
+
+# ---- 3. written files at the sizes where the kernels can break ---------------------------------------------------------------
+@pytest.mark.parametrize("N,K", [(1, 3), (21, 4), (85, 1), (257, 9)])
+def test_written_files(ba, tmp_path, N, K):
+    p0, p1, miss = bi.probabilities(N, K, seed=N, missing=0.05)
+    if K > 1:
+        miss[:, 1] = True        # a variant with every sample missing
+    path = str(tmp_path / "w.bgen")
+    var = bi.write_bgen(path, p0, p1, miss)
+    res = ba.snp_readBGEN(path, [[v["snp_id"] for v in var]], return_bytes=True)
+    want, _, _, sums = bi.decode_file(path, [v["offset"] for v in var])
+    check_against_decode(ba, res, want, sums)
+    if K > 1:
+        assert np.isnan(res.map["info"][1]) and np.isnan(res.map["freq"][1]) and (res.bytes[:, 1] == 3).all()
+
+
+def test_wide_file_wraps_the_window(ba, tmp_path):
+    """N = 11 000: a variant inflates to 33 010 bytes, more than the 32-KiB window.  One variant is one fixed block with
+    a match at distance 32 768, one is stored blocks only, one is Z_FIXED, the others are what zlib makes at level 6."""
+    N, K = 11000, 5
+    p0, p1, miss = bi.probabilities(N, K, seed=11, missing=0.01)
+    D = 10 + 3 * N
+    # variant 0: bytes [32776, 32876) repeat the ploidy bytes [8, 108) — samples 10883 .. 10932 have p0 = p1 = 2
+    miss[:100, 0] = False
+    lo, hi = (32776 - 10 - N) // 2, (32876 - 10 - N) // 2
+    p0[lo:hi, 0], p1[lo:hi, 0], miss[lo:hi, 0] = 2, 2, False
+    block = bi.inflated_block(p0[:, 0], p1[:, 0], miss[:, 0])
+    assert len(block) == D and block[32776:32876] == block[8:108]
+    w = bi.BitWriter()
+    bi.fixed_block(w, list(block[:32776]) + [(100, 32768)] + list(block[32876:]))
+    crafted = bi.zlib_wrap(w, block)
+    assert zlib.decompress(crafted) == block
+
+    def compress(j, blk):
+        if j == 1:
+            return zlib.compress(blk, 0)
+        c = zlib.compressobj(6, zlib.DEFLATED, 15, 8, zlib.Z_FIXED if j == 2 else zlib.Z_DEFAULT_STRATEGY)
+        return c.compress(blk) + c.flush()
+
+    path = str(tmp_path / "wide.bgen")
+    var = bi.write_bgen(path, p0, p1, miss, compress=compress, streams={0: crafted})
+    res = ba.snp_readBGEN(path, [[v["snp_id"] for v in var]], return_bytes=True)
+    want, _, _, sums = bi.decode_file(path, [v["offset"] for v in var])
+    check_against_decode(ba, res, want, sums)
+
+
+# ---- 4. read_as = "random" ----------------------------------------------------------------------------------------------------
+def test_random_calls(ba, tmp_path):
+    N, K = 257, 6
+    p0, p1, miss = bi.probabilities(N, K, seed=77, missing=0.04)
+    path = str(tmp_path / "r.bgen")
+    var = bi.write_bgen(path, p0, p1, miss)
+    ids = [[v["snp_id"] for v in var]]
+    rows = np.random.default_rng(8).integers(0, N, 300)
+    res = ba.snp_readBGEN(path, ids, ind_row=rows, read_as="random", seed=SEED, return_bytes=True)
+    want = np.empty((rows.size, K), dtype=np.uint8)
+    for j in range(K):
+        block = np.frombuffer(bi.inflated_block(p0[:, j], p1[:, j], miss[:, j]), dtype=np.uint8)
+        want[:, j], _ = ref.variant(block, N, rows, bi.DECODE_BYTES, 0, SEED, j)
+    assert np.array_equal(res.bytes, want)
+    assert set(np.unique(res.bytes)) <= {3, 4, 5, 6}
+    # wherever a probability is 255 the call is that genotype
+    P0, P1, M = p0[rows], p1[rows], miss[rows]
+    assert (res.bytes[(P0 == 255) & ~M] == 4).all() and (res.bytes[(P1 == 255) & ~M] == 5).all()
+    assert (res.bytes[(P0 == 0) & (P1 == 0) & ~M] == 6).all() and (res.bytes[M] == 3).all()
+    twin = ba.FBM_code256(res.bytes, ba.CODE_DOSAGE)
+    np.testing.assert_array_equal(ba.snp_colstats(res)["sumX"], ba.snp_colstats(twin)["sumX"])
+    # info / freq come from the probabilities, not from the draws
+    _, _, _, sums = bi.decode_file(path, [v["offset"] for v in var], rows)
+    assert np.array_equal(res.map["freq"], bi.info_freq(sums)[1], equal_nan=True)
+    again = ba.snp_readBGEN(path, ids, ind_row=rows, read_as="random", seed=SEED, return_bytes=True)
+    other = ba.snp_readBGEN(path, ids, ind_row=rows, read_as="random", seed=SEED + 1, return_bytes=True)
+    assert np.array_equal(again.bytes, res.bytes) and not np.array_equal(other.bytes, res.bytes)
+
+
+# ---- 5. snp_prodBGEN ------------------------------------------------------------------------------------------------------------
+def check_product(got, X, beta):
+    """|got - X beta| <= 4 m 2^-53 sum_j |x_ij| |beta_jc| per entry (the standard summation bound: both sides sum m
+    products in fp64 in some order); NaN rows are exactly the samples with a missing value"""
+    beta2 = beta[:, None] if beta.ndim == 1 else beta
+    got2 = got[:, None] if got.ndim == 1 else got
+    assert got2.shape == (X.shape[0], beta2.shape[1])
+    nan_row = np.isnan(X).any(axis=1)
+    assert np.array_equal(np.isnan(got2), np.repeat(nan_row[:, None], beta2.shape[1], axis=1))
+    ok = ~nan_row
+    want = X[ok] @ beta2
+    bound = 4 * X.shape[1] * 2.0 ** -53 * (np.abs(X[ok]) @ np.abs(beta2))
+    err = np.abs(got2[ok] - want)
+    print("snp_prodBGEN: max error %.3g, max error / bound %.3g" % (err.max(initial=0.0), (err / np.maximum(bound, 1e-300)).max(initial=0.0)))
+    assert (err <= bound).all()
+
+
+@pytest.fixture(scope="module")
+def prod_file(tmp_path_factory):
+    N, K = 257, 120
+    p0, p1, miss = bi.probabilities(N, K, seed=123, missing=0.001)
+    path = str(tmp_path_factory.mktemp("prod") / "p.bgen")
+    var = bi.write_bgen(path, p0, p1, miss)
+    _, X, _, _ = bi.decode_file(path, [v["offset"] for v in var])
+    assert 0 < np.isnan(X).any(axis=1).sum() < N
+    return dict(path=path, ids=[[v["snp_id"] for v in var]], X=X, offs=[v["offset"] for v in var])
+
+
+@pytest.mark.parametrize("ncol", [0, 1, 11])
+def test_product_shapes_of_beta(ba, prod_file, ncol):
+    """a vector, a one-column matrix, and 11 columns: one register tile of k_bgen_prod holds 8"""
+    rng = np.random.default_rng(ncol)
+    beta = rng.standard_normal(120) if ncol == 0 else rng.standard_normal((120, ncol))
+    got = ba.snp_prodBGEN(prod_file["path"], beta, prod_file["ids"])
+    assert got.ndim == (1 if ncol == 0 else 2)
+    check_product(got, prod_file["X"], beta)
+    ms = last_ms(ba)
+    assert ms[0] > 0 and ms[1] == 0 and ms[2] > 0
+
+
+@pytest.mark.parametrize("block_size", [1, 50, 1000])
+def test_product_block_sizes(ba, prod_file, block_size):
+    beta = np.random.default_rng(block_size).standard_normal((120, 3))
+    check_product(ba.snp_prodBGEN(prod_file["path"], beta, prod_file["ids"], block_size=block_size), prod_file["X"], beta)
+
+
+def test_product_with_rows(ba, prod_file):
+    rows = np.random.default_rng(2).integers(0, 257, 300)
+    beta = np.random.default_rng(3).standard_normal((120, 2))
+    check_product(ba.snp_prodBGEN(prod_file["path"], beta, prod_file["ids"], ind_row=rows), prod_file["X"][rows], beta)
+
+
+def test_product_three_files(ba, tmp_path):
+    files, ids, var = three_files(tmp_path)
+    X = np.concatenate([bi.decode_file(f, [x["offset"] for x in v])[1] for f, v in zip(files, var)], axis=1)
+    beta = np.random.default_rng(4).standard_normal((13, 9))
+    check_product(ba.snp_prodBGEN(files, beta, ids, block_size=4), X, beta)
+
+
+# ---- 6. errors and timers -------------------------------------------------------------------------------------------------------
+def test_errors_leave_the_process_working(ba, tmp_path):
+    N, K = 21, 4
+    p0, p1, miss = bi.probabilities(N, K, seed=5)
+    good = str(tmp_path / "good.bgen")
+    var = bi.write_bgen(good, p0, p1, miss)
+    ids = [[v["snp_id"] for v in var]]
+    z = zlib.compress(bi.inflated_block(p0[:, 2], p1[:, 2], miss[:, 2]), 6)
+    for kw, msg in ((dict(streams={2: z[:-5]}), r"Problem when uncompressing\. \(variant 2, status 2\)"),
+                    (dict(D_add=1), r"Probabilities should be stored using 8 bits\."),
+                    (dict(pos=0), r"Positions should be positive\."),
+                    (dict(alleles=3), r"Only 2 alleles allowed\.")):
+        bad = str(tmp_path / "bad.bgen")
+        vb = bi.write_bgen(bad, p0, p1, miss, **kw)
+        for call in (lambda: ba.snp_readBGEN(bad, [[v["snp_id"] for v in vb]]),
+                     lambda: ba.snp_prodBGEN(bad, np.ones(K), [[v["snp_id"] for v in vb]])):
+            with pytest.raises(ba.BsnError, match=msg):
+                call()
+        # the process goes on and a following good call is correct
+        res = ba.snp_readBGEN(good, ids, return_bytes=True)
+        assert np.array_equal(res.bytes, bi.decode_file(good, [v["offset"] for v in var])[0])
+    from bigsnpr_amd import _lib
+    table = bi.DECODE_BYTES.copy()
+    table[100] = 208
+    rows, offs = np.arange(N, dtype=np.int64), np.array([v["offset"] for v in var], dtype=np.int64)
+    h = _lib.vp()
+    rc = _lib.load().bsn_bgen_read(good.encode(), _lib.ptr(offs, _lib.i64p), K, N, _lib.ptr(rows, _lib.i64p), N,
+                                   _lib.ptr(table, _lib.u8p), 1, 0, 0, K, 0, C.byref(h), None, None, None)
+    assert rc != 0 and not h.value and "'decode' holds the byte 208" in _lib.load().bsn_last_error().decode()
