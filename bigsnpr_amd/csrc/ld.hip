@@ -20,32 +20,12 @@
 #include <unordered_map>
 #include "bsn_internal.hpp"
 #include "ld_plan.hpp"
+#include "plane_decode.hpp"
 
 namespace bsn {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t lut4b(uint32_t lut, uint32_t sel) {
-  return __builtin_amdgcn_perm(lut, lut, sel);
-}
-// device code (bsn_internal.hpp: 0, 1, 2 = allele count, 3 = missing) -> plane value
-constexpr uint32_t kLX = 0x00020100u;   // code 0,1,2,3 -> 0, 1, 2, 0
-constexpr uint32_t kLX2 = 0x00040100u;  //               -> 0, 1, 4, 0
-constexpr uint32_t kLM = 0x00010101u;   //               -> 1, 1, 1, 0
+// v4i, lut4b, the look-up constants, Planes and decode3: plane_decode.hpp (shared with king.hip)
 constexpr int TB = 64;                  // variants per tile side
-
-struct Planes {
-  v4i x, x2, m;
-};
-__device__ __forceinline__ Planes decode3(uint32_t w) {
-  const uint32_t s0 = w & 0x03030303u, s1 = (w >> 2) & 0x03030303u, s2 = (w >> 4) & 0x03030303u,
-                 s3 = (w >> 6) & 0x03030303u;
-  Planes p;
-  p.x = v4i{(int)lut4b(kLX, s0), (int)lut4b(kLX, s1), (int)lut4b(kLX, s2), (int)lut4b(kLX, s3)};
-  p.x2 = v4i{(int)lut4b(kLX2, s0), (int)lut4b(kLX2, s1), (int)lut4b(kLX2, s2), (int)lut4b(kLX2, s3)};
-  p.m = v4i{(int)lut4b(kLM, s0), (int)lut4b(kLM, s1), (int)lut4b(kLM, s2), (int)lut4b(kLM, s3)};
-  return p;
-}
 
 // The fp64 epilogue of one variant pair, in the reference's operation order (no contraction):
 // mode 0: r of corMat0 with threshold (dropped -> 2.0), src/corr.cpp:76-86;  mode 1: r2 of

@@ -304,6 +304,31 @@ int bsn_snp_max3(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t 
  * One record per process, written without a lock, like bsn_impute_last_ms. */
 int bsn_popstat_last_ms(double *ms_out /* 4 */);
 
+/* ---- KING-robust kinship table (bed_king / bed_kingQC; what snp_plinkKINGQC asks of PLINK 2, R/external-software.R:520-590) ----
+ * For every pair of positions i < j of ind_row, over the selected variants where both samples are called: NSNP, HETHET
+ * (both heterozygous), IBS0 (opposite homozygotes), HET1HOM2 (i heterozygous, j homozygous), HET2HOM1 (the reverse) and
+ *   KINSHIP = 0.5 - (double)(4 IBS0 + HET1HOM2 + HET2HOM1) / (4.0 * (double)(HETHET + min(HET1HOM2, HET2HOM1)))
+ * (Manichaikul et al. 2010, between-family; one division and one subtraction in IEEE double: NaN for 0 / 0, -inf for a
+ * zero denominator otherwise).  The counts are exact: seven int32 plane products over the sample-major copy of the image
+ * on the int8 matrix pipe, two when every selected variant is known to hold no missing call (bsn_bed_na_known's record;
+ * BSN_KING_GENERAL=1 forces the seven).  ind_row may be any list, repeats included; ind_col other than all variants in
+ * file order is served from a gathered copy of the selection.
+ * Two-phase like bsn_cormat: this call computes on the device and returns the number of rows; filter = 0 keeps every
+ * pair (non-finite kinships included), otherwise the pairs with KINSHIP >= thr.  Rows ascend in (i, j); two calls return
+ * the same bytes.  Refused by name: a byte (dosage) image, an out-of-core handle, no room for the sample-major operand
+ * or for the table, n < 2, m < 1, m >= 2^29. */
+typedef struct bsn_king bsn_king;
+int bsn_bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, double thr, int filter,
+                 int64_t *count, bsn_king **out);
+/* i1, i2 [count] (positions in ind_row, 0-based), counts [5 x count] (row k at 5 k: NSNP, HETHET, IBS0, HET1HOM2,
+ * HET2HOM1), kinship [count].  The bsn_bed of the call must still be open. */
+int bsn_king_fetch(bsn_king *king, int32_t *i1, int32_t *i2, int32_t *counts, double *kinship);
+int bsn_king_free(bsn_king *king);
+/* device milliseconds (HIP events) of the last bsn_bed_king of this process: [0] the operand (gathered selection,
+ * sample-major copy), [1] the per-sample totals of the two-product path (0 on the general path), [2] the pair kernel,
+ * [3] the compaction.  One record per process, written without a lock. */
+int bsn_king_last_ms(double *ms_out /* 4 */);
+
 /* _bigsnpr_prod_and_rowSumsSq (6 args) src/bed-fun.cpp:103-133 (the kernel of
  * bed_projectSelfPCA, R/bed-projectPCA.R:45-59): XV[n x K] = A~ V[m x K] and
  * rowSumsSq[i] = sum_j A~[i, j]^2, column-major host buffers. */
