@@ -3,8 +3,8 @@
     python -m bigsnpr_amd.build [--force] [--ablation]
 
 --ablation builds a SEPARATE library, libbigsnpr_hip_abl.so, with -DBSN_ABLATION: it additionally
-reads the profiling switches (abl_getenv in bsn_internal.hpp; the slab sweeps BSN_KY / BSN_KY_T of
-the streaming products).  The product library never reads them; the probes load the ablation build
+reads the profiling switches (abl_getenv in bsn_internal.hpp; the slab sweeps BSN_KY / BSN_KY_T /
+BSN_KY_WHOLE of the streaming products).  The product library never reads them; the probes load the ablation build
 through BSN_LIB_PATH.  (The kernel variants that profiles/*ablation*.txt were measured with — no MFMA /
 no decode / no loads ..., wrong numbers by construction — are concluded and no longer built.)
 """

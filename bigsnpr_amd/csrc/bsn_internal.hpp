@@ -18,7 +18,7 @@
 namespace bsn {
 // Switches that only exist in the PROFILING build (python -m bigsnpr_amd.build --ablation, libbigsnpr_hip_abl.so): experiments
 // whose records are under profiles/ (BSN_ZQ_SPLIT, BSN_START_SLICES, BSN_TCROSS_WAVES, BSN_TCROSS_PRIO) beside the slab
-// sweeps BSN_KY / BSN_KY_T of matvec.hip (prod_plan.hpp).  The product library does not read them (README.md lists the switches it does
+// sweeps BSN_KY / BSN_KY_T / BSN_KY_WHOLE of matvec.hip (prod_plan.hpp).  The product library does not read them (README.md lists the switches it does
 // read).  The windowed LD (ld.hip) has none left: DESIGN.md 3.6 says what its seven measured and where the records are.
 inline const char *abl_getenv(const char *name) {
 #ifdef BSN_ABLATION

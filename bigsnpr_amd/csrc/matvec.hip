@@ -790,8 +790,10 @@ __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, i
 //   B operand: lane l -> digit column (l & 15), the same 16 variants: w-digits for the code plane, (c w - 3 w)-digits
 //              for the missing-value plane (k_quant mode 1 with the cprod byte order), BOTH into one accumulator
 //   D        : lane l -> digit column (l & 15), sample rows 4 * (l >> 4) + r
-// The variants are split into gridDim.y slabs of `cps` chunks (int32 partial sums per slab, added by k_prod_final in
-// exact int64 like k_prod's): 782 workgroups of 512 samples alone would fill 3.05 rounds of 256 CUs.
+// The variants are split into slabs of chunks (int32 partial sums per slab, added by k_prod_final in exact int64 like
+// k_prod's) because 782 workgroups of 512 samples alone would fill 3.05 rounds of 256 CUs — but only for the sample blocks
+// beyond the last whole round (14 of the 782, 18 slabs); the blocks of the whole rounds take the planner's ky_whole slabs
+// (prod_plan.hpp: plan_prod, and prodt_slab for the workgroup's place in the one-dimensional grid).
 // The copy is CHUNK-MAJOR (bsn_bed::d_smaj): byte of the operator's first variant in a sample row (col0 / 4, a multiple of 16).
 // NASKIP: as in k_cprod — the missing-value plane of a K-step (16 samples x 64 variants) only when it has a missing code.
 // SPARSE (prodt_sparse.hpp): both planes in ONE v_smfmac_i32_16x16x128_i8 per tile and column block.  Of a genotype's
@@ -802,7 +804,7 @@ __global__ __launch_bounds__(256) void k_prod(const uint8_t *__restrict__ img, i
 // replace 8, measured level in the skeleton of tools/ubench/smfmac_parts.hip — 26.5 ms either way — and is not built.)
 template <int NB, bool HASQ, int TILES = 2, int WAVES = 16, int TAG = 0, int SGB = 3, bool NASKIP = false, bool SPARSE = false>
 __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict__ simg, int64_t rows_t, int64_t chunk0,
-                                                      int nchunks, int cps,
+                                                      const ProdTGrid geo,
                                                       const int8_t *__restrict__ wq, int32_t *__restrict__ acc_out,
                                                       int64_t n_pad, uint32_t lutQ, int seg_bs, int seg_stride, int seg_off) {
   constexpr int KC = 512, NCOL = 16 * NB, LD = KC / 256;
@@ -814,8 +816,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
   const int c = lane & 15, g = lane >> 4;
   // seg_bs > 0 (a segment of the sharded solve's product pass, op_prod_segments): the launch covers blocks
   // [seg_off, seg_off + seg_bs) of every piece of seg_stride blocks
-  const unsigned bx = seg_bs > 0 ? (blockIdx.x / (unsigned)seg_bs) * (unsigned)seg_stride + (unsigned)seg_off + blockIdx.x % (unsigned)seg_bs
-                                 : blockIdx.x;
+  // ... in a grid of (pieces x seg_bs) x geo.ky; every other launch is the one-dimensional grid of prodt_slab (prod_plan.hpp)
+  ProdTSlab sl;
+  if (seg_bs > 0) {
+    sl.bx = (int)((blockIdx.x / (unsigned)seg_bs) * (unsigned)seg_stride + (unsigned)seg_off + blockIdx.x % (unsigned)seg_bs);
+    sl.slab = (int)blockIdx.y;
+    sl.ch_begin = sl.slab * geo.cps;
+    sl.ch_end = sl.ch_begin + geo.cps < geo.nchunks ? sl.ch_begin + geo.cps : geo.nchunks;
+  } else {
+    sl = prodt_slab(geo, blockIdx.x);
+  }
+  const unsigned bx = (unsigned)sl.bx;
   const int64_t wg_base = (int64_t)bx * (WAVES * 16 * TILES);
   const int64_t row_base = wg_base + wave * (16 * TILES);
   uint32_t voff[TILES];
@@ -825,10 +836,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
     if (i > rows_t - 1) i = rows_t - 1;
     voff[t] = (uint32_t)((i - wg_base) * (KC / 4) + g * 16);
   }
-  const int ch_begin = (int)blockIdx.y * cps;
-  int ch_end = ch_begin + cps;
-  if (ch_end > nchunks) ch_end = nchunks;
-  if (ch_begin >= ch_end) return;   // (never: the launch geometry gives every slab at least one chunk)
+  const int ch_begin = sl.ch_begin, ch_end = sl.ch_end;
+  if (ch_begin >= ch_end) return;  // (never: the launch geometry gives every slab at least one chunk)
   if (wg_base >= rows_t) return;    // a workgroup wholly past the copy's rows (a segment's padding blocks): nothing to read or write
   // chunk ch of the slab: the workgroup's 512 sample rows x 128 B are ONE contiguous 64-KB run of the copy
   const int64_t chunk_stride = rows_t * (KC / 4);
@@ -1003,7 +1012,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
       if (i < n_pad) {
 #pragma unroll
         for (int nb = 0; nb < NB; nb++)
-          acc_out[((int64_t)blockIdx.y * n_pad + i) * NCOL + nb * 16 + c] = acc[t][nb][r];
+          acc_out[((int64_t)sl.slab * n_pad + i) * NCOL + nb * 16 + c] = acc[t][nb][r];
       }
     }
 }
@@ -1012,8 +1021,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_prodT(const uint8_t *__restrict_
 // row reads its NCOL contiguous int32 per K-chunk (16 B loads, consecutive rows adjacent).
 // blk_rows > 0: blocked output for the reduce-scatter of a segment (op_prod_segments) — row i belongs to piece
 // i / blk_rows and goes to Y[(piece * nv + v) * blk_rows + i % blk_rows]; rows[i] < 0 is padding (zero).
+// Image rows below rows_whole (k_prodT's whole-round blocks, prod_plan.hpp) have ky_whole slabs, the others ky.
 template <int NCOL>
-__global__ __launch_bounds__(256) void k_prod_final(const int32_t *__restrict__ acc, int64_t n_pad, int ky, int S, int nv,
+__global__ __launch_bounds__(256) void k_prod_final(const int32_t *__restrict__ acc, int64_t n_pad, int ky, int64_t rows_whole,
+                             int ky_whole, int S, int nv,
                              const VecMeta *meta, const int32_t *rows, int64_t n, double *Y,
                              int64_t ldy, int sub_const, double beta, int64_t blk_rows = 0) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1026,7 +1037,8 @@ __global__ __launch_bounds__(256) void k_prod_final(const int32_t *__restrict__ 
   long long d[NCOL];
 #pragma unroll
   for (int c = 0; c < NCOL; c++) d[c] = 0;
-  for (int k = 0; k < ky; k++) {
+  const int slabs = i2 < rows_whole ? ky_whole : ky;
+  for (int k = 0; k < slabs; k++) {
     const int4 *a = (const int4 *)(acc + ((int64_t)k * n_pad + i2) * NCOL);
 #pragma unroll
     for (int c4 = 0; c4 < NCOL / 4; c4++) {
@@ -1037,22 +1049,30 @@ __global__ __launch_bounds__(256) void k_prod_final(const int32_t *__restrict__ 
       d[4 * c4 + 3] += t.w;
     }
   }
-  for (int v = 0; v < nv; v++) {
-    double r = 0;
-    for (int s = S - 1; s >= 0; s--) {
-      long long dv = 0;
+  // Column v S + s is slice s of vector v: ONE walk down the columns (the registers are indexed by the unrolled loop, v and s
+  // are uniform counters), r = r 256 + d from a vector's top slice down to its slice 0 — the operations, in the order, of a
+  // loop over v and s that picks d[v S + s] out of the registers with NCOL selects per slice (which it was: 4 608 selects per
+  // row at 16 vectors x 3 slices, most of the launch once the rows have two slabs to add — profiles/prodt_whole_rounds_ab.txt).
+  int v = (NCOL - 1) / S, s = (NCOL - 1) - v * S;
+  double r = 0;
 #pragma unroll
-      for (int c = 0; c < NCOL; c++) dv = (c == v * S + s) ? d[c] : dv;
-      r = r * 256.0 + (double)dv;
+  for (int c = NCOL - 1; c >= 0; c--) {
+    if (v < nv) {   // (columns nv S and beyond are unused)
+      if (s == S - 1) r = 0;
+      r = r * 256.0 + (double)d[c];
+      if (s == 0) {
+        double C = sub_const ? (double)meta[v].sum2_hi * 16777216.0 + (double)meta[v].sum2_lo : 0.0;
+        double qs = meta[v].qscale;
+        double y = qs > 0 ? (r - C) / qs : 0.0;
+        if (meta[v].nonfinite) y = __longlong_as_double(0x7ff8000000000000LL);
+        if (blk_rows > 0)
+          Y[(i / blk_rows * nv + v) * blk_rows + i % blk_rows] = y;
+        else
+          Y[i + v * ldy] = beta != 0.0 ? beta * Y[i + v * ldy] + y : y;
+      }
     }
-    double C = sub_const ? (double)meta[v].sum2_hi * 16777216.0 + (double)meta[v].sum2_lo : 0.0;
-    double qs = meta[v].qscale;
-    double y = qs > 0 ? (r - C) / qs : 0.0;
-    if (meta[v].nonfinite) y = __longlong_as_double(0x7ff8000000000000LL);
-    if (blk_rows > 0)
-      Y[(i / blk_rows * nv + v) * blk_rows + i % blk_rows] = y;
-    else
-      Y[i + v * ldy] = beta != 0.0 ? beta * Y[i + v * ldy] + y : y;
+    if (s == 0) s = S - 1, v--;
+    else s--;
   }
 }
 
@@ -1744,13 +1764,15 @@ static void launch_prod(bsn_op *op, int NB, dim3 grid, int64_t m_pad, int64_t mc
 
 // One launch of k_prodT on the sample-major copy: the instance that choose_prodT (prod_plan.hpp) names.
 // (workgroup shapes 4 x 8 / 4 x 4 / 2 x 8 / 4 x 16 tiles x waves, chunks of 256 variants: all slower, profiles/r04_sample_major.txt)
-static void launch_prodT(bsn_op *op, const ProdTKernel &k, dim3 grid, int nchunks, int cps, const int8_t *q, int32_t *acc,
+// seg_bs > 0: a segment's two-dimensional grid `seg_grid`; otherwise the one-dimensional grid of `geo` (prodt_slab)
+static void launch_prodT(bsn_op *op, const ProdTKernel &k, const ProdTGrid &geo, dim3 seg_grid, const int8_t *q, int32_t *acc,
                          int64_t npad, uint32_t lutQ, int seg_bs, int seg_stride, int seg_off) {
   bsn_bed *b = op->bed;
+  const dim3 grid = seg_bs > 0 ? seg_grid : dim3((unsigned)prodt_workgroups(geo));
 #define BSN_PRODT(NBV, HASQV, TAGV, SGBV, NASKIPV, SPARSEV)                                                           \
   if (k == ProdTKernel{NBV, HASQV, TAGV, SGBV, NASKIPV, SPARSEV}) {                                                   \
     BSN_KLAUNCH((k_prodT<NBV, HASQV, 2, 16, TAGV, SGBV, NASKIPV, SPARSEV>), grid, dim3(1024), 0, b->stream, b->d_smaj, \
-                b->rows_smaj, op->col0 / 512, nchunks, cps, q, acc, npad, lutQ, seg_bs, seg_stride, seg_off);         \
+                b->rows_smaj, op->col0 / 512, geo, q, acc, npad, lutQ, seg_bs, seg_stride, seg_off);                  \
     BSN_HIP(hipGetLastError());                                                                                       \
     return;                                                                                                           \
   }
@@ -1764,12 +1786,14 @@ static void launch_prodT(bsn_op *op, const ProdTKernel &k, dim3 grid, int nchunk
 }
 
 // y = finalize of a product launch of NB column blocks over `rows` output rows (blk_rows > 0: a segment's blocked output)
-static void launch_prod_final(bsn_bed *b, int NB, const int32_t *acc, int64_t npad, int ky, int S, int nv, const VecMeta *meta,
+// (rows_whole > 0: the image rows of k_prodT's whole-round blocks, which have ky_whole slabs)
+static void launch_prod_final(bsn_bed *b, int NB, const int32_t *acc, int64_t npad, int ky, int64_t rows_whole, int ky_whole, int S,
+                              int nv, const VecMeta *meta,
                               const int32_t *d_rows, int64_t rows, double *Y, int64_t ldy, int sub_const, double beta,
                               int64_t blk_rows) {
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, b->stream, acc, npad, ky, S, nv, meta, d_rows,
-                       rows, Y, ldy, sub_const, beta, blk_rows);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, b->stream, acc, npad, ky, rows_whole, ky_whole, S,
+                       nv, meta, d_rows, rows, Y, ldy, sub_const, beta, blk_rows);
   };
   if (NB == 1) go(k_prod_final<16>);
   else if (NB == 2) go(k_prod_final<32>);
@@ -1818,9 +1842,13 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
   f.no_sparse = getenv("BSN_NO_SPARSE_PROD") != nullptr;   // (A/B switch, bit-identical; read on every call)
   f.nvec = nvec, f.S = S, f.segmented = sg != nullptr;
   if (f.have_smaj) f.ncu = device_cus();
+  // BSN_PLAN_CUS=<n>: the CU count the planner assumes (small shapes never fill a round of 256 CUs: with 4 they take
+  // k_prodT's whole-round geometry, tests/test_gpu_prodt_whole.py; same sums, read on every call)
+  if (const char *e = getenv("BSN_PLAN_CUS")) f.ncu = std::max(1, atoi(e));
 #ifdef BSN_ABLATION
   if (const char *e = getenv("BSN_KY")) f.ky = std::max(1, atoi(e));      // slab sweeps (correct results)
   if (const char *e = getenv("BSN_KY_T")) f.ky_t = std::max(1, atoi(e));
+  if (const char *e = getenv("BSN_KY_WHOLE")) f.ky_whole = std::max(1, atoi(e));
 #endif
   const ProdPlan pl = plan_prod(f);
   if (pl.refuse == ProdRefusal::pitch_limit) fail("more than 6.7e7 samples are not supported by the product kernel");
@@ -1829,6 +1857,11 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
   const int vmax = pl.vmax, ky = pl.ky, smaj_cps = pl.smaj_cps;
   const int64_t npad = n_padded(b), m_pad = pl.m_pad, mc = pl.mc;
   if (smaj && (int64_t)ky * smaj_cps < m_pad / 512) fail("internal: the slabs of k_prodT do not cover the variants");
+  if (smaj && pl.wgx_whole > 0 && (int64_t)pl.ky_whole * pl.cps_whole < m_pad / 512)
+    fail("internal: the slabs of k_prodT's whole rounds do not cover the variants");
+  // (k_prodT: image rows below rows_whole have ky_whole slabs; k_prod's launches have no such rows)
+  const int64_t rows_whole = smaj ? pl.wgx_whole * 512 : 0;
+  const int ky_whole = smaj ? pl.ky_whole : 0;
   VecMeta *meta = meta_buffer(op);
   const bool warm = op->prof_kind_override == 3;   // warm-start launches run under their own kernel name (TAG = 1)
   for (int v0 = 0; v0 < nvec; v0 += vmax) {
@@ -1836,7 +1869,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
     int NB = pick_nb(nv * S), ncol = 16 * NB;
     const ProdTKernel kt = choose_prodT(NB, has_q, warm, op->na_skip_p, pl.sparse_ok);   // (read where smaj && NB >= 2)
     int8_t *q = op->d_q.ensure((size_t)(npad > m_pad ? npad : m_pad) * kMaxCols * 2);
-    size_t acc_need = (size_t)ky * npad * ncol;
+    size_t acc_need = (size_t)std::max(ky, ky_whole) * npad * ncol;
     if (acc_need < (size_t)2 * op->m * kMaxCols) acc_need = (size_t)2 * op->m * kMaxCols;
     int32_t *acc = op->d_acc.ensure(acc_need);
     // (k_prodT decodes like k_cprod: its digit rows take the crossproduct's byte order; the sparse form its own)
@@ -1845,7 +1878,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
     dim3 grid((unsigned)pl.wgx, (unsigned)ky);
     prof_begin(op, NB == 3 ? 5 : 1);
     if (smaj && NB >= 2) {
-      const int nchunks = (int)(m_pad / 512);
+      const ProdTGrid geo = prodt_grid(pl);
       if (sg) {
         // the pass in segments of sample blocks: kernel + finalize of a segment, then the caller's hook (svd.hip queues the
         // segment's reduce-scatter on its second stream) while the next segment's kernel is queued behind on this one
@@ -1853,17 +1886,17 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
           const ProdSegment &sgm = sg->segs[sidx];
           const dim3 gs((unsigned)(sg->pieces * sgm.bs), (unsigned)ky);
           if (sidx > 0) prof_begin(op, NB == 3 ? 5 : 1, true);
-          launch_prodT(op, kt, gs, nchunks, smaj_cps, q, acc, npad, lutQ, sgm.bs, sg->stride, sgm.off);
+          launch_prodT(op, kt, geo, gs, q, acc, npad, lutQ, sgm.bs, sg->stride, sgm.off);
           prof_end(op);
           const int64_t rows_s = (int64_t)sgm.bs * 512, tot = rows_s * sg->pieces;
-          launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, sgm.d_rows, tot, sgm.d_out, 0, sub_const, 0.0, rows_s);
+          launch_prod_final(b, NB, acc, npad, ky, 0, 0, S, nv, meta, sgm.d_rows, tot, sgm.d_out, 0, sub_const, 0.0, rows_s);
           (*sg->after)(sidx);
         }
         op->passes++;
         sg->done = true;
         continue;
       }
-      launch_prodT(op, kt, grid, nchunks, smaj_cps, q, acc, npad, lutQ, 0, 0, 0);
+      launch_prodT(op, kt, geo, dim3(), q, acc, npad, lutQ, 0, 0, 0);
     } else if (NB > 2) {
       fail("internal: three column blocks without the sample-major copy");
     } else if (b->bits == 8) {
@@ -1887,7 +1920,7 @@ static void prod_planes(bsn_op *op, const double *d_X, const double *d_W2, int64
     prof_end(op);
     op->last_kernel = g_last_kernel;
     op->passes++;
-    launch_prod_final(b, NB, acc, npad, ky, S, nv, meta, op->rows(), op->n,
+    launch_prod_final(b, NB, acc, npad, ky, rows_whole, ky_whole, S, nv, meta, op->rows(), op->n,
                       d_Y + (int64_t)v0 * ldy, ldy, sub_const, beta, 0);
   }
 }

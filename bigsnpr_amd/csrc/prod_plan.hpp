@@ -1,11 +1,18 @@
 // prod_plan.hpp — the launch geometry of the streaming products (matvec.hip: prod_planes, op_cprod) and which instance of
 // k_cprod / k_prod / k_prodT a launch takes, decided from plain facts.
-// No HIP in here: tests/native pins the geometry and the choices on the CPU (tests/test_prod_plan_cpu.py).
+// No HIP in here but the __host__ __device__ mark of prodt_slab, which k_prodT compiles as it stands: tests/native pins the
+// geometry and the choices on the CPU (tests/test_prod_plan_cpu.py, tests/test_prodt_grid_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
 
 #include "byte_plan.hpp"
+
+#if defined(__HIPCC__)
+#define BSN_PLAN_HD __host__ __device__ inline
+#else
+#define BSN_PLAN_HD inline
+#endif
 
 namespace bsn {
 // Column blocks of 16 digit columns per launch.  Three (48 columns: 16 vectors x 3 slices, the early steps of a solve
@@ -39,6 +46,7 @@ struct ProdFacts {
   int ncu = 256;                 // compute units of the device
   bool segmented = false;        // a pass in segments of sample blocks (op_prod_segments): k_prodT only
   int ky = 0, ky_t = 0;          // profiling build: the slab sweeps BSN_KY (k_prod) / BSN_KY_T (k_prodT); 0 = the rule
+  int ky_whole = 0;              // profiling build: BSN_KY_WHOLE, the slabs of k_prodT's whole-round blocks; 0 = the rule
 };
 
 enum class ProdRefusal { none, pitch_limit, nothing_queued };
@@ -51,9 +59,56 @@ struct ProdPlan {
   int64_t wgx = 0;          // workgroups along the samples
   int ky = 1;               // slabs of variants (the grid's y; int32 partial sums per slab)
   int smaj_cps = 0;         // k_prodT: chunks of 512 variants per slab
+  // k_prodT: sample blocks 0 .. wgx_whole - 1 fill whole rounds of the CUs and take ky_whole slabs of cps_whole chunks;
+  // ky x smaj_cps is then the split of the blocks wgx_whole .. wgx - 1 alone.  wgx_whole = 0: every block takes ky x smaj_cps
+  int64_t wgx_whole = 0;
+  int ky_whole = 0, cps_whole = 0;
   int64_t mc = 0;           // k_prod / k_prod8: variants per slab
   bool sparse_ok = false;   // k_prodT<3> may run in its sparse form (prodt_sparse.hpp)
 };
+
+// Slabs of the sample blocks of k_prodT that fill whole rounds of the CUs (0: no second split, every block takes ky slabs).
+// Measured at 400 000 x 1 000 000 against 2, 3 and the split of every block: profiles/prodt_whole_rounds_ab.txt.
+constexpr int kProdTWholeSlabs = 2;
+
+// k_prodT's grid has ONE dimension: first the whole-round blocks slab by slab (as the two-dimensional grid ran them: all the
+// blocks of a slab side by side, so the workgroups in flight read the same chunks of the digit panel), then the remainder
+// blocks slab by slab — last, so that the CUs which finish their long workgroups first pick up the short ones.
+struct ProdTGrid {
+  int wgx, wgx_whole;       // sample blocks; those of the whole rounds
+  int ky_whole, cps_whole;  // slabs / chunks per slab of blocks 0 .. wgx_whole - 1
+  int ky, cps;              // of blocks wgx_whole .. wgx - 1
+  int nchunks;              // chunks of 512 variants of the pass
+};
+struct ProdTSlab {
+  int bx, slab;             // sample block; slab (the accumulator's first index)
+  int ch_begin, ch_end;     // its chunks
+};
+inline ProdTGrid prodt_grid(const ProdPlan &p) {   // (of a plan with p.smaj)
+  return {(int)p.wgx, (int)p.wgx_whole, p.ky_whole, p.cps_whole, p.ky, p.smaj_cps, (int)(p.m_pad / 512)};
+}
+BSN_PLAN_HD int64_t prodt_workgroups(const ProdTGrid &g) {
+  return (int64_t)g.wgx_whole * g.ky_whole + (int64_t)(g.wgx - g.wgx_whole) * g.ky;
+}
+// workgroup wg of the grid -> (sample block, slab, first chunk, end chunk); shared by k_prodT and tests/native
+BSN_PLAN_HD ProdTSlab prodt_slab(const ProdTGrid &g, uint32_t wg) {
+  const uint32_t nwhole = (uint32_t)g.wgx_whole * (uint32_t)g.ky_whole;
+  ProdTSlab s;
+  int cps;
+  if (wg < nwhole) {
+    s.slab = (int)(wg / (uint32_t)g.wgx_whole);
+    s.bx = (int)(wg - (uint32_t)s.slab * (uint32_t)g.wgx_whole);
+    cps = g.cps_whole;
+  } else {
+    const uint32_t r = wg - nwhole, nrest = (uint32_t)(g.wgx - g.wgx_whole);
+    s.slab = (int)(r / nrest);
+    s.bx = g.wgx_whole + (int)(r - (uint32_t)s.slab * nrest);
+    cps = g.cps;
+  }
+  s.ch_begin = s.slab * cps;
+  s.ch_end = s.ch_begin + cps < g.nchunks ? s.ch_begin + cps : g.nchunks;
+  return s;
+}
 
 inline ProdPlan plan_prod(const ProdFacts &f) {
   ProdPlan p;
@@ -96,7 +151,9 @@ inline ProdPlan plan_prod(const ProdFacts &f) {
     // image's bytes per slab at 400K x 1M, 1.2 % on the 125 000-variant shard of an 8-GPU run, where 18 slabs (the best
     // fill) measured 3.93 ms per pass against 3.80 - 3.82 with 8 - 10 (round 6, profiles/r06_shard_slabs.txt: the traffic
     // weighs about 0.3 of its bytes — the writes drain beside the stream).  At 400 000 x 1 000 000 on 256 CUs the rule
-    // gives 18 slabs of 109 chunks (782 x 18 workgroups = 54.98 rounds) for two and for three column blocks.
+    // gives 18 slabs of 109 chunks (782 x 18 workgroups = 54.98 rounds) for two and for three column blocks.  Since the
+    // second split below only the blocks beyond the last whole round take this split (14 of the 782); the rule and its
+    // fields are as they were, and where there is no second split they describe every block.
     const double slab_cost = 0.3 * 2.0 * (double)npad * 16.0 * nb_max * 4.0 / ((double)m_pad * (double)(f.pitch));
     int best = 1;
     double best_score = -1e300;
@@ -113,6 +170,22 @@ inline ProdPlan plan_prod(const ProdFacts &f) {
     if (ky < ky_min2) ky = (int)ky_min2;
     smaj_cps = (int)((nchunks + ky - 1) / ky);
     ky = (int)((nchunks + smaj_cps - 1) / smaj_cps);
+    // The split above exists only because the sample blocks alone do not fill whole rounds (782 = 3.05 x 256).  The first
+    // wgx / ncu rounds of blocks are whole rounds whatever their slab count, so they take kProdTWholeSlabs slabs (each
+    // block streams all, or half, ... of the variants in one workgroup: 1 / ky of the partial sums, of k_prod_final's
+    // reads and of the workgroup prologues) and ky x smaj_cps is the split of the remainder blocks alone, which are
+    // launched last (prodt_slab).  Not for a pass in segments (their blocks are pieces x bs, interleaved) nor where the
+    // blocks are less than one round.  ONE slab is not the best count: a workgroup then holds its CU for a third of the
+    // pass, and the kernels a solve queues on its second stream beside the pass (svd.hip: the early Rayleigh-Ritz guess)
+    // get a CU only where a workgroup ends.  A/B of 1, 2, 3 and the split of every block: profiles/prodt_whole_rounds_ab.txt.
+    if (!f.segmented && kProdTWholeSlabs + f.ky_whole > 0 && wgx >= ncu) {
+      p.wgx_whole = wgx / ncu * ncu;
+      int kw = f.ky_whole > 0 ? f.ky_whole : kProdTWholeSlabs;   // (BSN_KY_WHOLE: the sweep of the profiling build)
+      // (a slab of whole chunks below 2.5e6 variants: 4 882 chunks at most, which is at least ky_min2 slabs)
+      kw = (int)std::max<int64_t>(std::min<int64_t>(kw, nchunks), (nchunks + 4881) / 4882);
+      p.cps_whole = (int)((nchunks + kw - 1) / kw);
+      p.ky_whole = (int)((nchunks + p.cps_whole - 1) / p.cps_whole);
+    }
   }
   if (!smaj) {   // (k_prodT's slab count and chunks per slab were fixed together above: clamping one would drop chunks)
     if (ky > steps) ky = (int)steps;
