@@ -1,9 +1,10 @@
 """Inputs of the BGEN tests (tests/test_inflate_cpu.py, tests/test_bgen_cpu.py, tests/test_gpu_bgen.py): a reader for
 the R raw vectors that hold the reference's example .bgen / .bgi files (and for the matrix of its dosages), a writer of BGEN v1.2 files (layout 2, zlib,
-8 bits) with their .bgi index, a small deflate emitter for stored and fixed-Huffman blocks from an explicit list of
-literals and (length, distance) pairs — zlib itself never emits a distance above 32 506, so the limits are hit on purpose
-with it —, the corpus of valid streams, the fixed list of malformed ones, and the decode of a file through Python's zlib
-that the device results are held against."""
+8 bits) with their .bgi index, a small deflate emitter for stored, fixed-Huffman and dynamic-Huffman blocks from an
+explicit list of literals and (length, distance) pairs — zlib itself never emits a distance above 32 506, a 15-bit code
+on a few byte values or a one-code distance set, so the limits are hit on purpose with it —, the corpus of valid
+streams, the fixed list of malformed ones, the one stream zlib accepts and the statement refuses, and the decode of a
+file through Python's zlib that the device results are held against."""
 import gzip
 import os
 import sqlite3
@@ -155,6 +156,124 @@ def emit(tokens):
     return zlib_wrap(w, content), content
 
 
+def token_spans(tokens, start=0):
+    """[(pos, len, dist)] of the matches of a token list whose first byte is byte `start` of the output"""
+    pos, out = start, []
+    for t in tokens:
+        if isinstance(t, int):
+            pos += 1
+        elif t[0] != "raw":
+            out.append((pos, t[0], t[1]))
+            pos += t[0]
+    return out
+
+
+def flush_spans(tokens, flush_bytes=2048):
+    """[(flushed, pos)] of the flushes a sink takes that empties its pending bytes after every token of a Huffman block
+    once `flush_bytes` or more are waiting (k_inflate's: kFlushBytes), the final one included"""
+    pos, flushed, out = 0, 0, []
+    for t in tokens:
+        pos += 1 if isinstance(t, int) else t[0]
+        if pos - flushed >= flush_bytes:
+            out.append((flushed, pos))
+            flushed = pos
+    return out + [(flushed, pos)]
+
+
+# ---- dynamic blocks ----------------------------------------------------------------------------------------------------------
+_CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+CL_LENS = [4] * 10 + [5] * 6 + [4] * 3   # a complete code-length code: 13 codes of 4 bits, 6 of 5 (13 / 16 + 6 / 32 = 1)
+
+
+def canonical(lens):
+    """RFC 1951 3.2.2: {symbol: (code, bits)} of the symbols with a non-zero length.  Nothing is checked: an
+    over-subscribed list gives codes that do not fit their length, an incomplete one leaves codes unused."""
+    count = [0] * (max(list(lens) + [0]) + 2)
+    for n in lens:
+        if n:
+            count[n] += 1
+    code, nxt = 0, [0] * len(count)
+    for n in range(1, len(count)):
+        code = (code + count[n - 1]) << 1
+        nxt[n] = code
+    out = {}
+    for s, n in enumerate(lens):
+        if n:
+            out[s] = (nxt[n], n)
+            nxt[n] += 1
+    return out
+
+
+def lens_of(d, n):
+    """a list of n code lengths from {symbol: length}"""
+    out = [0] * n
+    for s, v in d.items():
+        out[s] = v
+    return out
+
+
+def dynamic_block(w, tokens, lit_lens, dist_lens, last=True, cl_syms=None, cl_lens=None):
+    """one dynamic-Huffman block.  lit_lens / dist_lens: the code lengths of the literal/length symbols 0 .. and of the
+    distance symbols 0 .., whose counts go into HLIT / HDIST as they are.  cl_syms: the code lengths as (symbol, repeat)
+    pairs of the code-length alphabet — (0 .. 15, 1) a length, (16, 3 .. 6) the previous one again, (17, 3 .. 10) and
+    (18, 11 .. 138) zeros; default: every length as its own symbol.  cl_lens: the 19 lengths of the code-length code
+    (default CL_LENS).  tokens: literals, (length, distance) pairs, (length, None) = the length symbol alone, ("raw", v, n)
+    = n bits as they are; the end-of-block code follows them.  tokens=None: the header and the code lengths only.
+    Nothing is checked and nothing raises: a symbol that has no code is left out."""
+    cl_lens = CL_LENS if cl_lens is None else cl_lens
+    if cl_syms is None:
+        cl_syms = [(n, 1) for n in list(lit_lens) + list(dist_lens)]
+    ncode = max([4] + [i + 1 for i in range(19) if cl_lens[_CL_ORDER[i]]])
+    w.bits(1 if last else 0, 1)
+    w.bits(2, 2)
+    w.bits(len(lit_lens) - 257, 5)
+    w.bits(len(dist_lens) - 1, 5)
+    w.bits(ncode - 4, 4)
+    for i in range(ncode):
+        w.bits(cl_lens[_CL_ORDER[i]], 3)
+    cl = canonical(cl_lens)
+    for s, rep in cl_syms:
+        if s in cl:
+            w.code(*cl[s])
+        if s == 16:
+            w.bits(rep - 3, 2)
+        elif s == 17:
+            w.bits(rep - 3, 3)
+        elif s == 18:
+            w.bits(rep - 11, 7)
+    if tokens is None:
+        return
+    lit, dst = canonical(lit_lens), canonical(dist_lens)
+
+    def put(codes, s):
+        if s in codes:
+            w.code(*codes[s])
+
+    for t in tokens:
+        if isinstance(t, int):
+            put(lit, t)
+        elif t[0] == "raw":
+            w.bits(t[1], t[2])
+        else:
+            ln, dist = t
+            s = 28 if ln == 258 else max(i for i in range(28) if _LBASE[i] <= ln)
+            put(lit, 257 + s)
+            w.bits(ln - _LBASE[s], _LEXT[s])
+            if dist is not None:
+                d = max(i for i in range(30) if _DBASE[i] <= dist)
+                put(dst, d)
+                w.bits(dist - _DBASE[d], _DEXT[d])
+    put(lit, 256)
+
+
+def emit_dynamic(tokens, lit_lens, dist_lens, **kw):
+    """a zlib stream of one dynamic block from the tokens, and what it inflates to"""
+    w = BitWriter()
+    dynamic_block(w, tokens, lit_lens, dist_lens, **kw)
+    content = apply_tokens(tokens)
+    return zlib_wrap(w, content), content
+
+
 # ---- the corpus ------------------------------------------------------------------------------------------------------------------
 def _data(n, seed=1):
     """compressible bytes: a few values, runs, and the odd repeat far back"""
@@ -170,6 +289,70 @@ def _compress(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, flush_at=None):
     if flush_at is None:
         return c.compress(data) + c.flush()
     return c.compress(data[:flush_at]) + c.flush(zlib.Z_FULL_FLUSH) + c.compress(data[flush_at:]) + c.flush()
+
+
+SPECS = {}   # name -> what the stream was emitted from (tokens of the whole stream from byte 0, code lengths): the claims
+             # of test_corpus_covers_what_it_claims are read off these, which corpus() has held against zlib
+
+
+def _dynamic_and_ring_cases():
+    """dynamic blocks that zlib's compressor does not produce, and matches and flushes at the edges of k_inflate's ring
+    and flush sizes (32 768 and kFlushBytes = 2 048)"""
+    out = []
+
+    def add(name, pair, **spec):
+        SPECS[name] = spec
+        out.append((name,) + pair)
+
+    # code lengths 1 .. 14 on fourteen byte values, 15 on one more and on the end of the block: a complete set
+    vals = [0, 255, 1, 254, 17, 128, 7, 64, 200, 33, 99, 150, 222, 5]
+    lit = lens_of(dict([(v, k + 1) for k, v in enumerate(vals)] + [(77, 15), (256, 15)]), 257)
+    tokens = [(vals + [77])[(7 * k) % 15] for k in range(90)]
+    add("dyn_lit15", emit_dynamic(tokens, lit, [0]), tokens=tokens, lit_lens=lit, dist_lens=[0])
+    # the one incomplete set the statement accepts: a single distance code of one bit
+    lit = lens_of({97: 2, 98: 2, 256: 2, 257: 2}, 258)
+    tokens = [97, (3, 1), 98, (3, 1), 97, 98, (3, 1)]
+    add("dyn_one_dist", emit_dynamic(tokens, lit, [1]), tokens=tokens, lit_lens=lit, dist_lens=[1])
+    # ... on distance symbol 29 with 286 + 30 lengths: both counts at their limits, 13 extra bits
+    lit = [9] * 256 + [2] + [0] * 28 + [2]
+    tokens = list(_data(32768, 12)) + [(258, 32768), (258, 24577)]
+    add("dyn_one_dist_29", emit_dynamic(tokens, lit, [0] * 29 + [1]), tokens=tokens, lit_lens=lit, dist_lens=[0] * 29 + [1])
+    # a run of symbol 16 that starts in the literal/length lengths and ends in the distance lengths
+    lit, dist = [1] + [0] * 255 + [2, 2], [2, 2, 2, 2]
+    cl_syms = [(1, 1), (18, 138), (18, 117), (2, 1), (16, 5)]
+    tokens = [0, (3, 1), 0, 0, (3, 2), 0, (3, 3), 0, (3, 4)]
+    add("dyn_run_crosses", emit_dynamic(tokens, lit, dist, cl_syms=cl_syms), tokens=tokens, lit_lens=lit, dist_lens=dist,
+        cl_syms=cl_syms)
+    # two dynamic blocks with different code sets; the second one's first match reaches into the bytes of the first
+    lit1 = lens_of(dict([(v, 4) for v in range(0x61, 0x69)] + [(256, 3), (257, 3), (258, 2)]), 259)
+    t1 = list(b"abcdefgh") + [(4, 3)] + list(b"hgfedcba") + [(3, 1), (4, 4)] + list(b"abcabcabhhgg") + [(4, 2), (3, 4)]
+    lit2 = lens_of({0x30: 3, 0x31: 3, 0x32: 3, 0x33: 3, 256: 2, 264: 3, 285: 3}, 286)
+    dist2 = [0] * 6 + [3] * 8
+    n1 = len(apply_tokens(t1))
+    t2 = [(10, n1 - 5), 0x30, 0x31, 0x32, 0x33, (258, 9), 0x33, (10, 100)]
+    w = BitWriter()
+    dynamic_block(w, t1, lit1, [2, 2, 2, 2], last=False)
+    dynamic_block(w, t2, lit2, dist2, last=True)
+    content = apply_tokens(t1 + t2)
+    add("dyn_two_tables", (zlib_wrap(w, content), content), tokens=t1 + t2, first_block_bytes=n1, lit_lens=lit1,
+        lit_lens2=lit2)
+    # a match whose destination straddles the end of the ring
+    tokens = list(_data(32700, 13)) + [(258, 50), 7]
+    add("ring_end_dest", emit(tokens), tokens=tokens)
+    # ... whose source straddles 32 768 while its destination straddles 65 536
+    tokens = (list(_data(32768, 14)) + [(258, 30000 + 17 * i) for i in range(100)] + list(_data(6838, 15))
+              + [(258, 32768), 9])
+    add("ring_end_both", emit(tokens), tokens=tokens)
+    # the largest flush, 2 047 + 258 bytes, and then one of exactly 2 048 that a match completes
+    tokens = list(_data(2047, 16)) + [(258, 2047)] + list(_data(1790, 17)) + [(258, 100), 1, 2, 3]
+    add("flush_2305", emit(tokens), tokens=tokens)
+    # i % dist over all five passes of the 64 lanes
+    tokens = list(_data(300, 18)) + [(258, 63), 5, (258, 65), 6, (258, 129), 7, (258, 257)]
+    add("periodic_258", emit(tokens), tokens=tokens)
+    # both Adler sums near 65 521 for the whole stream
+    tokens = [255] + [(258, 1)] * 271
+    add("adler_ff", emit(tokens), tokens=tokens)
+    return out
 
 
 _corpus = None
@@ -207,6 +390,8 @@ def corpus():
     fixed_block(w, [(20, 100), 7], last=True)
     content = apply_tokens([7], apply_tokens([(20, 100)], apply_tokens([1, 2, (50, 300), (258, 2)], start)))
     out.append(("stored_then_fixed", zlib_wrap(w, content), content))
+    out += _dynamic_and_ring_cases()
+    assert max(len(c[2]) for c in out) <= 70000
     for name, s, c in out:
         assert zlib.decompress(s) == c, name
     _corpus = out
@@ -250,6 +435,7 @@ def malformed():
     out.append(("length_symbol_286", zlib_wrap(w, b"A"), 300, 300, 4))
     w = BitWriter(); w.bits(1, 1); w.bits(1, 2); _fixed_litlen(w, 65); _fixed_litlen(w, 257); w.code(30, 5)
     out.append(("distance_symbol_30", zlib_wrap(w, b"A"), 300, 300, 4))
+    out += [(name, s, 10, 10, 4) for name, s in _malformed_dynamic()]
     for name, s, cap, exp, status in out:
         if status != 7:   # zlib refuses them too (a wrong expected length is the caller's business)
             try:
@@ -259,6 +445,43 @@ def malformed():
             assert not ok, name
     _malformed = out
     return out
+
+
+def _malformed_dynamic():
+    """[(name, stream)]: dynamic blocks that zlib and the statement (status 4) both refuse.  Where the fault is in the
+    header or in the code lengths, the stream stops there; the four trailer bytes leave enough bits for a symbol that
+    matches no code to be read to its end."""
+    ok_lit = lens_of({97: 1, 256: 2, 257: 2}, 258)
+    cases = [
+        ("dyn_16_first", dict(tokens=None, lit_lens=ok_lit, dist_lens=[1], cl_syms=[(16, 3)])),
+        ("dyn_repeat_overruns", dict(tokens=None, lit_lens=ok_lit[:257], dist_lens=[1], cl_syms=[(18, 138), (18, 138)])),
+        ("dyn_no_end_of_block", dict(tokens=None, lit_lens=lens_of({97: 1, 98: 1}, 257), dist_lens=[0])),
+        ("dyn_incomplete_lit", dict(tokens=None, lit_lens=lens_of({97: 2, 256: 2}, 257), dist_lens=[0])),
+        ("dyn_incomplete_dist", dict(tokens=None, lit_lens=ok_lit, dist_lens=[2, 2])),
+        ("dyn_oversubscribed_lit", dict(tokens=None, lit_lens=lens_of({97: 1, 98: 1, 256: 1}, 257), dist_lens=[0])),
+        ("dyn_oversubscribed_dist", dict(tokens=None, lit_lens=ok_lit, dist_lens=[1, 1, 1])),
+        ("dyn_incomplete_cl", dict(tokens=None, lit_lens=ok_lit, dist_lens=[1], cl_syms=[], cl_lens=lens_of({0: 1, 18: 2}, 19))),
+        ("dyn_hlit_30", dict(tokens=None, lit_lens=lens_of({97: 1, 256: 1}, 287), dist_lens=[0], cl_syms=[])),
+        ("dyn_hdist_30", dict(tokens=None, lit_lens=ok_lit, dist_lens=[0] * 30 + [1], cl_syms=[])),
+        ("dyn_length_without_dist_code", dict(tokens=[97, (3, None)], lit_lens=ok_lit, dist_lens=[0])),
+        ("dyn_one_dist_unused_code", dict(tokens=[97, (3, None), ("raw", 1, 1)], lit_lens=ok_lit, dist_lens=[1])),
+    ]
+    out = []
+    for name, kw in cases:
+        w = BitWriter()
+        dynamic_block(w, kw.pop("tokens"), kw.pop("lit_lens"), kw.pop("dist_lens"), **kw)
+        out.append((name, zlib_wrap(w, b"")))
+    return out
+
+
+def deviations():
+    """[(name, stream, out_cap, expected_len, status)]: what zlib accepts and the statement refuses (inflate_step.hpp,
+    DESIGN.md 3.5m) — a literal/length set that holds only the end-of-block code, at one bit.  zlib gives b"" for it."""
+    w = BitWriter()
+    dynamic_block(w, [], [0] * 256 + [1], [0])
+    s = zlib_wrap(w, b"")
+    assert zlib.decompress(s) == b""
+    return [("dyn_only_end_of_block", s, 0, 0, 4)]
 
 
 def _bad_distance():

@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
 import bgen_inputs as bi  # noqa: E402
+from bgen_cases import check_product  # noqa: E402
 import bgen_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +75,7 @@ def test_inflate_many_streams_in_one_call(ba, count):
 def test_inflate_malformed_list(ba):
     """the fixed list only (where room and expected length are one number, as in bsn_inflate's signature), between valid
     streams that must come out untouched"""
-    bad = [m for m in bi.malformed() if m[2] == m[3]]
+    bad = [m for m in bi.malformed() + bi.deviations() if m[2] == m[3]]
     good = bi.corpus()[1]
     streams, lens = [good[1]], [len(good[2])]
     for m in bad:
@@ -291,22 +292,6 @@ def test_random_calls(ba, tmp_path):
 
 
 # ---- 5. snp_prodBGEN ------------------------------------------------------------------------------------------------------------
-def check_product(got, X, beta):
-    """|got - X beta| <= 4 m 2^-53 sum_j |x_ij| |beta_jc| per entry (the standard summation bound: both sides sum m
-    products in fp64 in some order); NaN rows are exactly the samples with a missing value"""
-    beta2 = beta[:, None] if beta.ndim == 1 else beta
-    got2 = got[:, None] if got.ndim == 1 else got
-    assert got2.shape == (X.shape[0], beta2.shape[1])
-    nan_row = np.isnan(X).any(axis=1)
-    assert np.array_equal(np.isnan(got2), np.repeat(nan_row[:, None], beta2.shape[1], axis=1))
-    ok = ~nan_row
-    want = X[ok] @ beta2
-    bound = 4 * X.shape[1] * 2.0 ** -53 * (np.abs(X[ok]) @ np.abs(beta2))
-    err = np.abs(got2[ok] - want)
-    print("snp_prodBGEN: max error %.3g, max error / bound %.3g" % (err.max(initial=0.0), (err / np.maximum(bound, 1e-300)).max(initial=0.0)))
-    assert (err <= bound).all()
-
-
 @pytest.fixture(scope="module")
 def prod_file(tmp_path_factory):
     N, K = 257, 120
