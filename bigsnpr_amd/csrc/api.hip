@@ -408,6 +408,18 @@ int bsn_op_last_kernel(bsn_op *op, char *buf, int64_t len) {
   });
 }
 
+// The grid (prod_plan.hpp: CprodGrid) the first k_cprod launch of bsn_op_cprod over nvec vectors would take now; nothing runs.
+// out9: blocks of variants, those of the whole rounds, slabs and chunks per slab of the blocks beyond them, chunks, variants of
+// those blocks; then what the plan was made from: variants per workgroup, CUs (BSN_PLAN_CUS), workgroups of the kernel a CU
+// holds — three zeros for a launch that keeps one workgroup per block.  A hook of tests/test_gpu_cprod_whole.py, which binds
+// it itself: not part of the header's ABI, so that the Python side still loads an older build through BSN_LIB_PATH.
+int bsn_op_cprod_grid(bsn_op *op, int nvec, int64_t *out9) {
+  return guarded([&] {
+    if (!out9) fail("bsn_op_cprod_grid: no buffer");
+    op_cprod_grid(op, nvec, out9);
+  });
+}
+
 // ---- operator -------------------------------------------------------------------
 int bsn_op_create(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col,
                   int64_t m, const double *center, const double *scale, bsn_op **out) {

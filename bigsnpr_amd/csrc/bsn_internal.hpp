@@ -544,6 +544,7 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
 // does it while the host still works on the previous step); op_cprod with the same panel then starts with
 // its streaming kernel.  Any other product on the operator forgets the digits.
 void op_cprod_prequant(bsn_op *op, const double *d_X, int64_t ldx, int nvec);
+void op_cprod_grid(bsn_op *op, int nvec, int64_t *out);   // the grid op_cprod's first launch would take (9 words, matvec.hip)
 void op_cprod_raw(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_P, double *d_Q,
                   int64_t ld);  // P = sum_i g0 x, Q = sum_i na x (m x nvec each)
 void require_bits(const bsn_bed *b, int bits, const char *what);  // fails with a clear message otherwise

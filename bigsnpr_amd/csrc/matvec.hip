@@ -21,6 +21,8 @@
 //   Results are bit-reproducible (integer sums are order-independent).
 #include <cmath>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 
 #include "bsn_internal.hpp"
 #include "byte_plan.hpp"
@@ -308,6 +310,11 @@ __global__ __launch_bounds__(64) void k_quant(const double *__restrict__ X, int6
 // step without a missing code is zero).  Chosen by the host from the measured share of such steps (op_na_blocks):
 // at 1 % scattered missing values no step is free and the branch only costs; on nearly complete or batch-structured
 // data most are.
+// The grid (CONTIG on the plain image, one or two planes without counting: GEO below): the blocks of variants that fill whole
+// rounds of the CUs run as ever — one workgroup, all chunks of samples, sums into acc_out; the blocks beyond the last whole
+// round (162 of 1 954 at 1M variants on 256 CUs, where 94 CUs used to idle through the eighth round; all 245 of a warm-start
+// launch) are cut along the samples into slabs, launched last, whose int32 sums go to `part_out` and are added by
+// k_cprod_final (prod_plan.hpp: plan_cprod, cprod_slab).  BSN_CPROD_ONE_SPLIT=1: every block a whole-round block.
 template <int NB, int NPLANE, int KC, bool RAW0, bool STATS, bool CONTIG, int TILES = 2, int WAVES = 8, int MINW = 1,
           int TAG = 0, bool TILED = false, int SGB = 0, bool NASKIP = false>
 __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__restrict__ img, int64_t pitch,
@@ -315,7 +322,8 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
                                                int64_t m, const int8_t *__restrict__ xq,
                                                int32_t *__restrict__ acc_out, int64_t m_out,
                                                uint32_t lutA, uint32_t lutB, uint32_t lutC,
-                                               int32_t *__restrict__ counts, int32_t n_pad_samples) {
+                                               int32_t *__restrict__ counts, int32_t n_pad_samples,
+                                               const CprodGrid geo, int32_t *__restrict__ part_out) {
   constexpr int NCOL = 16 * NB;
   constexpr int LD = KC / 256;             // 16-B loads per variant row per chunk per lane
   constexpr int XS = KC / 16 * NCOL;       // uint4 entries per LDS buffer
@@ -323,7 +331,22 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = lane & 15, g = lane >> 4;
   constexpr int NT = 64 * WAVES;
-  const int64_t wg_base = (int64_t)blockIdx.x * (WAVES * 16 * TILES);
+  const int nchunks = (int)(pitch * 4 / KC);
+  // GEO: the launch runs on the one-dimensional grid of cprod_slab (prod_plan.hpp) — the blocks of variants that fill whole
+  // rounds of the CUs first, each over all chunks and into acc_out; then the blocks beyond the last whole round, cut along the
+  // samples into slabs whose sums go to part_out[slab][plane][variant - first remainder variant][NCOL] (k_cprod_final adds
+  // them).  Every other instance: one workgroup per block, all chunks.
+  constexpr bool GEO = CONTIG && !TILED && !STATS && NPLANE < 3 && KC == 512;
+  CprodSlab sl{(int)blockIdx.x, 0, 0, nchunks};
+  if constexpr (GEO) {
+    // (the division of cprod_slab runs on the vector unit: back into scalar registers, the loop has no vector register to spare)
+    sl = cprod_slab(geo, blockIdx.x);
+    sl.block = __builtin_amdgcn_readfirstlane(sl.block), sl.slab = __builtin_amdgcn_readfirstlane(sl.slab);
+    sl.ch_begin = __builtin_amdgcn_readfirstlane(sl.ch_begin), sl.ch_end = __builtin_amdgcn_readfirstlane(sl.ch_end);
+  }
+  const int ch_begin = sl.ch_begin, ch_end = sl.ch_end;
+  if (ch_begin >= ch_end) return;          // an empty slab (never: the planner gives every slab at least one chunk)
+  const int64_t wg_base = (int64_t)sl.block * (WAVES * 16 * TILES);
   const int64_t snp_base = wg_base + wave * (16 * TILES);
   const uint8_t *rowp[TILES];
   uint32_t voff[TILES];
@@ -352,7 +375,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
       return *(const uint4 *)(rowp[t] + off);
     }
   };
-  const int nchunks = (int)(pitch * 4 / KC);
+  // (the digit panel from the slab's first chunk on; the register sets and LDS buffers start at 0 there, whatever its parity)
   const uint4 *xq4 = (const uint4 *)xq;
 
   v4i acc[TILES][NPLANE][NB];
@@ -378,19 +401,22 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
 #pragma unroll
   for (int t = 0; t < TILES; t++)
 #pragma unroll
-    for (int it = 0; it < LD; it++) ga[0][t][it] = gload(t, it * 64);
+    for (int it = 0; it < LD; it++) ga[0][t][it] = gload(t, ch_begin * (KC / 4) + it * 64);
   // entry x of a thread's staging set exists when the panel is a whole number of workgroups, or below its end
   // (three column blocks shared by 16 waves: 1536 entries for 1024 threads)
   auto staged = [&](const int x) -> bool { return XFULL || tid + x * NT < XS; };
-  if (staged(0)) xs[0][tid] = xq4[tid];
-  if constexpr (NX > 1) if (staged(1)) xs[0][tid + NT] = xq4[tid + NT];
-  if constexpr (NX > 2) if (staged(2)) xs[0][tid + 2 * NT] = xq4[tid + 2 * NT];
-  if constexpr (NX > 3) if (staged(3)) xs[0][tid + 3 * NT] = xq4[tid + 3 * NT];
+  {
+    const uint4 *src = xq4 + (int64_t)ch_begin * XS;
+    if (staged(0)) xs[0][tid] = src[tid];
+    if constexpr (NX > 1) if (staged(1)) xs[0][tid + NT] = src[tid + NT];
+    if constexpr (NX > 2) if (staged(2)) xs[0][tid + 2 * NT] = src[tid + 2 * NT];
+    if constexpr (NX > 3) if (staged(3)) xs[0][tid + 3 * NT] = src[tid + 3 * NT];
+  }
 #pragma unroll
   for (int t = 0; t < TILES; t++)
 #pragma unroll
     for (int it = 0; it < LD; it++)
-      ga[1][t][it] = gload(t, (nchunks > 1 ? KC / 4 : 0) + it * 64);
+      ga[1][t][it] = gload(t, (ch_end - ch_begin > 1 ? ch_begin + 1 : ch_begin) * (KC / 4) + it * 64);
   __syncthreads();
 
   auto chunk = [&](auto SETC, const int ch) {
@@ -398,8 +424,8 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
     // No branches around the loads: a conditional load makes the compiler's waitcnt insertion
     // fall back to vmcnt(0) at the join, which drains the prefetch.  Past the end the last
     // chunk is simply loaded again (into registers / an LDS buffer nobody reads).
-    const int ch1 = ch + 1 < nchunks ? ch + 1 : nchunks - 1;
-    const int ch2 = ch + 2 < nchunks ? ch + 2 : nchunks - 1;
+    const int ch1 = ch + 1 < ch_end ? ch + 1 : ch_end - 1;
+    const int ch2 = ch + 2 < ch_end ? ch + 2 : ch_end - 1;
     {
       // the digit panel of the next chunk: into registers now, into LDS after the compute
       const uint4 *src = xq4 + (int64_t)ch1 * XS;
@@ -525,12 +551,20 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
     }
     __syncthreads();
   };
-  for (int ch = 0; ch < nchunks; ch += 2) {
+  for (int ch = ch_begin; ch < ch_end; ch += 2) {
     chunk(std::integral_constant<int, 0>{}, ch);
-    if (ch + 1 < nchunks) chunk(std::integral_constant<int, 1>{}, ch + 1);  // (odd only for KC = 1024)
+    if (ch + 1 < ch_end) chunk(std::integral_constant<int, 1>{}, ch + 1);  // (a slab may have an odd number of chunks)
   }
 
-  // raw accumulators: acc_out[plane][variant][NCOL]
+  // raw accumulators: acc_out[plane][variant][NCOL]; of a remainder block its slab of part_out
+  int32_t *out = acc_out;
+  int64_t out_m = m_out, out_j0 = 0;
+  if constexpr (GEO) {
+    if (sl.block >= geo.blocks_whole) {
+      out_m = geo.m_rem, out_j0 = m - geo.m_rem;
+      out = part_out + (int64_t)sl.slab * NPLANE * out_m * NCOL;
+    }
+  }
 #pragma unroll
   for (int t = 0; t < TILES; t++)
 #pragma unroll
@@ -541,7 +575,7 @@ __global__ __launch_bounds__(64 * WAVES, MINW) void k_cprod(const uint8_t *__res
         for (int p = 0; p < NPLANE; p++)
 #pragma unroll
           for (int nb = 0; nb < NB; nb++)
-            acc_out[((int64_t)p * m_out + j) * NCOL + nb * 16 + c] = acc[t][p][nb][r];
+            out[((int64_t)p * out_m + j - out_j0) * NCOL + nb * 16 + c] = acc[t][p][nb][r];
       }
     }
   if constexpr (STATS) {
@@ -585,13 +619,35 @@ __global__ __launch_bounds__(128) void k_cprod_final(const int32_t *__restrict__
                                                      const VecMeta *__restrict__ meta,
                                                      const double *__restrict__ center,
                                                      const double *__restrict__ scale, double *Z, int64_t ldz,
-                                                     int has_q) {
+                                                     int has_q, const int32_t *__restrict__ part, int64_t m_rem,
+                                                     int slabs) {
   constexpr int ROW = 2 * NCOL + 1;
   __shared__ int32_t srow[128 * ROW];
-  const int64_t j = (int64_t)blockIdx.x * 128 + threadIdx.x;
+  // (the last variants first: those of k_cprod's remainder blocks have slabs to add and should not be the grid's tail)
+  const int64_t j = (int64_t)(gridDim.x - 1 - blockIdx.x) * 128 + threadIdx.x;
   if (j >= m) return;
   int32_t *my = srow + threadIdx.x * ROW;
-  {
+  if (slabs > 0 && j >= m - m_rem) {
+    // a variant of a remainder block (k_cprod's grid, prod_plan.hpp): its sums are the slabs' partial sums added — in
+    // int64; the total is the int32 one workgroup over all samples would have written (launch_cprod's sample limit).
+    // A slab's row is read whole, its NCOL / 4 loads in flight together (as k_prod_final reads its slabs).
+    const int nplane = has_q ? 2 : 1;
+    for (int p = 0; p < nplane; p++) {
+      long long d[NCOL];
+#pragma unroll
+      for (int c = 0; c < NCOL; c++) d[c] = 0;
+      const int4 *row = (const int4 *)(part + ((int64_t)p * m_rem + (j - (m - m_rem))) * NCOL);
+      for (int k = 0; k < slabs; k++, row += (int64_t)nplane * m_rem * (NCOL / 4)) {
+#pragma unroll
+        for (int t = 0; t < NCOL / 4; t++) {
+          const int4 v = row[t];
+          d[4 * t] += v.x, d[4 * t + 1] += v.y, d[4 * t + 2] += v.z, d[4 * t + 3] += v.w;
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < NCOL; c++) my[p * NCOL + c] = (int32_t)d[c];
+    }
+  } else {
     const int4 *pa = (const int4 *)(acc + j * NCOL), *pq = (const int4 *)(acc + (m + j) * NCOL);
 #pragma unroll
     for (int t = 0; t < NCOL / 4; t++) {
@@ -1462,12 +1518,55 @@ static bool use_tiled(const bsn_op *op) {
   return op->bed->d_tiled != nullptr && op->cols_contig && (op->col0 & 63) == 0;
 }
 
+// compute units of the device (the slab rules of k_prodT and k_cprod fill whole rounds of them)
+static int device_cus() {
+  static const int ncu = [] {
+    hipDeviceProp_t pr;
+    int dev = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
+               ? pr.multiProcessorCount : 256;
+  }();
+  return ncu;
+}
+
+// The grid of a k_cprod launch that takes the geometry (prod_plan.hpp: plan_cprod).  How many workgroups of the instance a CU
+// holds is the runtime's answer, asked once per instance.  BSN_PLAN_CUS=<n>: the CU count assumed, as for k_prodT
+// (tests/test_gpu_cprod_whole.py; same sums, read on every call).
+static thread_local CprodGridFacts g_cprod_facts;   // what the last plan was made from (op_cprod_grid)
+static CprodGrid cprod_geometry(bsn_op *op, const void *kern, int per_wg, int threads, int NB, int nplane) {
+  static std::mutex mu;
+  static std::map<const void *, int> held;
+  int resident;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = held.find(kern);
+    if (it == held.end()) {
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, 0) != hipSuccess || nb < 1) nb = 1;
+      it = held.emplace(kern, nb).first;
+    }
+    resident = it->second;
+  }
+  CprodGridFacts f;
+  f.m = op->m, f.per_wg = per_wg, f.nchunks = (int)(op->bed->pitch * 4 / 512), f.pitch = op->bed->pitch;
+  f.NB = NB, f.nplane = nplane, f.ncu = device_cus(), f.resident = resident;
+  if (const char *e = getenv("BSN_PLAN_CUS")) f.ncu = std::max(1, atoi(e));
+  // BSN_CPROD_SLABS=<c>: that many slabs for the remainder blocks instead of the rule's count (same sums, read on every call)
+  if (const char *e = getenv("BSN_CPROD_SLABS")) f.slabs = std::max(1, atoi(e));
+  g_cprod_facts = f;
+  return plan_cprod(f);
+}
+
 // One crossproduct launch: the instance that choose_cprod (prod_plan.hpp) names, on the image it reads.  The list below is
 // the instances that exist — the counting and the three-plane pass have no three-block kernel, only the plain pass has
 // skipping ones; tiles per wave on the tiled copy: 4, the counting pass 2.
+// geo (op_cprod): null — one workgroup per block of variants, the instance's old grid.  Otherwise the call either PLANS
+// (acc == nullptr: *geo becomes the grid of cprod_slab for the instance this launch takes, from what the runtime says a CU
+// holds of it; the caller sizes d_acc by it) or LAUNCHES on *geo, the partial sums of the remainder blocks going to `part`.
 template <int NPLANE, bool RAW0, bool STATS>
 static void launch_cprod(bsn_op *op, int NB, const int8_t *q, int32_t *acc, uint32_t l0,
-                         uint32_t l1, uint32_t l2, int32_t *counts = nullptr) {
+                         uint32_t l1, uint32_t l2, int32_t *counts = nullptr, CprodGrid *geo = nullptr,
+                         int32_t *part = nullptr) {
   bsn_bed *b = op->bed;
   constexpr int KC = 512, TT = STATS ? 2 : 4;
   constexpr bool PLAIN = NPLANE == 2 && RAW0 && !STATS;
@@ -1481,11 +1580,26 @@ static void launch_cprod(bsn_op *op, int NB, const int8_t *q, int32_t *acc, uint
   const CprodKernel k = choose_cprod(f);
   const uint8_t *image = k.tiled ? b->d_tiled : b->d_img;
   const int per_wg = 16 * k.tiles * k.waves;   // variants of a workgroup
-  const dim3 grid((unsigned)((op->m + per_wg - 1) / per_wg)), block(64 * k.waves);
+  // the instances that take the geometry (k_cprod: GEO); BSN_CPROD_ONE_SPLIT=1: none (A/B switch, bit-identical; read on every call)
+  const bool geo_ok = geo && k.contig && !k.tiled && !STATS && NPLANE < 3 && !getenv("BSN_CPROD_ONE_SPLIT");
+  CprodGrid one;   // the old grid in the new terms: every block a whole-round block
+  one.blocks = one.blocks_whole = (int)((op->m + per_wg - 1) / per_wg), one.nchunks = (int)(b->pitch * 4 / KC);
+  const bool planning = geo && !acc;
+  if (planning && !geo_ok) {
+    *geo = one;
+    return;
+  }
+  const CprodGrid g = geo && !planning ? *geo : one;
+  const dim3 grid((unsigned)cprod_workgroups(g)), block(64 * k.waves);
 #define BSN_CPROD(NBV, CONTIGV, TV, WV, TAGV, TILEDV, SGBV, NASKIPV)                                                   \
   if (k == CprodKernel{NBV, CONTIGV, TV, WV, TAGV, TILEDV, SGBV, NASKIPV}) {                                           \
-    BSN_KLAUNCH((k_cprod<NBV, NPLANE, KC, RAW0, STATS, CONTIGV, TV, WV, 1, TAGV, TILEDV, SGBV, NASKIPV>), grid, block, \
-                0, b->stream, image, b->pitch, cols, op->col0, op->m, q, acc, op->m, l0, l1, l2, counts, npad);        \
+    auto kern = k_cprod<NBV, NPLANE, KC, RAW0, STATS, CONTIGV, TV, WV, 1, TAGV, TILEDV, SGBV, NASKIPV>;                \
+    if (planning) {                                                                                                    \
+      *geo = cprod_geometry(op, (const void *)kern, per_wg, 64 * k.waves, NB, NPLANE);                                 \
+      return;                                                                                                          \
+    }                                                                                                                  \
+    BSN_KLAUNCH(kern, grid, block, 0, b->stream, image, b->pitch, cols, op->col0, op->m, q, acc, op->m, l0, l1, l2,    \
+                counts, npad, g, part);                                                                                \
     BSN_HIP(hipGetLastError());                                                                                        \
     return;                                                                                                            \
   }
@@ -1512,11 +1626,12 @@ static void launch_cprod(bsn_op *op, int NB, const int8_t *q, int32_t *acc, uint
 }
 
 // z = finalize of a crossproduct launch of NB column blocks
+// (geo.slabs > 0: the variants of k_cprod's remainder blocks have their sums in the slabs of `part`)
 static void launch_cprod_final(bsn_op *op, int NB, const int32_t *acc, int S, int nv, const VecMeta *meta, double *Z,
-                               int64_t ldz, bool has_q) {
+                               int64_t ldz, bool has_q, const CprodGrid &geo, const int32_t *part) {
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)((op->m + 127) / 128)), dim3(128), 0, op->bed->stream, acc, op->m, S, nv, meta,
-                       op->d_center.p, op->d_scale.p, Z, ldz, has_q ? 1 : 0);
+                       op->d_center.p, op->d_scale.p, Z, ldz, has_q ? 1 : 0, part, geo.m_rem, geo.slabs);
   };
   if (NB == 1) go(k_cprod_final<16>);
   else if (NB == 2) go(k_cprod_final<32>);
@@ -1663,6 +1778,34 @@ void op_cprod_prequant(bsn_op *op, const double *d_X, int64_t ldx, int nvec) {
   op->preq_S = S;
 }
 
+// The crossproduct launch on the 2-bit image, by what the operator knows: counting along / complete data / the plain pass
+// (acc == nullptr: only the grid of that launch, into *geo — see launch_cprod)
+static void cprod_on_image(bsn_op *op, int NB, const int8_t *q, int32_t *acc, CprodGrid *geo, int32_t *part) {
+  if (op->stats_pending) {
+    if (!op->rows_identity) fail("internal: fused scaling statistics need all samples");
+    launch_cprod<2, true, true>(op, NB, q, acc, kLutRaw, kLutNA, 0, op->d_counts.ensure((size_t)4 * op->m + 8), geo, part);
+  } else if (op->no_na) {
+    launch_cprod<1, true, false>(op, NB, q, acc, kLutRaw, 0, 0, nullptr, geo, part);  // complete variants: code == genotype
+  } else {
+    launch_cprod<2, true, false>(op, NB, q, acc, kLutRaw, kLutNA, 0, nullptr, geo, part);
+  }
+}
+
+// The grid the first launch of op_cprod over nvec vectors would take now (tests: the geometry of a case is asserted before the
+// GPU runs it).  out: blocks, blocks_whole, slabs, cps, nchunks, m_rem, then what the plan was made from — variants per
+// workgroup, CUs, workgroups of the instance a CU holds (0, 0, 0: an instance without the geometry, or the switch).
+void op_cprod_grid(bsn_op *op, int nvec, int64_t *out) {
+  require_bits(op->bed, 2, "the grid of k_cprod");
+  if (nvec <= 0) fail("op_cprod_grid: no vectors");
+  CprodGrid g;
+  g_cprod_facts = CprodGridFacts();
+  g_cprod_facts.per_wg = g_cprod_facts.ncu = g_cprod_facts.resident = 0;
+  const int S = op->slices;
+  op_na_blocks(op, nvec * S);
+  cprod_on_image(op, pick_nb(std::min(nvec, cprod_vmax(op, S)) * S), nullptr, nullptr, &g, nullptr);
+  out[0] = g.blocks, out[1] = g.blocks_whole, out[2] = g.slabs, out[3] = g.cps, out[4] = g.nchunks, out[5] = g.m_rem;
+  out[6] = g_cprod_facts.per_wg, out[7] = g_cprod_facts.ncu, out[8] = g_cprod_facts.resident;
+}
 void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z, int64_t ldz) {
   bsn_bed *b = op->bed;
   refuse_generic(b, "this function (it needs the streaming products)");
@@ -1684,7 +1827,13 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
     int8_t *q = op->d_q.ensure((size_t)npad * kMaxCols * 2);
     // (byte image: one block of partial sums per 131 072-sample slice)
     const int nslice = b->bits == 8 ? byte_slices(b->pitch) : 1;
-    int32_t *acc = op->d_acc.ensure(std::max((size_t)2 * op->m * kMaxCols, (size_t)nslice * 2 * op->m * ncol));
+    CprodGrid geo;   // the grid of the launch, before the accumulators are sized
+    if (b->bits == 2) cprod_on_image(op, NB, q, nullptr, &geo, nullptr);
+    // (behind the accumulators of the largest launch: the partial sums of the remainder blocks, prod_plan.hpp)
+    const size_t acc_words = std::max((size_t)2 * op->m * kMaxCols, (size_t)nslice * 2 * op->m * ncol);
+    const size_t part_words = (size_t)cprod_partial_words(geo, op->stats_pending || !op->no_na ? 2 : 1, NB);
+    int32_t *acc = op->d_acc.ensure(acc_words + part_words);
+    int32_t *part = acc + acc_words;
     if (!have_digits) quantise(op, xsrc + (int64_t)v0 * ldx, ldx, b->n, npad, nv, 0, S, ncol, 1, 0, meta, q);
     prof_begin(op, op->stats_pending ? 2 : NB == 3 ? 4 : 0);  // the pass that carries the code counts is timed apart
     if (b->bits == 8) {
@@ -1710,14 +1859,7 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
       BSN_HIP(hipGetLastError());
       continue;
     }
-    if (op->stats_pending) {
-      if (!op->rows_identity) fail("internal: fused scaling statistics need all samples");
-      launch_cprod<2, true, true>(op, NB, q, acc, kLutRaw, kLutNA, 0, op->d_counts.ensure((size_t)4 * op->m + 8));
-    } else if (op->no_na) {
-      launch_cprod<1, true, false>(op, NB, q, acc, kLutRaw, 0, 0);  // complete variants: code == genotype
-    } else {
-      launch_cprod<2, true, false>(op, NB, q, acc, kLutRaw, kLutNA, 0);
-    }
+    cprod_on_image(op, NB, q, acc, &geo, part);
     prof_end(op);
     op->passes++;
     if (op->late_center || op->late_scale) {
@@ -1731,7 +1873,7 @@ void op_cprod(bsn_op *op, const double *d_X, int64_t ldx, int nvec, double *d_Z,
     }
     const bool has_q = op->stats_pending || !op->no_na;
     if (op->stats_pending) finish_fused_stats(op);
-    launch_cprod_final(op, NB, acc, S, nv, meta, d_Z + (int64_t)v0 * ldz, ldz, has_q);
+    launch_cprod_final(op, NB, acc, S, nv, meta, d_Z + (int64_t)v0 * ldz, ldz, has_q, geo, part);
   }
 }
 
@@ -1799,17 +1941,6 @@ static void launch_prod_final(bsn_bed *b, int NB, const int32_t *acc, int64_t np
   else if (NB == 2) go(k_prod_final<32>);
   else go(k_prod_final<48>);
   BSN_HIP(hipGetLastError());
-}
-
-// compute units of the device (k_prodT's slab rule fills whole rounds of them)
-static int device_cus() {
-  static const int ncu = [] {
-    hipDeviceProp_t pr;
-    int dev = 0;
-    return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0)
-               ? pr.multiProcessorCount : 256;
-  }();
-  return ncu;
 }
 
 // Y (+)= sum_j P[code_ij] W1[j, v] + sum_j lutQ[code_ij] W2[j, v]  (- sum_j W2[j, v] if sub_const)

@@ -1,7 +1,8 @@
 // prod_plan.hpp — the launch geometry of the streaming products (matvec.hip: prod_planes, op_cprod) and which instance of
 // k_cprod / k_prod / k_prodT a launch takes, decided from plain facts.
-// No HIP in here but the __host__ __device__ mark of prodt_slab, which k_prodT compiles as it stands: tests/native pins the
-// geometry and the choices on the CPU (tests/test_prod_plan_cpu.py, tests/test_prodt_grid_cpu.py).
+// No HIP in here but the __host__ __device__ mark of prodt_slab and cprod_slab, which k_prodT and k_cprod compile as they
+// stand: tests/native pins the geometry and the choices on the CPU (tests/test_prod_plan_cpu.py, tests/test_prodt_grid_cpu.py,
+// tests/test_cprod_grid_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -276,6 +277,103 @@ inline CprodKernel choose_cprod(const CprodFacts &f) {
                                 : CprodKernel{2, true, 2, 16, 0, true, 3, false};
   if (f.NB == 1) return {1, f.cols_contig, 2, 8, f.cols_contig && f.warm ? 1 : 0, false, 0, false};
   return {2, f.cols_contig, 2, 16, 0, false, f.cols_contig ? 3 : 0, false};
+}
+
+// ---- Z = A~' X: the grid of one k_cprod launch ---------------------------------------------------------------------
+// A workgroup of k_cprod owns a block of variants (256 with one column block, 512 with two or three) for the whole sample
+// range, so the blocks alone leave the last round of the CUs partly empty: 1 954 blocks of 512 variants are 7.63 rounds of
+// 256 CUs.  As for k_prodT, the blocks that fill whole rounds stay as they are — one workgroup, all 512-sample chunks, sums
+// straight into acc_out — and only the blocks beyond the last whole round are cut along the samples into `slabs` slabs of
+// `cps` chunks, whose int32 partial sums k_cprod_final adds.  A launch with less than one round of blocks (the warm start of
+// a solve: 1 / 16 of the variants) is all remainder.  No atomics, no workgroup waits for another.
+struct CprodGridFacts {
+  int64_t m = 0;            // variants of the launch
+  int per_wg = 512;         // variants of a workgroup (16 x tiles x waves of the instance)
+  int nchunks = 1;          // chunks of 512 samples of the image
+  int64_t pitch = 128;      // bytes per variant of the image
+  int NB = 1, nplane = 2;   // column blocks, planes of the launch
+  int ncu = 256;            // compute units (BSN_PLAN_CUS overrides the device's)
+  int resident = 1;         // workgroups of the launched instance a CU holds (asked of the runtime)
+  bool one_split = false;   // BSN_CPROD_ONE_SPLIT=1, or an instance without the geometry: one workgroup per block
+  int slabs = 0;            // BSN_CPROD_SLABS: the slab count of the remainder blocks instead of the rule's (1: none); 0 = the rule
+};
+struct CprodGrid {
+  int blocks = 0, blocks_whole = 0;   // blocks of variants; those of the whole rounds (== blocks: the geometry as it was)
+  int slabs = 0, cps = 0;             // slabs / chunks per slab of blocks blocks_whole .. blocks - 1 (0, 0 without a remainder)
+  int nchunks = 0;                    // chunks of 512 samples
+  int64_t m_rem = 0;                  // variants from the first remainder block on (the partial region's variant count)
+};
+struct CprodSlab {
+  int block, slab;          // block of variants; slab (the partial region's first index; 0 for a whole-round block)
+  int ch_begin, ch_end;     // its chunks
+};
+constexpr int kCprodMaxSlabs = 24;
+BSN_PLAN_HD int64_t cprod_workgroups(const CprodGrid &g) {
+  return (int64_t)g.blocks_whole + (int64_t)(g.blocks - g.blocks_whole) * g.slabs;
+}
+// int32 words of the partial region [slab][plane][variant - first remainder variant][16 NB]
+inline int64_t cprod_partial_words(const CprodGrid &g, int nplane, int NB) {
+  return (int64_t)g.slabs * nplane * g.m_rem * 16 * NB;
+}
+// workgroup wg of the one-dimensional grid -> (block, slab, first chunk, end chunk); shared by k_cprod and tests/native.
+// The whole-round blocks first, then the remainder slab by slab — last, so that the CUs which finish first pick them up.
+BSN_PLAN_HD CprodSlab cprod_slab(const CprodGrid &g, uint32_t wg) {
+  CprodSlab s;
+  if (wg < (uint32_t)g.blocks_whole) {
+    s.block = (int)wg, s.slab = 0, s.ch_begin = 0, s.ch_end = g.nchunks;
+    return s;
+  }
+  const uint32_t r = wg - (uint32_t)g.blocks_whole, nrest = (uint32_t)(g.blocks - g.blocks_whole);
+  s.slab = (int)(r / nrest);
+  s.block = g.blocks_whole + (int)(r - (uint32_t)s.slab * nrest);
+  s.ch_begin = s.slab * g.cps;
+  s.ch_end = s.ch_begin + g.cps < g.nchunks ? s.ch_begin + g.cps : g.nchunks;
+  return s;
+}
+inline CprodGrid plan_cprod(const CprodGridFacts &f) {
+  CprodGrid g;
+  g.blocks = (int)((f.m + f.per_wg - 1) / f.per_wg);
+  g.nchunks = f.nchunks;
+  g.blocks_whole = g.blocks;
+  const int64_t slots = (int64_t)std::max(1, f.ncu) * std::max(1, f.resident);
+  const int64_t whole = g.blocks / slots * slots, rest = g.blocks - whole;
+  if (f.one_split || rest == 0 || f.nchunks <= 1) return g;
+  // The remainder is cut only where it leaves CUs EMPTY.  Where a CU holds several workgroups (three of the one-block kernel)
+  // and every CU still has one, the launch is bound by HBM, not by the places taken: 489 blocks on 256 CUs x 3 (a 125 000-
+  // variant shard) cut into 14 slabs ran 6 % SLOWER (2.24 -> 2.39 ms, profiles/cprod_whole_rounds_ab.txt).
+  if (rest >= std::max(1, f.ncu) && f.slabs == 0) return g;
+  // plan_prod's rule on the remainder alone: among 1 .. 24 slabs the count whose workgroups fill whole rounds best — the
+  // remainder then takes rounds / c of a whole block's time, fill is what of that the slots work — less what the slabs
+  // cost: every slab writes its nplane x 16 NB int32 sums per variant and k_cprod_final reads them back, against the `pitch`
+  // bytes the variant streams.  One slab is the unsplit block, which writes acc_out as ever and costs nothing.
+  // The weight of that cost is 1.0.  k_prodT's 0.3 chose 24 slabs for the 245 two-block workgroups of that shard — fill
+  // 0.957 -> 0.999 — and the launch with its finalize took 2.83 ms instead of 2.39: 0.9 % per slab where 0.3 says 0.15 %, a
+  // weight of 1.8; the sweep at 1M variants (BSN_CPROD_SLABS: 1, 3, 5, 7, 11, 14, 22 — the solve follows the fill) has 3
+  // and 11 slabs level, a weight of 0.7.  400 000 x 1 000 000 on 256 CUs: the 162 remainder blocks in 3 slabs of 261 chunks
+  // with three column blocks, in 11 of 72 with two; the 67 one-block blocks beyond five rounds of 768 in 11; the 244 one-block
+  // workgroups of the warm start in 3.  The shard keeps one workgroup per block.  (profiles/cprod_whole_rounds_ab.txt)
+  const double slab_cost = 1.0 * 2.0 * (double)f.nplane * 16.0 * f.NB * 4.0 / (double)f.pitch;
+  int best = 1;
+  double best_score = -1e300;
+  for (int c = 1; c <= kCprodMaxSlabs && c <= f.nchunks; c++) {
+    const int cps = (f.nchunks + c - 1) / c;
+    if ((f.nchunks + cps - 1) / cps != c) continue;   // (a count that whole chunks cannot make)
+    const int64_t W = rest * c;
+    const double fill = (double)W / ((double)slots * (double)((W + slots - 1) / slots));
+    const double score = fill - (c > 1 ? slab_cost * c : 0.0);
+    if (score > best_score + 1e-9) best_score = score, best = c;
+  }
+  // (BSN_CPROD_SLABS: a count of the caller's — tests at shapes too small for the rule to split, sweeps; whole chunks per slab)
+  if (f.slabs > 0) {
+    const int c = std::min(f.slabs, f.nchunks), cps = (f.nchunks + c - 1) / c;
+    best = (f.nchunks + cps - 1) / cps;
+  }
+  if (best == 1) return g;   // the split would not pay
+  g.blocks_whole = (int)whole;
+  g.cps = (f.nchunks + best - 1) / best;
+  g.slabs = best;
+  g.m_rem = f.m - whole * f.per_wg;
+  return g;
 }
 
 // k_prod<NB, contig, rawp, hasq, tag, tiled> on the variant-major image (or its streaming-layout copy)
