@@ -134,6 +134,12 @@ SIGNATURES = {
     "bsn_bed_fst": (C.c_int, [vp, i64p, i64, i32p, C.c_int32, i64p, i64, C.c_double, f64p, f64p]),
     "bsn_snp_max3": (C.c_int, [vp, i64p, i64, i32p, i64p, i64, f64p, C.c_int32, f64p]),
     "bsn_popstat_last_ms": (C.c_int, [f64p]),
+    "bsn_hwe": (C.c_int, [i32p, i64, C.c_int, f64p]),
+    "bsn_hwe_lanes": (C.c_int, [i32p, i64, C.c_int, C.c_int, f64p, f64p]),
+    "bsn_bed_hwe": (C.c_int, [vp, i64p, i64, i64p, i64, C.c_int, f64p, i32p]),
+    "bsn_bed_qc": (C.c_int, [vp, i64p, i64, i64p, i64, i32p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int,
+                             u8p, u8p, f64p, f64p]),
+    "bsn_qc_last_ms": (C.c_int, [f64p]),
     "bsn_bed_king": (C.c_int, [vp, i64p, i64, i64p, i64, C.c_double, C.c_int, C.POINTER(C.c_int64), C.POINTER(vp)]),
     "bsn_king_fetch": (C.c_int, [vp, i32p, i32p, i32p, f64p]),
     "bsn_king_free": (C.c_int, [vp]),

@@ -304,6 +304,39 @@ int bsn_snp_max3(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int32_t 
  * One record per process, written without a lock, like bsn_impute_last_ms. */
 int bsn_popstat_last_ms(double *ms_out /* 4 */);
 
+/* ---- exact Hardy-Weinberg test and the QC filters (bed_hwe / bed_plinkQC; what snp_plinkQC asks of PLINK,
+ * R/external-software.R:247-290) ----
+ * The exact test of Wigginton, Cutler & Abecasis (2005) per variant, as csrc/hwe_step.hpp states it:
+ * p_out[j] from counts[3 j .. 3 j + 2] = the homozygotes of one allele, the heterozygotes, the homozygotes of the other.
+ * midp != 0: the mid-p variant.  No genotype: NaN; monomorphic: 1; a p-value below about 1e-300 may come back as 0.
+ * Refused by name: a negative count, a variant with more than INT32_MAX genotypes, m < 1. */
+int bsn_hwe(const int32_t *counts /* 3 x m: hom1, het, hom2 */, int64_t m, int midp, double *p_out /* [m] */);
+/* the same with the kernel form chosen by the caller: lanes = 1 (one lane walks down and up), 2 (two adjacent lanes, one
+ * walk each) or 0 (what bsn_hwe takes).  Every form returns the same bits.  ms_out (may be NULL): device ms of the kernel.
+ * For tests and tools/probe_qc.py. */
+int bsn_hwe_lanes(const int32_t *counts, int64_t m, int midp, int lanes, double *p_out, double *ms_out);
+/* the test over the selected samples of a genotype handle: one counting pass (as bsn_bed_group_counts with one group;
+ * out-of-core handles are served slab by slab), the counts stay on the device for the test.  counts_out (may be NULL):
+ * the counts of 0, 1, 2 and missing, 4 x m.  Refused by name: a byte (dosage) image, more than INT32_MAX samples. */
+int bsn_bed_hwe(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, int midp,
+                double *p_out /* [m] */, int32_t *counts_out /* 4 x m or NULL */);
+/* plink --mind --geno --maf --hwe in one call; nothing but the results leaves the device.  cls[i]: 0 = founder and counted
+ * for the test, 1 = founder, not counted for the test, 2 = not a founder (counted for the missing rates only).
+ *  1. sample i is removed when NA_i > mind * m over the selected variants; S1 is the rest;
+ *  2. over S1, independently of each other, variant j is removed when NA_j > geno * |S1|, when the exact test over class 0
+ *     gives p < hwe (skipped when hwe <= 0), or when its minor allele frequency over classes 0 and 1 is not >= maf (no call
+ *     among them: NaN, removed whenever maf > 0).
+ * keep_row [n], keep_col [m]: 1 = kept.  row_miss (n, may be NULL): NA_i / m.  col_stats (3 x m at 3 j, may be NULL): the
+ * missing rate over S1, the minor allele frequency, p (computed for col_stats also when hwe <= 0).
+ * Refused by name: a byte (dosage) image, an out-of-core handle, a threshold outside [0, 1], a class outside 0 .. 2, more
+ * than INT32_MAX samples, every sample removed, no sample of class 0 while hwe > 0, none of class 0 or 1 while maf > 0. */
+int bsn_bed_qc(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const int32_t *cls /* [n] */,
+               double maf, double geno, double mind, double hwe, int midp, uint8_t *keep_row /* [n] */,
+               uint8_t *keep_col /* [m] */, double *row_miss /* [n] or NULL */, double *col_stats /* 3 x m or NULL */);
+/* device milliseconds (HIP events) of the last bsn_bed_hwe / bsn_bed_qc of this process: [0] the per-sample counts, [1] the
+ * per-class counting pass, [2] the test kernel, [3] the masks.  One record per process, written without a lock. */
+int bsn_qc_last_ms(double *ms_out /* 4 */);
+
 /* ---- KING-robust kinship table (bed_king / bed_kingQC; what snp_plinkKINGQC asks of PLINK 2, R/external-software.R:520-590) ----
  * For every pair of positions i < j of ind_row, over the selected variants where both samples are called: NSNP, HETHET
  * (both heterozygous), IBS0 (opposite homozygotes), HET1HOM2 (i heterozygous, j homozygous), HET2HOM1 (the reverse) and
