@@ -189,6 +189,15 @@ SIGNATURES = {
     "bsn_sfbm_last_ms": (C.c_int, [vp, f64p]),
     "bsn_sfbm_ldsplit": (C.c_int, [vp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_double, f64p, f64p, i32p,
                                    f64p, f64p, f64p, i32p, i32p, i32p, f64p]),
+    # the panel kernels of the SVD one at a time (tests only)
+    "bsn_panel_gemm_tn": (C.c_int, [vp, i64, C.c_int32, vp, i64, C.c_int32, i64, vp, C.c_int32]),
+    "bsn_panel_gemm_nn": (C.c_int, [vp, i64, C.c_int32, vp, C.c_int32, vp, i64, C.c_double, C.c_double, vp, i64, i64]),
+    "bsn_panel_right_mult": (C.c_int, [vp, i64, i64, C.c_int32, C.c_int32, vp]),
+    "bsn_panel_update": (C.c_int, [vp, i64, C.c_int32, vp, vp, C.c_int32, vp, i64, i64, vp]),
+    "bsn_panel_round_cols": (C.c_int, [vp, i64, i64, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32]),
+    "bsn_panel_fused_orth": (C.c_int, [vp, i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, f64p, f64p]),
+    "bsn_panel_compact_gather": (C.c_int, [vp, i64, C.c_int32, C.c_int32, C.c_int32, vp]),
+    "bsn_panel_block_roundtrip": (C.c_int, [vp, i64, C.c_int32, C.c_int32, vp, vp]),
     "bsn_malloc": (C.c_int, [C.POINTER(vp), i64]),
     "bsn_free": (C.c_int, [vp]),
     "bsn_host_alloc": (C.c_int, [C.POINTER(vp), i64]),

@@ -428,6 +428,86 @@ __global__ void k_take_rows(const double *__restrict__ full, int64_t n, int cb, 
   W[t] = row0 + i < n ? full[row0 + i + j * n] : 0.0;
 }
 
+// ---- the launches of the panel kernels ------------------------------------------------------------------------
+// One free function per launch: grid, block, template choice and LDS size live here and nowhere else, so that the
+// backend below and the kernel-level test entries at the end of this file (bsn_panel_*) run the same launches.
+// doubles of `partial` that panel_gemm_tn writes for operands of `rows` rows and p columns of A
+inline size_t panel_partial_count(int64_t rows, int p) {
+  return (size_t)((rows + kGemmRows - 1) / kGemmRows) * (size_t)((p + 15) / 16) * 2 * 256;
+}
+// dC (p x cb, leading dimension ldc) = A[:, :p]' B[:, :cb] for operands with `rows` rows; cb <= 32
+void panel_gemm_tn(hipStream_t st, const double *A, int64_t lda, int p, const double *B, int64_t ldb, int cb, int64_t rows,
+                   double *dC, int ldc, double *partial) {
+  if (p <= 0 || cb <= 0) return;
+  dim3 grid((unsigned)((p + 15) / 16), (unsigned)((rows + kGemmRows - 1) / kGemmRows));
+  const int nt = (cb + 15) / 16;
+  if (nt == 1)
+    hipLaunchKernelGGL((k_gemm_tn<1>), grid, dim3(256), 0, st, A, lda, p, B, ldb, cb, rows, partial);
+  else if (nt == 2)
+    hipLaunchKernelGGL((k_gemm_tn<2>), grid, dim3(256), 0, st, A, lda, p, B, ldb, cb, rows, partial);
+  else
+    fail("internal: panel product with %d columns", cb);
+  hipLaunchKernelGGL(k_gemm_tn_reduce, dim3(grid.x, nt), dim3(1024), 0, st, partial, (int)grid.y, (int)grid.x, p, cb, dC, ldc);
+}
+void panel_gemm_nn(hipStream_t st, const double *Q, int64_t ldq, int p, const double *S, int nc, const double *In, int64_t ldi,
+                   double alpha, double beta, double *Out, int64_t ldo, int64_t n) {
+  hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((n + 255) / 256)), dim3(256), kTP * kMaxB * 8, st, Q, ldq, p, S, nc, In, ldi,
+                     alpha, beta, Out, ldo, n);
+}
+void panel_right_mult(hipStream_t st, double *W, int64_t ld, int64_t n, int cb, int r, const double *M) {
+  hipLaunchKernelGGL(k_right_mult, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, ld, n, cb, r, M);
+}
+void panel_update(hipStream_t st, const double *Q, int64_t ldq, int p, const double *C, const double *Ri, int cb, double *W,
+                  int64_t ldw, int64_t n, unsigned long long *mx) {
+  const dim3 rows((unsigned)((n + 1023) / 1024));
+  if (cb <= 8)
+    hipLaunchKernelGGL((k_update<8>), rows, dim3(256), 0, st, Q, ldq, p, C, Ri, cb, W, ldw, n, mx);
+  else
+    hipLaunchKernelGGL((k_update<16>), rows, dim3(256), 0, st, Q, ldq, p, C, Ri, cb, W, ldw, n, mx);
+}
+void panel_orth2(hipStream_t st, const OrthSmall &a, unsigned long long *mx_clear) {
+  hipLaunchKernelGGL(k_orth2, dim3(1), dim3(512), 0, st, a, mx_clear);
+}
+// wide: 256 workgroups per column (a whole panel on one GPU), else 64 (a rank's sample block)
+void panel_col_absmax(hipStream_t st, const double *X, int64_t ld, int64_t n, int cb, unsigned long long *mx, bool wide) {
+  hipLaunchKernelGGL(k_col_absmax, dim3(wide ? 256 : 64, cb), dim3(1024), 0, st, X, ld, n, mx);
+}
+void panel_round_cols(hipStream_t st, double *X, int64_t ld, int64_t n, int cb, const unsigned long long *mx, int slices) {
+  hipLaunchKernelGGL(k_round_cols, dim3((unsigned)((n + 255) / 256), cb), dim3(256), 0, st, X, ld, n, mx, slices);
+}
+void panel_block(hipStream_t st, const double *full, int64_t n, int cb, int64_t nr, int world, double *blk) {
+  const int64_t tot = (int64_t)world * cb * nr;
+  hipLaunchKernelGGL(k_block, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, full, n, cb, nr, world, blk);
+}
+void panel_unblock(hipStream_t st, const double *blk, int64_t n, int cb, int64_t nr, double *full) {
+  hipLaunchKernelGGL(k_unblock, dim3((unsigned)((n * cb + 255) / 256)), dim3(256), 0, st, blk, n, cb, nr, full);
+}
+void panel_place_rows(hipStream_t st, const double *src, int64_t rows, int cb, int64_t r0, int64_t nr, double *W) {
+  hipLaunchKernelGGL(k_place_rows, dim3((unsigned)((rows * cb + 255) / 256)), dim3(256), 0, st, src, rows, cb, r0, nr, W);
+}
+void panel_take_rows(hipStream_t st, const double *full, int64_t n, int cb, int64_t nr, int64_t row0, double *W) {
+  hipLaunchKernelGGL(k_take_rows, dim3((unsigned)((nr * cb + 255) / 256)), dim3(256), 0, st, full, n, cb, nr, row0, W);
+}
+void panel_max_over_ranks(hipStream_t st, const unsigned long long *all, int world, int cb, unsigned long long *mx) {
+  hipLaunchKernelGGL(k_max_over_ranks, dim3(1), dim3(64), 0, st, all, world, cb, mx);
+}
+// int16 up to 16 bits (slices <= 2), int32 up to 32: q is the rank's [column][row] block of integers
+void panel_pack_int(hipStream_t st, double *W, int64_t nr, int cb, const unsigned long long *mx, int slices, void *q) {
+  const dim3 gp((unsigned)((nr + 255) / 256), cb);
+  if (slices <= 2)
+    hipLaunchKernelGGL((k_pack_int<int16_t>), gp, dim3(256), 0, st, W, nr, mx, slices, (int16_t *)q);
+  else
+    hipLaunchKernelGGL((k_pack_int<int32_t>), gp, dim3(256), 0, st, W, nr, mx, slices, (int32_t *)q);
+}
+void panel_unpack_int(hipStream_t st, const void *q_all, int64_t n, int cb, int64_t nr, const unsigned long long *mx, int slices,
+                      double *full) {
+  const dim3 gu((unsigned)((n * cb + 255) / 256));
+  if (slices <= 2)
+    hipLaunchKernelGGL((k_unpack_int<int16_t>), gu, dim3(256), 0, st, (const int16_t *)q_all, n, cb, nr, mx, slices, full);
+  else
+    hipLaunchKernelGGL((k_unpack_int<int32_t>), gu, dim3(256), 0, st, (const int32_t *)q_all, n, cb, nr, mx, slices, full);
+}
+
 // Panels of length n (samples) are held by SAMPLE BLOCKS when the solve is distributed: rank r owns
 // rows [r nr, (r+1) nr) of the basis Q and of the working panel W, orthogonalises them locally and
 // shares only the small coefficient matrices (p x b, b x b) — the n-side algebra is divided by the
@@ -646,8 +726,7 @@ struct HipSvdBackend : SvdBackend {
   }
   void reduce_scatter_W(int cb) {  // Wfull (n x cb partial sums) -> W (nr x cb, summed over ranks)
     const int64_t tot = (int64_t)world * cb * nr;
-    hipLaunchKernelGGL(k_block, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, Wfull.p, n, cb, nr, world,
-                       Wblk.p);
+    panel_block(st, Wfull.p, n, cb, nr, world, Wblk.p);
     BSN_HIP(hipGetLastError());
     if (comm) {
       comm_reduce_scatter_sum(comm, Wblk.p, Wc, nr * cb, st);
@@ -669,7 +748,7 @@ struct HipSvdBackend : SvdBackend {
       sync_stream();
       hook(Wblk.p, tot, ctx);
     }
-    hipLaunchKernelGGL(k_unblock, dim3((unsigned)((n * cb + 255) / 256)), dim3(256), 0, st, Wblk.p, n, cb, nr, dst);
+    panel_unblock(st, Wblk.p, n, cb, nr, dst);
     BSN_HIP(hipGetLastError());
   }
 
@@ -867,8 +946,7 @@ struct HipSvdBackend : SvdBackend {
       }
       double *recv = ws.Wrecv.p + (size_t)cb * r0;
       comm_reduce_scatter_sum(comm, segs[sgi].d_out, recv, rows_s * cb, sc);
-      hipLaunchKernelGGL(k_place_rows, dim3((unsigned)((rows_s * cb + 255) / 256)), dim3(256), 0, sc, recv, rows_s, cb,
-                         r0, nr, Wc);
+      panel_place_rows(sc, recv, rows_s, cb, r0, nr, Wc);
       BSN_HIP(hipGetLastError());
     };
     if (overlap) {   // the second stream must not run ahead of what produced Wc / Wblk's previous contents
@@ -916,17 +994,7 @@ struct HipSvdBackend : SvdBackend {
   // dC (p x cb, leading dimension ldc) = A[:, :p]' B[:, :cb] for operands with `rows` rows (leading
   // dimension = rows); local rows only
   void gemm_tn_any(const double *A, const double *B, int64_t rows, int p, int cb, double *dC, int ldc = 0) {
-    if (p <= 0 || cb <= 0) return;
-    dim3 grid((unsigned)((p + 15) / 16), (unsigned)((rows + kGemmRows - 1) / kGemmRows));
-    const int nt = (cb + 15) / 16;
-    if (nt == 1)
-      hipLaunchKernelGGL((k_gemm_tn<1>), grid, dim3(256), 0, st, A, rows, p, B, rows, cb, rows, partial.p);
-    else if (nt == 2)
-      hipLaunchKernelGGL((k_gemm_tn<2>), grid, dim3(256), 0, st, A, rows, p, B, rows, cb, rows, partial.p);
-    else
-      fail("internal: panel product with %d columns", cb);
-    hipLaunchKernelGGL(k_gemm_tn_reduce, dim3(grid.x, nt), dim3(1024), 0, st, partial.p, (int)grid.y, (int)grid.x, p, cb,
-                       dC, ldc > 0 ? ldc : p);
+    panel_gemm_tn(st, A, rows, p, B, rows, cb, rows, dC, ldc > 0 ? ldc : p, partial.p);
   }
   void gemm_tn(const double *A, int p, int cb, double *C_host) {
     gemm_tn_any(A, Wc, nr, p, cb, dsmall.p);
@@ -941,10 +1009,9 @@ struct HipSvdBackend : SvdBackend {
     unsigned long long *mx = (unsigned long long *)dorth.p;
     if (!have_mx) {
       BSN_HIP(hipMemsetAsync(mx, 0, (size_t)cb * 8, st));
-      hipLaunchKernelGGL(k_col_absmax, dim3(256, cb), dim3(1024), 0, st, X, rows, rows, mx);
+      panel_col_absmax(st, X, rows, rows, cb, mx, true);
     }
-    hipLaunchKernelGGL(k_round_cols, dim3((unsigned)((rows + 255) / 256), cb), dim3(256), 0, st, X, rows, rows, mx,
-                       op->slices);
+    panel_round_cols(st, X, rows, rows, cb, mx, op->slices);
     BSN_HIP(hipGetLastError());
   }
   void round_W(int cb) override {
@@ -966,25 +1033,16 @@ struct HipSvdBackend : SvdBackend {
       // column keeps an unscaled zero: as in k_round_cols).  The integers travel as doubles: an all-gather only moves bytes.
       unsigned long long *mx = (unsigned long long *)dorth.p;
       BSN_HIP(hipMemsetAsync(mx, 0, (size_t)cb * 8, st));
-      hipLaunchKernelGGL(k_col_absmax, dim3(64, cb), dim3(1024), 0, st, Wc, nr, nr, mx);
+      panel_col_absmax(st, Wc, nr, nr, cb, mx, false);
       // (the segments' receive buffer is free here; it also has to hold world * cb maxima when the sample blocks are short)
       double *gmax = ws.Wrecv.ensure(std::max((size_t)nr * kMaxB, (size_t)world * kMaxB));
       comm_all_gather(comm, (const double *)mx, gmax, cb, st);
-      hipLaunchKernelGGL(k_max_over_ranks, dim3(1), dim3(64), 0, st, (const unsigned long long *)gmax, world, cb, mx);
-      const dim3 gp((unsigned)((nr + 255) / 256), cb), gu((unsigned)((n * cb + 255) / 256));
-      if (op->slices <= 2) {
-        int16_t *q_send = (int16_t *)Wfull.p, *q_all = (int16_t *)Wblk.p;
-        hipLaunchKernelGGL((k_pack_int<int16_t>), gp, dim3(256), 0, st, Wc, nr, mx, op->slices, q_send);
-        BSN_HIP(hipGetLastError());
-        comm_all_gather(comm, (const double *)q_send, (double *)q_all, nr * cb / 4, st);
-        hipLaunchKernelGGL((k_unpack_int<int16_t>), gu, dim3(256), 0, st, q_all, n, cb, nr, mx, op->slices, Qfull.p);
-      } else {
-        int32_t *q_send = (int32_t *)Wfull.p, *q_all = (int32_t *)Wblk.p;
-        hipLaunchKernelGGL((k_pack_int<int32_t>), gp, dim3(256), 0, st, Wc, nr, mx, op->slices, q_send);
-        BSN_HIP(hipGetLastError());
-        comm_all_gather(comm, (const double *)q_send, (double *)q_all, nr * cb / 2, st);
-        hipLaunchKernelGGL((k_unpack_int<int32_t>), gu, dim3(256), 0, st, q_all, n, cb, nr, mx, op->slices, Qfull.p);
-      }
+      panel_max_over_ranks(st, (const unsigned long long *)gmax, world, cb, mx);
+      // (the integers of a rank: Wfull as the send buffer, Wblk for all ranks'; 4 int16 or 2 int32 per double)
+      panel_pack_int(st, Wc, nr, cb, mx, op->slices, Wfull.p);
+      BSN_HIP(hipGetLastError());
+      comm_all_gather(comm, Wfull.p, Wblk.p, nr * cb / (op->slices <= 2 ? 4 : 2), st);
+      panel_unpack_int(st, Wblk.p, n, cb, nr, mx, op->slices, Qfull.p);
       BSN_HIP(hipGetLastError());
       n_compact_gathers++;
       return;
@@ -992,8 +1050,7 @@ struct HipSvdBackend : SvdBackend {
     // every rank rounds the same gathered block (column maxima over all n rows), then keeps its rows
     all_gather_rows(Wc, cb, Qfull.p);
     round_cols(Qfull.p, n, cb, false);
-    hipLaunchKernelGGL(k_take_rows, dim3((unsigned)((nr * cb + 255) / 256)), dim3(256), 0, st, Qfull.p, n, cb, nr,
-                       row0, Wc);
+    panel_take_rows(st, Qfull.p, n, cb, nr, row0, Wc);
     BSN_HIP(hipGetLastError());
   }
   void gram_to_host(const double *A, const double *B, int64_t rows, int p, int cb, double *out) {
@@ -1020,11 +1077,7 @@ struct HipSvdBackend : SvdBackend {
   // the ranks
   static constexpr int B2 = kMaxB * kMaxB;
   void update_W(int p, int cb, const double *C, const double *Ri, unsigned long long *mx) {
-    const dim3 rows((unsigned)((nr + 1023) / 1024));
-    if (cb <= 8)
-      hipLaunchKernelGGL((k_update<8>), rows, dim3(256), 0, st, Q.p, nr, p, C, Ri, cb, Wc, nr, nr, mx);
-    else
-      hipLaunchKernelGGL((k_update<16>), rows, dim3(256), 0, st, Q.p, nr, p, C, Ri, cb, Wc, nr, nr, mx);
+    panel_update(st, Q.p, nr, p, C, Ri, cb, Wc, nr, nr, mx);
   }
   // Gram blocks of the newest basis block + orthonormalisation of W against Q[:, :p] and itself, queued
   // without returning to the host; ONE synchronisation.  with_grams = false: orthonormalisation only
@@ -1085,7 +1138,7 @@ struct HipSvdBackend : SvdBackend {
       // the column maxima of the finished panel feed the rounding; with sample blocks they would have to be
       // combined over the ranks, so the distributed solve takes them from the gathered block instead
       unsigned long long *mxp = (pass == 1 && !dist) ? mx : nullptr;
-      hipLaunchKernelGGL(k_orth2, dim3(1), dim3(512), 0, st, a, mxp);
+      panel_orth2(st, a, mxp);
       update_W(p, cb, C, Ri, mxp);
     }
     BSN_HIP(hipGetLastError());
@@ -1148,16 +1201,14 @@ struct HipSvdBackend : SvdBackend {
   void W_minus_QC(int p, int cb, const double *C) override {
     mx_valid = false;
     copy_h2d(op->bed, dsmall.p, C, (size_t)p * cb * 8);
-    hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((nr + 255) / 256)), dim3(256), kTP * kMaxB * 8, st,
-                       Q.p, nr, p, dsmall.p, cb, Wc, nr, 1.0, -1.0, Wc, nr, nr);
+    panel_gemm_nn(st, Q.p, nr, p, dsmall.p, cb, Wc, nr, 1.0, -1.0, Wc, nr, nr);
     BSN_HIP(hipGetLastError());
     sync_stream();  // C is a host vector that may be reused
   }
   void W_times(int cb, int r, const double *M) override {
     mx_valid = false;
     copy_h2d(op->bed, dsmall.p, M, (size_t)cb * r * 8);
-    hipLaunchKernelGGL(k_right_mult, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, Wc, nr, nr,
-                       cb, r, dsmall.p);
+    panel_right_mult(st, Wc, nr, nr, cb, r, dsmall.p);
     BSN_HIP(hipGetLastError());
     sync_stream();
   }
@@ -1247,13 +1298,9 @@ struct HipSvdBackend : SvdBackend {
     BSN_HIP(hipStreamWaitEvent(up, ws.ev_early, 0));   // Z of this step and the stored Q are final
     for (int c0 = 0; c0 < k; c0 += kMaxB) {
       const int nc = k - c0 < kMaxB ? k - c0 : kMaxB;
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((nr + 255) / 256)), dim3(256), kTP * kMaxB * 8, up,
-                         Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, (const double *)nullptr, (int64_t)0,
-                         0.0, 1.0, dU.p + (int64_t)c0 * nr, nr, nr);
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((m_local + 255) / 256)), dim3(256),
-                         kTP * kMaxB * 8, up, Z.p, m_local, pp, dS.p + sk + (size_t)c0 * pp,
-                         nc, (const double *)nullptr, (int64_t)0, 0.0, 1.0,
-                         dV.p + (int64_t)c0 * m_local, m_local, m_local);
+      panel_gemm_nn(up, Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0, dU.p + (int64_t)c0 * nr, nr, nr);
+      panel_gemm_nn(up, Z.p, m_local, pp, dS.p + sk + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0, dV.p + (int64_t)c0 * m_local,
+                    m_local, m_local);
     }
     BSN_HIP(hipGetLastError());
     if (u) BSN_HIP(hipMemcpyAsync(u, dU.p, (size_t)n * k * 8, hipMemcpyDeviceToHost, up));
@@ -1280,12 +1327,9 @@ struct HipSvdBackend : SvdBackend {
     copy_h2d(op->bed, dS.p, S, (size_t)pp * keep * 8);
     for (int c0 = 0; c0 < keep; c0 += kMaxB) {
       const int nc = keep - c0 < kMaxB ? keep - c0 : kMaxB;
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((nr + 255) / 256)), dim3(256), kTP * kMaxB * 8, st, Q.p, nr, pp,
-                         dS.p + (size_t)c0 * pp, nc, (const double *)nullptr, (int64_t)0, 0.0, 1.0,
-                         tQ.p + (int64_t)c0 * nr, nr, nr);
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((m_local + 255) / 256)), dim3(256), kTP * kMaxB * 8, st, Z.p,
-                         m_local, pp, dS.p + (size_t)c0 * pp, nc, (const double *)nullptr, (int64_t)0, 0.0, 1.0,
-                         tZ.p + (int64_t)c0 * m_local, m_local, m_local);
+      panel_gemm_nn(st, Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0, tQ.p + (int64_t)c0 * nr, nr, nr);
+      panel_gemm_nn(st, Z.p, m_local, pp, dS.p + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0, tZ.p + (int64_t)c0 * m_local,
+                    m_local, m_local);
     }
     BSN_HIP(hipGetLastError());
     BSN_HIP(hipMemcpyAsync(Q.p, tQ.p, (size_t)nr * keep * 8, hipMemcpyDeviceToDevice, st));
@@ -1327,13 +1371,9 @@ struct HipSvdBackend : SvdBackend {
     copy_h2d(op->bed, dS.p + (size_t)pp * k, Sv.data(), (size_t)pp * k * 8);
     for (int c0 = 0; c0 < k && pp > 0; c0 += kMaxB) {
       int nc = k - c0 < kMaxB ? k - c0 : kMaxB;
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((nr + 255) / 256)), dim3(256), kTP * kMaxB * 8, st,
-                         Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, (const double *)nullptr, (int64_t)0,
-                         0.0, 1.0, dU.p + (int64_t)c0 * nr, nr, nr);
-      hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((m_local + 255) / 256)), dim3(256),
-                         kTP * kMaxB * 8, st, Z.p, m_local, pp, dS.p + (size_t)pp * k + (size_t)c0 * pp,
-                         nc, (const double *)nullptr, (int64_t)0, 0.0, 1.0,
-                         dV.p + (int64_t)c0 * m_local, m_local, m_local);
+      panel_gemm_nn(st, Q.p, nr, pp, dS.p + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0, dU.p + (int64_t)c0 * nr, nr, nr);
+      panel_gemm_nn(st, Z.p, m_local, pp, dS.p + (size_t)pp * k + (size_t)c0 * pp, nc, nullptr, 0, 0.0, 1.0,
+                    dV.p + (int64_t)c0 * m_local, m_local, m_local);
     }
     BSN_HIP(hipGetLastError());
     if (pp == 0) {
@@ -2000,3 +2040,208 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
   });
   return rc != 0 ? rc : (unconverged ? 2 : 0);
 }
+
+// ---- kernel-level entries for the tests (tests/test_gpu_svd_panel.py) --------------------------------------------------
+// The panel kernels one at a time, through the launch functions the backend uses, on caller-owned device memory
+// (bsn_malloc / bsn_memcpy_h2d / bsn_memcpy_d2h).  Null stream, synchronised before returning.  Every argument is checked
+// on the host before the first launch: no call can launch out of bounds.
+namespace bsn {
+namespace {
+constexpr int kPanelMaxP = 4096;   // basis columns the entries accept (the solve's cap is far below)
+void panel_done() {
+  BSN_HIP(hipGetLastError());
+  BSN_HIP(hipStreamSynchronize(nullptr));
+}
+// rows of a "rank's" sample block in the one-device restatements of the sharded exchanges
+int64_t panel_block_rows(int64_t n, int world) { return ((n + world - 1) / world + 3) / 4 * 4; }
+}  // namespace
+}  // namespace bsn
+
+extern "C" {
+
+int bsn_panel_gemm_tn(const double *d_A, int64_t lda, int32_t p, const double *d_B, int64_t ldb, int32_t cb, int64_t rows,
+                      double *d_C, int32_t ldc) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_A || !d_B || !d_C) fail("bsn_panel_gemm_tn: null pointer");
+    if (cb > 32) fail("internal: panel product with %d columns", (int)cb);
+    if (p < 1 || p > kPanelMaxP || cb < 1 || rows < 1 || rows > ((int64_t)1 << 31) || lda < rows || ldb < rows || ldc < p)
+      fail("bsn_panel_gemm_tn: dimensions");
+    DevBuf<double> partial;
+    partial.ensure(panel_partial_count(rows, p));
+    panel_gemm_tn(nullptr, d_A, lda, p, d_B, ldb, cb, rows, d_C, ldc, partial.p);
+    panel_done();
+  });
+}
+
+int bsn_panel_gemm_nn(const double *d_Q, int64_t ldq, int32_t p, const double *d_S, int32_t nc, const double *d_In, int64_t ldi,
+                      double alpha, double beta, double *d_Out, int64_t ldo, int64_t n) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_Q || !d_S || !d_Out || (alpha != 0.0 && !d_In)) fail("bsn_panel_gemm_nn: null pointer");
+    if (p < 1 || p > kPanelMaxP || nc < 1 || nc > kMaxB || n < 1 || n > ((int64_t)1 << 31) || ldq < n || ldo < n ||
+        (alpha != 0.0 && ldi < n))
+      fail("bsn_panel_gemm_nn: dimensions (at most %d columns)", kMaxB);
+    panel_gemm_nn(nullptr, d_Q, ldq, p, d_S, nc, d_In, ldi, alpha, beta, d_Out, ldo, n);
+    panel_done();
+  });
+}
+
+int bsn_panel_right_mult(double *d_W, int64_t ld, int64_t n, int32_t cb, int32_t r, const double *d_M) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_W || !d_M) fail("bsn_panel_right_mult: null pointer");
+    if (cb < 1 || cb > kMaxB || r < 1 || r > kMaxB || cb * r > 256 || n < 1 || n > ((int64_t)1 << 31) || ld < n)
+      fail("bsn_panel_right_mult: dimensions (at most %d columns)", kMaxB);
+    panel_right_mult(nullptr, d_W, ld, n, cb, r, d_M);
+    panel_done();
+  });
+}
+
+int bsn_panel_update(const double *d_Q, int64_t ldq, int32_t p, const double *d_C, const double *d_Ri, int32_t cb, double *d_W,
+                     int64_t ldw, int64_t n, uint64_t *d_mx) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_Ri || !d_W || (p > 0 && (!d_Q || !d_C))) fail("bsn_panel_update: null pointer");
+    if (p < 0 || p > kPanelMaxP || cb < 1 || cb > kMaxB || n < 1 || n > ((int64_t)1 << 31) || ldw < n || (p > 0 && ldq < n))
+      fail("bsn_panel_update: dimensions (at most %d columns)", kMaxB);
+    panel_update(nullptr, d_Q, ldq, p, d_C, d_Ri, cb, d_W, ldw, n, (unsigned long long *)d_mx);
+    panel_done();
+  });
+}
+
+int bsn_panel_round_cols(double *d_X, int64_t ld, int64_t rows, int32_t cb, int32_t slices, int32_t have_mx, uint64_t *d_mx,
+                         int32_t wide_grid) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_X || !d_mx) fail("bsn_panel_round_cols: null pointer");
+    if (cb < 1 || cb > kMaxB || rows < 1 || rows > ((int64_t)1 << 31) || ld < rows || slices < 1 || slices > 7)
+      fail("bsn_panel_round_cols: dimensions (at most %d columns, 1 to 7 slices)", kMaxB);
+    unsigned long long *mx = (unsigned long long *)d_mx;
+    if (!have_mx) {
+      BSN_HIP(hipMemsetAsync(mx, 0, (size_t)cb * 8, nullptr));
+      panel_col_absmax(nullptr, d_X, ld, rows, cb, mx, wide_grid != 0);
+    }
+    panel_round_cols(nullptr, d_X, ld, rows, cb, mx, slices);
+    panel_done();
+  });
+}
+
+// returns -1 where HipSvdBackend::fused would (the caller takes the step-by-step path), 0 when the queue ran
+int bsn_panel_fused_orth(double *d_QW, int64_t nr, int32_t p, int32_t p0, int32_t cb, int32_t iters, double *flag_out,
+                         double *Rout_out) {
+  bool unsupported = false;
+  const int rc = guarded([&] {
+    require_gpu();
+    if (!d_QW || !flag_out || !Rout_out) fail("bsn_panel_fused_orth: null pointer");
+    if (p < 0 || cb < 1 || nr < 1 || nr > ((int64_t)1 << 31) || iters < 0 || iters > 8)
+      fail("bsn_panel_fused_orth: dimensions");
+    if (cb > kMaxB || p + cb > kOrthMaxP) {
+      unsupported = true;
+      return;
+    }
+    // the newest basis block is the cb columns in front of the panel, as in a solve
+    if ((p == 0 && p0 != 0) || (p > 0 && (p < cb || p0 != p - cb))) fail("bsn_panel_fused_orth: p0 must be p - cb");
+    constexpr int B2 = kMaxB * kMaxB;
+    const size_t pc = (size_t)p * cb, hg = (size_t)(p + cb) * cb;
+    DevBuf<double> dorth, dM, partial;
+    dorth.ensure((size_t)16 + 3 * B2 + 7 * (size_t)(p + cb + 4) * kMaxB);
+    dM.ensure((size_t)kOrthMaxP * kOrthMaxP);
+    partial.ensure(panel_partial_count(nr, p + cb));
+    hipStream_t st = nullptr;
+    double *Q = d_QW, *Wc = d_QW + (int64_t)p * nr;
+    // the device copy of Q'Q as the earlier steps of a solve would have left it (the newest block is folded in again below)
+    BSN_HIP(hipMemsetAsync(dM.p, 0, (size_t)kOrthMaxP * kOrthMaxP * 8, st));
+    for (int c0 = 0; c0 < p; c0 += 2 * kMaxB)
+      panel_gemm_tn(st, Q, nr, p, Q + (int64_t)c0 * nr, nr, std::min(2 * kMaxB, p - c0), nr, dM.p + (size_t)c0 * kOrthMaxP,
+                    kOrthMaxP, partial.p);
+    // ---- the queue of HipSvdBackend::fused: the same arena, the same order ----
+    unsigned long long *mx = (unsigned long long *)dorth.p;
+    double *flag = dorth.p + 16, *dRout = flag + 1, *dZtZ = dRout + B2, *X = dZtZ + pc, *HG1 = X + (p > 0 ? hg : 0),
+           *HG2 = HG1 + hg, *C = HG2 + hg, *Ct = C + pc, *Ri = Ct + pc;
+    const double *A0 = p > 0 ? Q : Wc;
+    BSN_HIP(hipMemsetAsync(flag, 0, (size_t)(1 + B2) * 8, st));
+    OrthSmall a;
+    a.p = p;
+    a.cb = cb;
+    a.p0 = p0;
+    a.QtQ = p > 0 ? X : nullptr;
+    a.ldq = p + cb;
+    a.M = dM.p;
+    a.ldm = kOrthMaxP;
+    a.C = C;
+    a.Ct = Ct;
+    a.Ri = Ri;
+    a.Rout = dRout;
+    a.flag = flag;
+    a.iters = iters;
+    a.Cs = a.Gs = a.Rs = a.Ris = a.Ro = a.Dv = a.tmp = nullptr;
+    for (int pass = 0; pass < 2; pass++) {
+      double *HG = pass == 0 ? HG1 : HG2;
+      if (pass == 0 && p > 0)
+        panel_gemm_tn(st, Q, nr, p + cb, Q + (int64_t)p0 * nr, nr, 2 * cb, nr, X, p + cb, partial.p);
+      else
+        panel_gemm_tn(st, A0, nr, p + cb, Wc, nr, cb, nr, HG, p + cb, partial.p);
+      a.pass = pass;
+      a.HG = HG;
+      unsigned long long *mxp = pass == 1 ? mx : nullptr;
+      panel_orth2(st, a, mxp);
+      panel_update(st, Q, nr, p, C, Ri, cb, Wc, nr, nr, mxp);
+    }
+    panel_done();
+    std::vector<double> h((size_t)1 + B2);
+    BSN_HIP(hipMemcpy(h.data(), flag, h.size() * 8, hipMemcpyDeviceToHost));
+    *flag_out = h[0];
+    for (int t = 0; t < cb * cb; t++) Rout_out[t] = h[1 + (size_t)t];
+  });
+  return rc != 0 ? rc : (unsupported ? -1 : 0);
+}
+
+int bsn_panel_compact_gather(const double *d_full, int64_t n, int32_t cb, int32_t world, int32_t slices, double *d_out) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_full || !d_out) fail("bsn_panel_compact_gather: null pointer");
+    if (n < 1 || n > ((int64_t)1 << 31) || cb < 1 || cb > kMaxB || world < 1 || world > 64 || slices < 1 || slices > 4)
+      fail("bsn_panel_compact_gather: dimensions (at most %d columns, 64 ranks, 4 slices)", kMaxB);
+    const int64_t nr = panel_block_rows(n, world);
+    const size_t blk = (size_t)nr * cb, isz = slices <= 2 ? 2 : 4;
+    DevBuf<double> Wr, q_all;
+    DevBuf<unsigned long long> gmax, mx;
+    Wr.ensure(blk * world);
+    q_all.ensure((blk * world * isz + 7) / 8);
+    gmax.ensure((size_t)world * kMaxB);
+    mx.ensure(kMaxB);
+    hipStream_t st = nullptr;
+    BSN_HIP(hipMemsetAsync(gmax.p, 0, (size_t)world * kMaxB * 8, st));
+    for (int r = 0; r < world; r++) {
+      panel_take_rows(st, d_full, n, cb, nr, (int64_t)r * nr, Wr.p + blk * r);
+      panel_col_absmax(st, Wr.p + blk * r, nr, nr, cb, gmax.p + (size_t)r * cb, false);
+    }
+    panel_max_over_ranks(st, gmax.p, world, cb, mx.p);
+    for (int r = 0; r < world; r++)
+      panel_pack_int(st, Wr.p + blk * r, nr, cb, mx.p, slices, (char *)q_all.p + blk * r * isz);
+    panel_unpack_int(st, q_all.p, n, cb, nr, mx.p, slices, d_out);
+    panel_done();
+  });
+}
+
+int bsn_panel_block_roundtrip(const double *d_full, int64_t n, int32_t cb, int32_t world, double *d_out, double *d_placed) {
+  return guarded([&] {
+    require_gpu();
+    if (!d_full || !d_out || !d_placed) fail("bsn_panel_block_roundtrip: null pointer");
+    if (n < 1 || n > ((int64_t)1 << 31) || cb < 1 || cb > kMaxB || world < 1 || world > 64)
+      fail("bsn_panel_block_roundtrip: dimensions (at most %d columns, 64 ranks)", kMaxB);
+    const int64_t nr = panel_block_rows(n, world);
+    DevBuf<double> blk;
+    blk.ensure((size_t)world * cb * nr);
+    hipStream_t st = nullptr;
+    panel_block(st, d_full, n, cb, nr, world, blk.p);
+    panel_unblock(st, blk.p, n, cb, nr, d_out);
+    // every rank's chunk (nr x cb) as a received segment into its rows of a panel with world * nr rows
+    for (int r = 0; r < world; r++)
+      panel_place_rows(st, blk.p + (size_t)r * cb * nr, nr, cb, (int64_t)r * nr, (int64_t)world * nr, d_placed);
+    panel_done();
+  });
+}
+
+}  // extern "C"

@@ -822,6 +822,42 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
                      double *cost2_out, double *perc_kept_out, int32_t *n_block_ok_out, int32_t *all_last_out,
                      int32_t *levels_run_out, double *seconds_out);
 
+/* ---- the panel kernels of bsn_bed_randomsvd one at a time: FOR TESTS, not part of the drop-in surface ----------------------
+ * The tall-skinny fp64 algebra between the streaming passes of a solve (bigsnpr_amd/csrc/svd.hip), through the launch
+ * functions the solve itself uses, on DEVICE matrices of the caller (column-major; bsn_malloc / bsn_memcpy_h2d /
+ * bsn_memcpy_d2h).  Null stream, synchronised before returning.  Every entry checks its arguments before the first launch and
+ * refuses by name: null pointers, 1 <= cb <= 32 for bsn_panel_gemm_tn and cb, r, nc <= 16 elsewhere, cb * r <= 256, leading
+ * dimensions below the row count.  No stability is promised for these names. */
+/* C (p x cb, leading dimension ldc) = A[:, :p]' B[:, :cb] over `rows` rows: k_gemm_tn<1|2> + k_gemm_tn_reduce */
+int bsn_panel_gemm_tn(const double *d_A, int64_t lda, int32_t p, const double *d_B, int64_t ldb, int32_t cb, int64_t rows,
+                      double *d_C, int32_t ldc);
+/* Out[:, :nc] = alpha In[:, :nc] + beta Q[:, :p] S (p x nc, leading dimension p); In may be NULL when alpha == 0 and may be Out */
+int bsn_panel_gemm_nn(const double *d_Q, int64_t ldq, int32_t p, const double *d_S, int32_t nc, const double *d_In, int64_t ldi,
+                      double alpha, double beta, double *d_Out, int64_t ldo, int64_t n);
+/* in place W[:, :r] = W[:, :cb] M (cb x r, leading dimension cb) */
+int bsn_panel_right_mult(double *d_W, int64_t ld, int64_t n, int32_t cb, int32_t r, const double *d_M);
+/* in place W <- (W - Q[:, :p] C) Ri: k_update<8|16>.  C p x cb (leading dimension p), Ri cb x cb; d_mx: 16 x uint64 or NULL, the
+ * bit patterns of the column maxima of |W| are folded into its first cb entries by atomic max */
+int bsn_panel_update(const double *d_Q, int64_t ldq, int32_t p, const double *d_C, const double *d_Ri, int32_t cb, double *d_W,
+                     int64_t ldw, int64_t n, uint64_t *d_mx);
+/* rounding of the columns of X to the 8 * slices bit grid of the streaming products.  have_mx = 0: d_mx [16] is cleared and filled
+ * by k_col_absmax first, with 256 (wide_grid != 0) or 64 workgroups per column; have_mx != 0: d_mx is taken as it is */
+int bsn_panel_round_cols(double *d_X, int64_t ld, int64_t rows, int32_t cb, int32_t slices, int32_t have_mx, uint64_t *d_mx,
+                         int32_t wide_grid);
+/* the device queue of the fused block step on d_QW (nr x (p + cb), the panel W behind the basis Q, leading dimension nr): both
+ * passes of gemm_tn -> k_orth2 -> k_update, with p > 0 the [Q W]'[Qb W] product of pass 0 (Qb = columns p0 = p - cb .. p - 1),
+ * no host round trip in between.  W is replaced in place; flag_out [1] and Rout_out [cb * cb] go to the host.  Returns -1 (and does
+ * nothing) where the solve takes the step-by-step path: cb > 16 or p + cb > 384. */
+int bsn_panel_fused_orth(double *d_QW, int64_t nr, int32_t p, int32_t p0, int32_t cb, int32_t iters, double *flag_out,
+                         double *Rout_out);
+/* what the sharded solve's rounding of a finished block does, on one device and without a communicator: `world` sample blocks of
+ * nr = ceil(n / world) rounded up to a multiple of 4 rows, k_take_rows + k_col_absmax per block, k_max_over_ranks,
+ * k_pack_int<int16 (slices <= 2) | int32> per block, k_unpack_int into d_out (n x cb, leading dimension n).  d_full: n x cb, ld n */
+int bsn_panel_compact_gather(const double *d_full, int64_t n, int32_t cb, int32_t world, int32_t slices, double *d_out);
+/* k_block of d_full (n x cb, ld n) into the same sample blocks, k_unblock into d_out (n x cb) and k_place_rows of every block into
+ * d_placed (world * nr rows, leading dimension world * nr) */
+int bsn_panel_block_roundtrip(const double *d_full, int64_t n, int32_t cb, int32_t world, double *d_out, double *d_placed);
+
 /* ---- device memory + timing helpers for hosts without a HIP binding -------- */
 int bsn_malloc(void **d_ptr, int64_t bytes);
 int bsn_free(void *d_ptr);

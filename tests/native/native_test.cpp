@@ -137,6 +137,7 @@ struct HostBackend : SvdBackend {
   // ---- the fused block step of the product's HIP backend, with host loops for the tall products and the
   // SAME small-matrix code (orth_small.hpp) the device runs in one workgroup ----
   int fused_mode = 0;   // 0 = step-by-step path only; 1 = two-pass fused path (nt_set_fused)
+  int orth_iters = 3;   // Neumann terms of the fused step (nt_fused_orth sets what the device entry is given)
   int n_fused = 0, n_careful = 0;
   std::vector<double> Mdev;   // the "device" copy of Q'Q, leading dimension kOrthMaxP
   struct HostCtx {
@@ -183,7 +184,7 @@ struct HostBackend : SvdBackend {
     double flag = 0.0;
     OrthSmall a;
     a.p = p; a.cb = cb; a.p0 = p0; a.QtQ = p > 0 ? blkQ : nullptr; a.ldq = p; a.M = Mdev.data(); a.ldm = kOrthMaxP;
-    a.C = C.data(); a.Ct = Ct.data(); a.Ri = Ri.data(); a.Rout = Ro.data(); a.flag = &flag; a.iters = 3;
+    a.C = C.data(); a.Ct = Ct.data(); a.Ri = Ri.data(); a.Rout = Ro.data(); a.flag = &flag; a.iters = orth_iters;
     a.Cs = Cs.data(); a.Gs = Gs.data(); a.Rs = Rs.data(); a.Ris = Ris.data(); a.Ro = Rob.data(); a.Dv = Dv.data(); a.tmp = tmp.data();
     HostCtx cx;
     for (int pass = 0; pass < 2; pass++) {
@@ -347,6 +348,38 @@ void nt_svd_host(const double *A, int64_t n, int64_t m_local, int64_t m_total, i
   // below what the rounded products resolve)
   info[7] = (r.exhausted && r.exhausted_resid > 1e-9 ? 1 : 0) | (r.below_resolution > 0 ? 2 : 0);
   *resid = r.max_rel_resid;
+}
+
+// The fused host step on a given basis and panel (tests/test_gpu_svd_panel.py: the CPU twin of bsn_panel_fused_orth).
+// Q n x p and W n x cb column-major, p0 = p - cb (0 for p == 0); Q'Q of the stored basis is formed here by plain loops.
+// W is replaced by the orthonormalised panel (left as it was when the flag is raised); Rout_out [cb * cb].
+// Returns what fused() returns: cb, -1 (not supported) or -2 (flag raised).
+int nt_fused_orth(const double *Q, double *W, int64_t n, int p, int p0, int cb, int iters, double *flag_out, double *Rout_out) {
+  HostBackend bk;
+  bk.n = n;
+  bk.m_local = 0;
+  bk.m_total = 0;
+  bk.fused_mode = 1;
+  bk.orth_iters = iters;
+  bk.Q.assign(Q, Q + (size_t)n * p);
+  bk.W.assign(W, W + (size_t)n * cb);
+  if (p + cb <= kOrthMaxP) {
+    bk.Mdev.assign((size_t)kOrthMaxP * kOrthMaxP, 0.0);
+    for (int j = 0; j < p; j++)
+      for (int i = 0; i < p; i++) {
+        double s = 0;
+        for (int64_t r = 0; r < n; r++) s += Q[r + (size_t)i * n] * Q[r + (size_t)j * n];
+        bk.Mdev[(size_t)i + (size_t)j * kOrthMaxP] = s;
+      }
+  }
+  std::vector<double> blkZ((size_t)p * cb + 1), blkQ((size_t)p * cb + 1), Rout;
+  const int r = bk.fused(p, p0, cb, blkZ.data(), blkQ.data(), Rout);
+  *flag_out = r == -2 ? 1.0 : 0.0;
+  if (r == cb) {
+    std::memcpy(W, bk.W.data(), sizeof(double) * (size_t)n * cb);
+    std::memcpy(Rout_out, Rout.data(), sizeof(double) * (size_t)cb * cb);
+  }
+  return r;
 }
 
 // ---- ld_plan.hpp (tests/test_ld_plan_cpu.py) ----
