@@ -144,6 +144,10 @@ SIGNATURES = {
     "bsn_king_fetch": (C.c_int, [vp, i32p, i32p, i32p, f64p]),
     "bsn_king_free": (C.c_int, [vp]),
     "bsn_king_last_ms": (C.c_int, [f64p]),
+    "bsn_bed_ibd": (C.c_int, [vp, i64p, i64, i64p, i64, u8p, C.c_double, C.c_int, C.POINTER(C.c_int64), C.POINTER(vp)]),
+    "bsn_ibd_fetch": (C.c_int, [vp, i32p, i32p, i32p, f64p, f64p, C.POINTER(C.c_int64)]),
+    "bsn_ibd_free": (C.c_int, [vp]),
+    "bsn_ibd_last_ms": (C.c_int, [f64p]),
     "bsn_bed_to_fbm": (C.c_int, [vp, i64p, i64, i64p, i64, u8p]),
     "bsn_bed_readbina": (C.c_int, [vp, u8p, u8p]),
     "bsn_bed_is_streamed": (C.c_int, [vp]),

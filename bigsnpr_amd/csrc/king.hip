@@ -13,12 +13,15 @@
 //     k_king_scan     exclusive scan of those counts, one workgroup, fixed order
 //     k_king_write    every segment writes its rows behind its offset
 // No float atomics, no order that depends on the schedule: two calls return the same bytes.  DESIGN.md 3.5n.
+// The walk over the batches of tile pairs (kingwalk::pairs_walk, king_walk.hpp) is shared with bed_ibd (ibd.hip), whose
+// table is another reading of the same stash: what a row is and which pairs pass is the caller's PairSink.
 #include <algorithm>
 #include <memory>
 #include <vector>
 
 #include "bsn_internal.hpp"
 #include "king_step.hpp"
+#include "king_walk.hpp"
 #include "plane_decode.hpp"
 
 struct bsn_king {
@@ -31,9 +34,7 @@ struct bsn_king {
 namespace bsn {
 namespace {
 
-constexpr int KT = 64;                   // samples per tile edge
-constexpr int kBatchTiles = 2048;        // tile pairs whose dense statistics are held at once (28 B x 4096 each: 235 MB)
-constexpr size_t kStashCnt = (size_t)5 * KT * KT, kStashKin = (size_t)KT * KT;
+using namespace kingwalk;   // KT, kBatchTiles, the stash, Batch, PairSink
 
 // device milliseconds of the last call of this process (bsn_king_last_ms): the operand (gathered selection, sample-major
 // copy, row list), the per-sample totals of the complete-data path (0 on the general path), the pair kernel, the compaction
@@ -184,26 +185,10 @@ __global__ __launch_bounds__(256, 2) void k_king_pairs(Operand op, const int2 *_
     }
 }
 
-// A batch holds the tile rows a0 .. a1 - 1, tile row a with its T - a tile pairs (a, a), (a, a + 1), ... in that order.
-struct Batch {
-  int a0, T;
-  int64_t i0, i1, n;   // the samples (positions of ind_row) i0 <= i < i1 of the batch; n: all samples
-  double thr;
-  int filter;
-};
-__device__ __forceinline__ int64_t tile_slot(const Batch &B, int a, int b) {
-  const int64_t k = a - B.a0;
-  return k * B.T - k * (2 * (int64_t)B.a0 + k - 1) / 2 + (b - a);
-}
-// segment = (sample i of the batch, column tile b), one wave each: is the lane's pair (i, 64 b + lane) a row of the table?
+// is the lane's pair of the segment (king_walk.hpp) a row of the table?
 __device__ __forceinline__ bool seg_row(const Batch &B, const double *__restrict__ st_kin, int64_t seg, int lane, int64_t &i, int64_t &j,
                                         size_t &slot, int &e) {
-  i = B.i0 + seg / B.T;
-  const int b = (int)(seg % B.T), a = (int)(i / KT);
-  j = (int64_t)b * KT + lane;
-  if (b < a || j <= i || j >= B.n) return false;
-  slot = (size_t)tile_slot(B, a, b);
-  e = (int)(i - (int64_t)a * KT) * KT + lane;
+  if (!seg_pair(B, seg, lane, i, j, slot, e)) return false;
   return !B.filter || king::passes(st_kin[slot * kStashKin + e], B.thr);
 }
 
@@ -295,17 +280,42 @@ void table_reserve(bsn_king *K, int64_t need, int64_t keep, hipStream_t st) {
   K->cap = cap;
 }
 
-void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, double thr, int filter,
-              int64_t *count_out, bsn_king **out) {
+// the rows of bed_king's table: the stash's own columns, filtered by the kinship
+struct KingSink final : PairSink {
+  bsn_king *K;
+  explicit KingSink(bsn_king *k) : K(k) {}
+  void reserve(int64_t need, int64_t keep, hipStream_t st) override { table_reserve(K, need, keep, st); }
+  void count(const Batch &B, const int32_t *, const double *st_kin, int64_t nseg, int32_t *cnt, hipStream_t st) override {
+    hipLaunchKernelGGL(k_king_count, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, st, B, st_kin, nseg, cnt);
+    BSN_HIP(hipGetLastError());
+  }
+  void write(const Batch &B, const int32_t *st_cnt, const double *st_kin, int64_t nseg, const int64_t *off, int64_t base,
+             hipStream_t st) override {
+    hipLaunchKernelGGL(k_king_write, dim3((unsigned)((nseg + 3) / 4)), dim3(256), 0, st, B, st_cnt, st_kin, nseg, off, base, K->d_i1->p,
+                       K->d_i2->p, K->d_cnt->p, K->d_kin->p);
+    BSN_HIP(hipGetLastError());
+  }
+};
+
+}  // namespace
+
+namespace kingwalk {
+
+void pairs_check(bsn_bed *bed, int64_t n, int64_t m, const char *what) {
   require_gpu();
-  if (!bed || !count_out || !out) fail("bed_king: null argument");
-  refuse_generic(bed, "bed_king");
-  require_bits(bed, 2, "bed_king");
-  require_resident(bed, "bed_king");
-  if (n < 2) fail("bed_king: at least 2 samples are needed to form a pair ('ind.row' holds %lld)", (long long)n);
-  if (m < 1) fail("bed_king: at least 1 variant is needed ('ind.col' holds %lld)", (long long)m);
+  if (!bed) fail("%s: null argument", what);
+  refuse_generic(bed, what);
+  require_bits(bed, 2, what);
+  require_resident(bed, what);
+  if (n < 2) fail("%s: at least 2 samples are needed to form a pair ('ind.row' holds %lld)", what, (long long)n);
+  if (m < 1) fail("%s: at least 1 variant is needed ('ind.col' holds %lld)", what, (long long)m);
   if (m > king::kMaxVariants)
-    fail("bed_king: %lld variants: the int32 plane sums are exact for fewer than 2^29 variants only", (long long)m);
+    fail("%s: %lld variants: the int32 plane sums are exact for fewer than 2^29 variants only", what, (long long)m);
+}
+
+int64_t pairs_walk(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, double thr, int filter,
+                   const char *what, PairSink &sink, double ms[4]) {
+  pairs_check(bed, n, m, what);
   BSN_HIP(hipSetDevice(bed->device));
   // (no list: the first n samples, whose positions are their rows)
   bool rows_ident = true, cols_all = m == bed->m;
@@ -322,7 +332,6 @@ void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *in
     cols_all = cols_all && c == j;
     complete = complete && bed->na_cnt[(size_t)c] == 0;
   }
-  for (double &v : g_last_ms) v = 0.0;
 
   // ---- the operand: the handle's own sample-major copy (all variants in file order; a row list selects its rows), or
   // the copy of a gathered image of the selection
@@ -345,7 +354,7 @@ void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *in
     copy_h2d(src, d_rows.ensure((size_t)npad), rows.data(), (size_t)npad * 4);
   }
   if (!image_smaj(src))
-    fail("bed_king: no room for the sample-major operand of the selection (%.1f GB beside the image; BSN_NO_SMAJ forbids it too)",
+    fail("%s: no room for the sample-major operand of the selection (%.1f GB beside the image; BSN_NO_SMAJ forbids it too)", what,
          (double)round_up(src->n, 256) * (double)round_up((src->m + 3) / 4 + 128, 256) / 1e9);
   evo.mark(1, st);
   const int64_t nch = (m + 511) / 512;
@@ -394,16 +403,11 @@ void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *in
   d_segcnt.ensure((size_t)max_seg);
   d_off.ensure((size_t)max_seg + 1);
 
-  std::unique_ptr<bsn_king> K(new bsn_king());
-  K->bed = bed;
-  K->d_i1 = std::make_unique<DevBuf<int32_t>>();
-  K->d_i2 = std::make_unique<DevBuf<int32_t>>();
-  K->d_cnt = std::make_unique<DevBuf<int32_t>>();
-  K->d_kin = std::make_unique<DevBuf<double>>();
-  if (!filter) table_reserve(K.get(), n * (n - 1) / 2, 0, st);
+  int64_t count = 0;
+  if (!filter) sink.reserve(n * (n - 1) / 2, 0, st);
   BSN_HIP(hipStreamSynchronize(st));
-  g_last_ms[0] = evo.ms(0, 1);
-  if (complete) g_last_ms[1] = ev.ms(0, 1);
+  ms[0] += evo.ms(0, 1);
+  if (complete) ms[1] += ev.ms(0, 1);
 
   std::vector<int2> tiles;
   for (size_t c = 0; c + 1 < cut.size(); c++) {
@@ -428,28 +432,42 @@ void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *in
       hipLaunchKernelGGL(k_king_pairs<true>, dim3((unsigned)tiles.size()), dim3(256), 0, st, op, d_tiles.p, d_stc.p, d_stk.p);
     BSN_HIP(hipGetLastError());
     ev.mark(1, st);
-    const unsigned gseg = (unsigned)((nseg + 3) / 4);
-    hipLaunchKernelGGL(k_king_count, dim3(gseg), dim3(256), 0, st, B, d_stk.p, nseg, d_segcnt.p);
-    BSN_HIP(hipGetLastError());
+    sink.count(B, d_stc.p, d_stk.p, nseg, d_segcnt.p, st);
     hipLaunchKernelGGL(k_king_scan, dim3(1), dim3(1024), 0, st, d_segcnt.p, nseg, d_off.p, d_off.p + max_seg);
     BSN_HIP(hipGetLastError());
     ev.mark(2, st);
     int64_t rows_batch = 0;
     copy_d2h(src, &rows_batch, d_off.p + max_seg, 8);
     BSN_HIP(hipStreamSynchronize(st));
-    table_reserve(K.get(), K->count + rows_batch, K->count, st);
+    sink.reserve(count + rows_batch, count, st);
     ev.mark(3, st);
-    if (rows_batch > 0) {
-      hipLaunchKernelGGL(k_king_write, dim3(gseg), dim3(256), 0, st, B, d_stc.p, d_stk.p, nseg, d_off.p, K->count, K->d_i1->p,
-                         K->d_i2->p, K->d_cnt->p, K->d_kin->p);
-      BSN_HIP(hipGetLastError());
-    }
+    if (rows_batch > 0) sink.write(B, d_stc.p, d_stk.p, nseg, d_off.p, count, st);
     ev.mark(4, st);
     BSN_HIP(hipStreamSynchronize(st));
-    g_last_ms[2] += ev.ms(0, 1);
-    g_last_ms[3] += ev.ms(1, 2) + ev.ms(3, 4);
-    K->count += rows_batch;
+    ms[2] += ev.ms(0, 1);
+    ms[3] += ev.ms(1, 2) + ev.ms(3, 4);
+    count += rows_batch;
   }
+  return count;
+}
+
+}  // namespace kingwalk
+
+namespace {
+
+void bed_king(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, double thr, int filter,
+              int64_t *count_out, bsn_king **out) {
+  if (!bed || !count_out || !out) fail("bed_king: null argument");
+  std::unique_ptr<bsn_king> K(new bsn_king());
+  K->bed = bed;
+  K->d_i1 = std::make_unique<DevBuf<int32_t>>();
+  K->d_i2 = std::make_unique<DevBuf<int32_t>>();
+  K->d_cnt = std::make_unique<DevBuf<int32_t>>();
+  K->d_kin = std::make_unique<DevBuf<double>>();
+  KingSink sink(K.get());
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  K->count = pairs_walk(bed, ind_row, n, ind_col, m, thr, filter, "bed_king", sink, ms);
+  for (int q = 0; q < 4; q++) g_last_ms[q] = ms[q];
   *count_out = K->count;
   *out = K.release();
 }

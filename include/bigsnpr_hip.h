@@ -362,6 +362,29 @@ int bsn_king_free(bsn_king *king);
  * [3] the compaction.  One record per process, written without a lock. */
 int bsn_king_last_ms(double *ms_out /* 4 */);
 
+/* ---- method-of-moments IBD table (bed_ibd / bed_ibdQC; what snp_plinkIBDQC asks of PLINK 1.9's --genome) ----
+ * For every pair of positions i < j of ind_row, over the selected variants where both samples are called: IBS0 (opposite
+ * homozygotes), IBS1 (one heterozygous, the other homozygous), IBS2 (the rest), and the estimate of csrc/ibd_step.hpp
+ * (DESIGN.md 3.5p): Z0, Z1, Z2 (PLINK's default, "bounded"), PI_HAT = Z1 / 2 + Z2 and DST = (IBS2 + IBS1 / 2) / S.  The
+ * moments E00, E01, E02, E11, E12 are means over the variants with more than 3 called alleles and both alleles seen among
+ * the frequency samples: the positions of ind_row where freq_mask is non-zero (NULL: all), summed in the fixed order of
+ * the header.  A pair without a shared call is NaN in every double.  filter = 0: every pair; otherwise the pairs with
+ * PI_HAT >= min_pi_hat (NaN passes nothing).  Rows ascend in (i, j); two calls return the same bytes.  The pair statistics
+ * are those of bsn_bed_king (same kernel, operand and batches; BSN_KING_GENERAL keeps its meaning).
+ * Refused by name: a byte (dosage) image, an out-of-core handle, n < 2, m < 1, m >= 2^29, no room for the sample-major
+ * operand or for the table, min_pi_hat outside [0, 1], a frequency mask without a sample, no variant used for the moments. */
+typedef struct bsn_ibd bsn_ibd;
+int bsn_bed_ibd(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m,
+                const uint8_t *freq_mask /* [n] or NULL */, double min_pi_hat, int filter, int64_t *count, bsn_ibd **out);
+/* i1, i2 [count] (positions in ind_row, 0-based), ibs [3 x count] (row k at 3 k: IBS0, IBS1, IBS2), est [5 x count] (row k
+ * at 5 k: Z0, Z1, Z2, PI_HAT, DST), E [5] and n_used (either may be NULL; filled for an empty table too).  The bsn_bed
+ * of the call must still be open. */
+int bsn_ibd_fetch(bsn_ibd *ibd, int32_t *i1, int32_t *i2, int32_t *ibs, double *est, double *E, int64_t *n_used);
+int bsn_ibd_free(bsn_ibd *ibd);
+/* device milliseconds (HIP events) of the last bsn_bed_ibd of this process: [0] .. [3] as bsn_king_last_ms, [4] the counting
+ * pass of the frequency samples, [5] the moment kernels.  One record per process, written without a lock. */
+int bsn_ibd_last_ms(double *ms_out /* 6 */);
+
 /* _bigsnpr_prod_and_rowSumsSq (6 args) src/bed-fun.cpp:103-133 (the kernel of
  * bed_projectSelfPCA, R/bed-projectPCA.R:45-59): XV[n x K] = A~ V[m x K] and
  * rowSumsSq[i] = sum_j A~[i, j]^2, column-major host buffers. */
