@@ -21,7 +21,7 @@ from .project import bed_projectPCA  # noqa: F401,E402
 from .plink_io import bed_to_bytes, snp_readBed, snp_writeBed  # noqa: F401,E402
 from .pcadapt import bed_pcadapt, multLinReg, snp_pcadapt  # noqa: F401,E402
 from .gwas import big_univLinReg, big_univLogReg  # noqa: F401,E402
-from .impute import snp_fastImputeSimple  # noqa: F401,E402
+from .impute import predictor_lists, snp_fastImpute, snp_fastImputeSimple  # noqa: F401,E402
 from .bgen import check_bgen_format, format_snp_id, snp_prodBGEN, snp_readBGEN, snp_readBGI  # noqa: F401,E402
 from .popstat import bed_counts_by_group, bed_fst, bed_MAF_by_group, snp_fst, snp_MAX3  # noqa: F401,E402
 from .king import bed_king, bed_kingQC, king_last_ms, king_norel  # noqa: F401,E402

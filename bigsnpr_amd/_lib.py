@@ -124,6 +124,8 @@ SIGNATURES = {
     "bsn_plr_last_stats": (C.c_int, [f64p]),
     "bsn_impute_simple": (C.c_int, [vp, C.c_int, C.c_uint64, C.POINTER(vp), u8p, i64p]),
     "bsn_impute_last_ms": (C.c_int, [f64p]),
+    "bsn_fast_impute": (C.c_int, [vp, i64p, i32p, C.c_double, C.c_uint64, C.POINTER(vp), u8p, f64p, i64p]),
+    "bsn_fast_impute_last_ms": (C.c_int, [f64p]),
     "bsn_inflate": (C.c_int, [u8p, i64p, i64, u8p, i64p, i32p]),
     "bsn_bgen_read": (C.c_int, [C.c_char_p, i64p, i64, i64, i64p, i64, u8p, C.c_int, C.c_uint64, i64, i64, i64, C.POINTER(vp), u8p,
                                 f64p, f64p]),

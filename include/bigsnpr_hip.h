@@ -225,6 +225,27 @@ int bsn_impute_simple(bsn_bed *src, int method, uint64_t seed, bsn_bed **out, ui
  * image, [2] the kernels that write the FBM bytes (0 when none were asked for) */
 int bsn_impute_last_ms(double *ms_out);
 
+/* R/impute.R:29-160 — R: snp_fastImpute, as one independent boosted-tree model per variant (the statement
+ * is bigsnpr_amd/csrc/fastimpute_step.hpp).  `src` is any resident 2-bit handle and is not modified; *out receives a NEW
+ * 2-bit handle (CODE_IMPUTE_PRED).  Variant j with a missing and an observed call is a target; its predictors are the
+ * variants pred_idx[pred_off[j] .. pred_off[j + 1]) (ascending, never j, possibly none), read from `src` as the codes
+ * 0, 1, 2, missing.  An observed sample trains with probability p_train (one Philox4x32-10 call keyed by `seed` with the
+ * counter (sample, variant)) and validates otherwise; when nobody trains, all observed samples do.  Ten rounds of one
+ * depth-4 tree on the logistic loss of call / 2 (eta 0.3, lambda 1, gamma 0, min_child_weight 1; exact greedy splits
+ * over thresholds 0.5 / 1.5 / 2.5 with a learnt direction for missing codes; gradients quantised to 2^-30 and summed as
+ * int64), then call = nearbyint(2 p) at every missing position.  infos (2 x m row-major, may be NULL): [0][j] the share
+ * of missing calls, [1][j] the share of validation samples whose call differs from the observed one (NaN for a variant
+ * that is no target or has no validation sample).  A variant without any observed call stays missing and is counted in
+ * *n_all_missing.  fbm_bytes_out (n x m column-major, may be NULL): the content the reference's file would have
+ * (4 + call at an imputed position).  Refused by name: a byte image, an out-of-core handle, p_train outside (0, 1], a
+ * predictor outside [0, m) or equal to its target, a result image or scratch that does not fit the free device memory. */
+int bsn_fast_impute(bsn_bed *src, const int64_t *pred_off /* [m+1] */, const int32_t *pred_idx, double p_train, uint64_t seed,
+                    bsn_bed **out, uint8_t *fbm_bytes_out /* or NULL */, double *infos /* 2 x m */, int64_t *n_all_missing);
+/* device milliseconds (HIP events, host copies excluded) of the last bsn_fast_impute of this process: ms_out[0] the
+ * boosting kernel, [1] the copy of the image it rewrites, [2] the kernels that write the FBM bytes (0 when none were
+ * asked for) */
+int bsn_fast_impute_last_ms(double *ms_out);
+
 /* ---- snp_readBGEN / snp_prodBGEN: inflate and decode BGEN on the device ----------------------------------
  * BGEN v1.2 files as the UK Biobank ships them (R/read-bgen.R, src/read-bgen.cpp, src/prod-bgen.cpp): layout 2, zlib,
  * two alleles, unphased, 8 bits per probability.  The probabilities of a variant are one zlib stream of 10 + 3 N bytes;
