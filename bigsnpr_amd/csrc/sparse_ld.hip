@@ -20,6 +20,7 @@
 // the results equal the sequential loop bit for bit.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -106,6 +107,14 @@ double lassosum2_gap0(const double *beta_hat, int64_t m) {
   double ss = 0.0;
   for (int64_t j = 0; j < m; j++) ss = ss + beta_hat[j] * beta_hat[j];
   return 2 * ss;
+}
+
+// chains or grid points per launch: what the free memory holds, or BSN_CHAIN_BATCH=<n> of them if that is fewer (read on
+// every call; the seam through which tests/test_gpu_chain_batches.py runs the batch loops of the three drivers)
+int64_t chain_batch(int64_t batch) {
+  const char *e = getenv("BSN_CHAIN_BATCH");
+  const long long n = e ? atoll(e) : 0;
+  return n >= 1 ? std::min<int64_t>(batch, n) : batch;
 }
 
 constexpr int kAxpyBatch = 32;   // entries per lane and round of a column update (2 048 per round: a C5 column in two)
@@ -988,7 +997,7 @@ void run_gibbs(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, i
   const size_t n_out = (size_t)m * (size_t)(sampling ? num_iter : G);
   const int64_t per_g = (s->m2 + 2 * m) * 8;
   const int64_t fixed_b = (int64_t)n_out * 8 + m * 24 + G * 48 + (int64_t)(env.lo.size() + env.hi.size()) * 4;
-  const int64_t batch = std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g);
+  const int64_t batch = chain_batch(std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g));
   if (batch < 1)
     fail("%s: the result (%lld B) and the state of one chain (%lld B) do not fit the free device memory", what,
          (long long)fixed_b, (long long)per_g);
@@ -1097,7 +1106,7 @@ void run_auto(const bsn_sfbm *s, const double *beta_hat, const double *n_vec, co
   const int64_t per_g = (s->m2 + 6 * m) * 8 + m * 4;
   const int64_t fixed_b = (int64_t)(3 * n_est + n_smp + 3 * n_path) * 8 + m * 32 + G * 32 +
                           (int64_t)(env.lo.size() + env.hi.size()) * 4;
-  const int64_t batch = std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g);
+  const int64_t batch = chain_batch(std::min<int64_t>(G, std::max<int64_t>((int64_t)(free_b / 4 * 3) - fixed_b, 0) / per_g));
   if (batch < 1)
     fail("%s: the results (%lld B) and the state of one chain (%lld B) do not fit the free device memory", what,
          (long long)fixed_b, (long long)per_g);
@@ -1303,6 +1312,7 @@ int bsn_lassosum2(const bsn_sfbm *s, const double *beta_hat, int64_t m, const do
     const int64_t per_g = (s->m2 + m) * 8;
     int64_t batch = G;
     if (per_g > 0) batch = std::min<int64_t>(G, (int64_t)(free_b / 4 * 3) / per_g);
+    batch = chain_batch(batch);
     if (batch < 1) fail("lassosum2: the state of one grid point (%lld B) does not fit the free device memory", (long long)per_g);
     int clock_khz = 0;
     int dev = 0;

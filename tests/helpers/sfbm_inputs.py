@@ -1,7 +1,8 @@
 """Synthetic, seeded inputs for the sparse-LD kernels of bigsnpr_amd/csrc/sparse_ld.hip, sized so that the loops of those
 kernels take a second turn, and the checks that the product tests share.  tests/test_sfbm_inputs_cpu.py proves without a
 GPU that each input crosses the threshold it is meant for (the thresholds are read from the source, `kernel_constants`);
-tests/test_gpu_sfbm_shapes.py runs the device on them.
+tests/test_gpu_sfbm_shapes.py runs the device on them, tests/test_gpu_ldpred2_auto_shapes.py runs snp_ldpred2_auto on them
+and on the inputs that only its kernel needs, and tests/test_gpu_chain_batches.py the batch loops of the three chain drivers.
 
 The bound of every product check.  A computed sum of L products, in ANY order and with or without fused multiply-adds,
 satisfies |fl(sum_k a_k x_k) - sum_k a_k x_k| <= gamma_L sum_k |a_k| |x_k| with gamma_L = L u / (1 - L u) and u = 2^-53
@@ -382,6 +383,85 @@ def gibbs_statement(ref, A, df, gp, seed, sub=None, burn_in=50, num_iter=100):
     """the CPU statement `ref.grid` with snp_ldpred2_grid's inputs from df, scaled back as R/LDpred2.R:139 does: (beta, moves)"""
     fp, fi, fx = csc_arrays(A)
     scale, bh, n = gibbs_inputs(df)
-    beta, moves, _ = ref.grid(fp, fi, fx, A.shape[0], bh, n, gp["h2"], gp["p"], gp["sparse"], ind_sub=sub, burn_in=burn_in,
-                              num_iter=num_iter, seed=seed, nthreads=16)
+    beta, moves, _ = ref.grid(fp, fi, fx, A.shape[0], bh, n, gp["h2"], gp["p"], gp["sparse"], ind_sub=sub, stream=gp.get("stream"),
+                              burn_in=burn_in, num_iter=num_iter, seed=seed, nthreads=16)
     return beta * scale[:, None], moves
+
+
+# ---- LDpred2-auto on the inputs above, and the inputs that only k_ldpred2_auto needs ------------------------------------------
+
+AUTO_SEED = 2024
+AUTO_WIDE = {"vec_p_init": (1.0, 0.05, 0.01), "h2_init": 0.2, "burn_in": WIDE_BURN_IN, "num_iter": WIDE_NUM_ITER, "report_step": 3}
+AUTO_SMALL = {"vec_p_init": (1.0, 0.1, 0.01), "h2_init": 0.3, "burn_in": SMALL_BURN_IN, "num_iter": SMALL_NUM_ITER,
+              "report_step": 4}
+
+
+def full_of(A):
+    """(p, i, x, m2) of the full columns, as the statements take them"""
+    return csc_arrays(A) + (A.shape[0],)
+
+
+def wide_auto_cases(A):
+    """(name, ind_corr, summary statistics, ascending) of the three selections of wide_band under auto"""
+    m2 = A.shape[0]
+    df = df_of(wide_beta_hat(m2), WIDE_N)
+    srt, uns = wide_subsets(m2)
+    return [("whole", None, df, True), ("ascending", srt, take(df, srt), True), ("unsorted", uns, take(df, uns), False)]
+
+
+STRADDLE_M = 320
+STRADDLE = {"vec_p_init": (0.7,), "h2_init": 0.2, "p_bounds": (0.7, 0.7), "burn_in": 5, "num_iter": 25, "report_step": 1}
+
+
+def straddle_case():
+    """320 coordinates of which p = 0.7 (held there by p_bounds) keeps about 260 causal: the size of the causal set after a
+    sweep falls on both sides of the stride of the epilogue's loops (kGibbsThreads) and on it"""
+    return as_full(banded_corr(STRADDLE_M, 6, seed=900, n=500)), small_df(STRADDLE_M, 901)
+
+
+WINDOW_LIMIT_M2 = 20_000
+WINDOW_LIMIT = {"vec_p_init": (1.0, 0.05, 0.01), "h2_init": 0.2, "burn_in": 5, "num_iter": 10, "report_step": 4, "use_MLE": True}
+
+
+def window_limit_cases(W, m2=WINDOW_LIMIT_M2):
+    """The summary statistics and the two matrices of test_window_limit in tests/test_gpu_ldpred2_grid.py, from the same
+    generator in the same order: a few entries per column, one of them `half` rows from the diagonal, so an envelope of
+    2 half + 64 rows.  W: the rows of the largest LDS window.  Yields (half, fits, A, df)."""
+    rng = np.random.default_rng(17)
+    df = {"beta": rng.normal(0, 0.05, m2), "beta_se": np.full(m2, 0.03), "n_eff": np.full(m2, 1500.0)}
+    for half, fits in ((W // 2 - 40, True), (W // 2, False)):
+        d = np.arange(m2 - half)
+        far = sparse.coo_matrix((rng.uniform(-0.05, 0.05, d.size), (d, d + half)), shape=(m2, m2))
+        near = sparse.diags([rng.uniform(-0.3, 0.3, m2 - 1)], [1])
+        up = sparse.csc_matrix(far + near)
+        yield half, fits, as_full(sparse.csc_matrix(up + up.T + sparse.identity(m2))), df
+
+
+def diverging_case(m2=200):
+    """the matrix and summary statistics of test_divergence_gives_the_statements_nan_pattern (tests/test_gpu_ldpred2_auto.py):
+    0.9 on the first two off-diagonals, not positive definite"""
+    A = sparse.csc_matrix(sparse.diags([np.full(m2 - 2, 0.9), np.full(m2 - 1, 0.9), np.ones(m2), np.full(m2 - 1, 0.9),
+                                        np.full(m2 - 2, 0.9)], [-2, -1, 0, 1, 2]))
+    rng = np.random.default_rng(17)
+    return as_full(A), {"beta": rng.normal(0, 0.05, m2), "beta_se": np.full(m2, 0.03), "n_eff": np.full(m2, 1500.0)}
+
+
+# ---- the batch loops of the three drivers -------------------------------------------------------------------------------------
+
+BATCH_CAPS = (1, 2, 4)               # of 5 chains: 5 batches of 1; 2, 2, 1; 4, 1.  Of the 8 grid points of SMALL_LASSO: 8, 4, 2 batches
+BATCH_CAPS_LASSO = (1, 2, 3, 4)      # 3: batches of 3, 3, 2, a last batch shorter than the others for the grid of 8 as well
+BATCH_M = 65
+# five chains: unequal p in an order that is not the sorted one (the drivers visit large p first), stream ids that are not 0 .. 4
+BATCH_CHAINS = {"p": np.array([0.03, 1.0, 0.005, 0.3, 0.1]), "h2": np.array([0.3, 0.2, 0.3, 0.25, 0.3]),
+                "sparse": np.array([False, False, True, False, True]), "stream": np.array([7, 3, 11, 5, 20], dtype=np.uint64)}
+BATCH_AUTO = {"vec_p_init": (0.03, 1.0, 0.005, 0.3, 0.1), "stream": np.array([7, 3, 11, 5, 20], dtype=np.uint64), "h2_init": 0.3,
+              "burn_in": SMALL_BURN_IN, "num_iter": SMALL_NUM_ITER, "report_step": 4}
+
+
+def batch_cases():
+    """(name, full matrix, ind_corr, summary statistics): the 130 columns of small_with_empty_columns, and BATCH_M of them
+    ascending and shuffled (both hold the two empty columns)"""
+    E = small_with_empty_columns()
+    asc, shuffled = small_subsets(BATCH_M)
+    return [("whole", E, None, small_df(SMALL_M2, 800, np.arange(SMALL_M2))), ("ascending", E, asc, small_df(BATCH_M, 801, asc)),
+            ("shuffled", E, shuffled, small_df(BATCH_M, 802, shuffled))]

@@ -11,12 +11,14 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import auto_statement  # noqa: E402
 import ldpred2_auto_ref as ref  # noqa: E402
+from auto_statement import equal_lists as _equal_lists  # noqa: E402
+from auto_statement import same as _same  # noqa: E402
 from scipy import sparse  # noqa: E402
 
 P4 = [1e-4, 0.01, 0.3, 1.0]
-ARRAYS = ("beta_est", "postp_est", "corr_est", "sample_beta", "path_p_est", "path_h2_est", "path_alpha_est")
-SCALARS = ("h2_est", "p_est", "alpha_est")
 
 
 @pytest.fixture(scope="module")
@@ -64,39 +66,10 @@ def sf100(ba, corr100):
         yield sf
 
 
-def _expected(ba, sf, full, df, vec_p_init, h2_init, seed, sub=None, stream=None, burn_in=20, num_iter=30, report_step=None,
-              allow_jump_sign=True, shrink_corr=1.0, use_MLE=True, p_bounds=(1e-5, 1.0), alpha_bounds=(-1.5, 0.5)):
-    """the statement on the full columns, finished as R/LDpred2.R:257-264 finishes a chain; df holds the rows of `sub`.
-    Returns the list of dicts and the statement's raw output (path_nb, moves)."""
-    fp, fi, fx, m2 = full
-    beta, se, n = (np.asarray(df[k]) for k in ("beta", "beta_se", "n_eff"))
-    sd = 1 / np.sqrt(n * se ** 2 + beta ** 2)
+def _expected(ba, sf, full, df, vec_p_init, h2_init, seed, sub=None, **kw):
+    """auto_statement.expected with the device's own mean LD score of the listed columns: an input to both sides"""
     mean_ld = float(np.mean(ba.ld_scores_sfbm(sf, sub)))
-    raw = ref.auto(fp, fi, fx, m2, beta * sd, n, 2 * np.log(sd), vec_p_init, h2_init, mean_ld, ind_sub=sub, stream=stream,
-                   burn_in=burn_in, num_iter=num_iter, report_step=report_step, no_jump_sign=not allow_jump_sign,
-                   shrink_corr=shrink_corr, use_mle=use_MLE, p_bounds=p_bounds, alpha_bounds=alpha_bounds, seed=seed, nthreads=16)
-    out = []
-    for g in range(len(vec_p_init)):
-        out.append({"beta_est": raw["beta_est"][:, g] / sd, "postp_est": raw["postp_est"][:, g], "corr_est": raw["corr_est"][:, g],
-                    "sample_beta": raw["sample_beta"][:, :, g], "path_p_est": raw["path_p"][:, g],
-                    "path_h2_est": raw["path_h2"][:, g], "path_alpha_est": raw["path_alpha"][:, g],
-                    "h2_est": np.mean(raw["path_h2"][burn_in:, g]), "p_est": np.mean(raw["path_p"][burn_in:, g]),
-                    "alpha_est": np.mean(raw["path_alpha"][burn_in:, g])})
-    return out, raw
-
-
-def _same(res, want):
-    assert len(res) == len(want)
-    for r, w in zip(res, want):
-        for k in ARRAYS:
-            assert np.shape(r[k]) == np.shape(w[k]), k
-            assert np.array_equal(r[k], w[k], equal_nan=True), k
-        for k in SCALARS:
-            assert np.array_equal(r[k], w[k], equal_nan=True), k
-
-
-def _equal_lists(a, b):
-    return all(np.array_equal(x[k], y[k], equal_nan=True) for x, y in zip(a, b) for k in ARRAYS + SCALARS)
+    return auto_statement.expected(full, df, mean_ld, vec_p_init, h2_init, seed, sub=sub, **kw)
 
 
 def test_auto_equals_the_statement_and_seeds(ba, data, sf100, full100):

@@ -39,5 +39,7 @@ def test_every_switch_of_the_library_is_documented():
     # every test file a row names exists
     for name in set(re.findall(r"`(test_\w+\.py)`", table)):
         assert os.path.isfile(os.path.join(ROOT, "tests", name)), name
+    for name in set(re.findall(r"`(tests/test_\w+\.py)", table)):          # written with its folder, with or without a ::test
+        assert os.path.isfile(os.path.join(ROOT, name)), name
     for name in set(re.findall(r"`(tools/\w+\.py)`", table)):
         assert os.path.isfile(os.path.join(ROOT, name)), name

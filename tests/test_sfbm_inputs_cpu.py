@@ -1,4 +1,5 @@
-"""The inputs of tests/test_gpu_sfbm_shapes.py (tests/helpers/sfbm_inputs.py) without a GPU: each one crosses the threshold
+"""The inputs of tests/test_gpu_sfbm_shapes.py, tests/test_gpu_ldpred2_auto_shapes.py and tests/test_gpu_chain_batches.py
+(tests/helpers/sfbm_inputs.py) without a GPU: each one crosses the threshold
 of the loop it is meant for, the thresholds being read from bigsnpr_amd/csrc/sparse_ld.hip, and the references are well
 behaved on it (no NaN column, every chain moves, a positive definite system whose iteration bound scipy's MINRES keeps).
 If a constant of the kernels is retuned, the test here names the input that no longer covers its loop."""
@@ -11,7 +12,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+import auto_statement  # noqa: E402
 import lassosum2_ref  # noqa: E402
+import ldpred2_auto_ref as auto_ref  # noqa: E402
 import ldpred2_ref  # noqa: E402
 import sfbm_inputs as si  # noqa: E402
 from scipy import sparse  # noqa: E402
@@ -189,6 +192,101 @@ def test_small_statements_move(m):
         beta, moves = si.gibbs_statement(ldpred2_ref, A, df, si.SMALL_CHAINS, 77, sub=sub, burn_in=si.SMALL_BURN_IN,
                                          num_iter=si.SMALL_NUM_ITER)
         assert beta.shape == (m, 3) and np.isfinite(beta).all() and np.all(moves > 0), (m, name, moves)
+
+
+# ---- LDpred2-auto: the statement alone on the inputs of tests/test_gpu_ldpred2_auto_shapes.py ----------------------------------------
+
+def _auto(A, df, sub, kw, seed=si.AUTO_SEED):
+    """the statement with the mean LD score summed on the host: (list of chains, raw output with path_nb and moves)"""
+    return auto_statement.expected(si.full_of(A), df, auto_statement.host_mean_ld(A, sub), seed=seed, sub=sub, **kw)
+
+
+def _finite(want):
+    return all(np.isfinite(w[k]).all() for w in want for k in auto_statement.ARRAYS + auto_statement.SCALARS)
+
+
+def test_wide_band_auto_needs_a_second_round_and_wraps_the_ring(K, wide):
+    A = wide
+    m2 = A.shape[0]
+    L = np.diff(A.indptr)
+    gibbs_round = K["kGibbsThreads"] * K["kGibbsAxpy"]
+    assert L.max() > gibbs_round, "wide_band no longer needs a second round of add_column in k_ldpred2_auto"
+    fp, fi, _ = si.csc_arrays(A)
+    for name, sub, df, ascending in si.wide_auto_cases(A):
+        fits, rows = auto_ref.envelope(fp, fi, m2, sub)
+        assert fits == ascending, name
+        if ascending:
+            # fewer ring rows than rows of dotprods: the ring wraps, a row r is not at ring[r]
+            assert rows <= auto_ref.window_rows() and rows < m2, (name, rows)
+        assert np.sum((L if sub is None else L[sub]) > gibbs_round) > 100, name
+        want, raw = _auto(A, df, sub, si.AUTO_WIDE)
+        print("auto on wide_band (%s): envelope %d rows, moves %s" % (name, rows, raw["moves"]))
+        assert _finite(want) and np.all(raw["moves"] > 0) and np.all(raw["path_nb"] >= 0), name
+        assert all(w["sample_beta"].shape == (df["beta"].size, 3) for w in want)
+
+
+@pytest.mark.parametrize("m", si.SMALL_M)
+def test_small_auto_statements_move(m):
+    block = 64
+    for name, A, sub, df in si.small_cases(m):
+        want, raw = _auto(A, df, sub, si.AUTO_SMALL)
+        nb = raw["path_nb"]
+        print("auto on %d coordinates (%s): moves %s, causal %d .. %d" % (m, name, raw["moves"], nb.min(), nb.max()))
+        assert _finite(want) and np.all(raw["moves"] > 0) and np.all(nb >= 0) and np.all(nb <= m), (m, name)
+        if m >= block - 1:
+            # the append to ind_causal starts inside the first block of 64 positions and, where m allows, behind it
+            below, at_or_above = np.any(nb < block, axis=0), np.any(nb >= block, axis=0)
+            assert np.any(below & at_or_above) if m >= block else below.any(), (m, name, nb.min(axis=0), nb.max(axis=0))
+        if m <= 2:
+            assert np.any((nb >= 1) & (nb <= 2))          # the MLE on one or two causal variants
+
+
+def test_straddle_case_ends_sweeps_on_both_sides_of_one_stride(K):
+    A, df = si.straddle_case()
+    stride = K["kGibbsThreads"]
+    want, raw = _auto(A, df, None, si.STRADDLE)
+    nb = raw["path_nb"][:, 0]
+    print("straddle: %d sweeps below %d, %d at it, %d above, range %d .. %d"
+          % (np.sum(nb < stride), stride, np.sum(nb == stride), np.sum(nb > stride), nb.min(), nb.max()))
+    assert _finite(want) and raw["moves"][0] > 0 and nb.min() >= 0
+    assert np.any(nb < stride) and np.any(nb == stride) and np.any(nb > stride)
+    assert np.all(want[0]["path_p_est"] == si.STRADDLE["p_bounds"][0])
+
+
+def test_window_limit_matrices_sit_on_both_sides_of_the_largest_window():
+    W = auto_ref.window_rows()
+    seen = []
+    for half, fits, A, df in si.window_limit_cases(W):
+        fp, fi, _ = si.csc_arrays(A)
+        got_fits, rows = auto_ref.envelope(fp, fi, A.shape[0])
+        assert A.shape[0] == si.WINDOW_LIMIT_M2 and rows == 2 * half + 64
+        assert got_fits == fits, (half, rows)
+        if fits:
+            assert -(-rows // 64) * 64 == W, "the fitting matrix no longer asks for the largest window"
+        else:
+            assert rows > W
+        seen.append(fits)
+    assert seen == [True, False]
+
+
+def test_batch_inputs_move_every_chain_and_grid_point():
+    """the inputs of tests/test_gpu_chain_batches.py: the visiting order differs from the given one, the stream ids are
+    not the positions, and no chain or grid point stands still (a stale buffer would then change nothing)"""
+    gp = si.BATCH_CHAINS
+    assert gp["p"].size == 5 and np.unique(gp["p"]).size == 5 and np.any(np.diff(gp["p"]) > 0)          # not large p first
+    assert not np.array_equal(gp["stream"], np.arange(5)) and np.array_equal(gp["p"], si.BATCH_AUTO["vec_p_init"])
+    assert max(si.BATCH_CAPS) < 5 and 5 % 2 and 5 % 4 and 8 % 3 and 3 in si.BATCH_CAPS_LASSO          # a shorter last batch
+    kw = {k: v for k, v in si.BATCH_AUTO.items() if k != "stream"}
+    for name, A, sub, df in si.batch_cases():
+        assert df["beta"].size == (si.SMALL_M2 if sub is None else si.BATCH_M)
+        assert sub is None or (si.EMPTY in sub and si.EMPTY_WITH_DIAGONAL in sub)
+        beta, iters, spars, moves = si.lassosum2_statement(lassosum2_ref, A, df, sub=sub, **si.SMALL_LASSO)
+        assert beta.shape[1] == 8 and np.isfinite(beta).all() and np.all(moves > 0), (name, moves)
+        beta, moves = si.gibbs_statement(ldpred2_ref, A, df, gp, 77, sub=sub, burn_in=si.SMALL_BURN_IN, num_iter=si.SMALL_NUM_ITER)
+        assert np.isfinite(beta).all() and np.all(moves > 0), (name, moves)
+        assert np.unique(beta, axis=1).shape[1] == 5
+        want, raw = _auto(A, df, sub, dict(kw, stream=si.BATCH_AUTO["stream"]), seed=77)
+        assert _finite(want) and np.all(raw["moves"] > 0), (name, raw["moves"])
 
 
 def test_repeated_index_statement_equals_the_transliteration():
