@@ -150,7 +150,11 @@ SIGNATURES = {
     "bsn_ibd_fetch": (C.c_int, [vp, i32p, i32p, i32p, f64p, f64p, C.POINTER(C.c_int64)]),
     "bsn_ibd_free": (C.c_int, [vp]),
     "bsn_ibd_last_ms": (C.c_int, [f64p]),
-    "bsn_bed_to_fbm": (C.c_int, [vp, i64p, i64, i64p, i64, u8p]),
+    "bsn_knn": (C.c_int, [vp, i64, i64, vp, i64, i64, C.c_int32, C.c_int32, i32p, f64p]),
+    "bsn_prob_dist": (C.c_int, [vp, i64, i64, C.c_int32, C.c_int32, f64p, f64p]),
+    "bsn_lof": (C.c_int, [vp, i64, i64, C.c_int32, i32p, C.c_int32, f64p]),
+    "bsn_knn_last_stats": (C.c_int, [f64p]),
+    "bsn_bed_to_fbm":(C.c_int, [vp, i64p, i64, i64p, i64, u8p]),
     "bsn_bed_readbina": (C.c_int, [vp, u8p, u8p]),
     "bsn_bed_is_streamed": (C.c_int, [vp]),
     "bsn_bed_streaming_kernels": (C.c_int, [vp, C.c_char_p, i64]),

@@ -765,6 +765,30 @@ int bsn_robust_sort(double *x, int64_t m);
 int bsn_robust_mc_window(const double *d_up, int64_t nu, const double *d_lo, int64_t nl, double a, double b, int64_t cap, double *out,
                          int64_t *count_out);
 
+/* ---- exact k nearest neighbours and the outlier-sample statistics over them (knn.hip) --------------------------------
+ * The outlier-sample step of the reference's PCA workflow (vignettes/bedpca.Rmd: bigutilsr::prob_dist(obj.svd$u), then
+ * dist.self / sqrt(dist.nn)), and bigutilsr::knn_parallel / LOF.  bigutilsr is external to the reference tree: parity with
+ * its numbers is not pinned; the rule is stated in csrc/knn_step.hpp and pinned against a CPU statement
+ * compiled from that header.  All pairs in fp64: squared distance acc = fma(t, t, acc), t = q[d] - x[d], d ascending;
+ * candidates ordered by (squared distance, 0-based index of the data point); the k smallest in that order.
+ * DEVICE matrices, column-major with a leading dimension (bsn_malloc / bsn_memcpy_h2d), not modified; host vectors out.
+ * Refused by name: p or k outside 1 .. 64, k above the number of candidates, 2^31 points or more, a non-finite coordinate,
+ * no room for the workspace.  BSN_KNN_SLABS=<s> forces the number of slabs of data points (same bits for every s). */
+/* d_data: n x p; d_query: nq x p, or NULL — self mode: the data is its own query (nq, ldq ignored) and the candidate with
+ * the query's own index is left out, by index (other rows equal to the query stay in, at distance 0).
+ * idx_out (int32, 0-based) / dist_out (the correctly rounded square root): nq x k, column-major */
+int bsn_knn(const double *d_data, int64_t n, int64_t ld, const double *d_query /* NULL: self mode */, int64_t nq, int64_t ldq,
+            int32_t p, int32_t k, int32_t *idx_out, double *dist_out);
+/* over the self-mode table with k = kNN: m2[i] = mean of the squared distances of i's neighbours; dist_self_out [n] =
+ * sqrt(m2); dist_nn_out [n] = mean of m2 over i's neighbours */
+int bsn_prob_dist(const double *d_U, int64_t n, int64_t ld, int32_t p, int32_t kNN, double *dist_self_out, double *dist_nn_out);
+/* local outlier factors (Breunig et al. 2000) for every kk of seq_k [nk] over the self-mode table with k = max(seq_k):
+ * lof_out n x nk, column-major.  Duplicated rows give inf and NaN as IEEE has them */
+int bsn_lof(const double *d_U, int64_t n, int64_t ld, int32_t p, const int32_t *seq_k, int32_t nk, double *lof_out);
+/* the last of the three calls above in this process: device ms of the packing pass, the scan, the merge, what follows the
+ * table (square roots, statistics); then the slab count and the queries per workgroup it ran with */
+int bsn_knn_last_stats(double *out /* 6 */);
+
 /* R/clumping.R:106, R/bed-clumping.R:48 — `ord <- order(S.chr, decreasing = TRUE)` — for every chromosome at once: S [m]
  * holds the statistics of the groups [group_off[g], group_off[g + 1]) one after the other (NULL / 0: one group); ord
  * receives, group by group, the 0-based positions INSIDE the group in decreasing order of S, ties in index order (R's
