@@ -1,5 +1,6 @@
-"""Inputs and plain NumPy restatements shared by tests/test_knn_cpu.py and tests/test_gpu_knn.py (knn_parallel, prob_dist,
-LOF: bigsnpr_amd/csrc/knn_step.hpp is the statement, tests/native/knn_ref.py its CPU twin)."""
+"""Inputs, the sweep over the scan kernels and plain NumPy restatements shared by tests/test_knn_cpu.py,
+tests/test_gpu_knn.py and tests/test_gpu_knn_shapes.py (knn_parallel, prob_dist, LOF: bigsnpr_amd/csrc/knn_step.hpp is the
+statement, tests/native/knn_ref.py its CPU twin)."""
 import numpy as np
 
 PLANTED = 5     # isolated far points at the end of planted_outliers()
@@ -37,6 +38,69 @@ def planted_outliers(seed=5):
         far[t, t] = 60.0 * (1 if t % 2 == 0 else -1)
         far[t, PLANTED + t] = 45.0
     return np.concatenate([X, far])
+
+
+# ---- the sweep over the scan kernels ---------------------------------------------------------------------------------
+# knn.hip compiles one k_knn_scan<P, QL> per padded coordinate count P = 4, 8, .., 64 and queries per lane QL (2 only for
+# P <= 32), each with its own register budget and unroll factor U = (P * QL <= 32 ? 4 : 2).  The sweep reaches every one:
+#   p = P - 3 and P   three zero-padded coordinates and none
+#   k = 5 and 17      blocks of 256 queries (QL = 2 where P <= 32) and of 128 (QL = 1)
+#   n = 513           three blocks of 256, the last of ONE query (lane 0 holds a valid and an invalid query under QL = 2),
+#                     or five blocks of 128
+#   S = 1 and 3       one run of 16 tiles of 32 + 1 point, or slabs of 171 = 5 tiles + 11: both tails are odd, so the
+#                     `jj + u < cnt` guard is live for U = 4 and for U = 2
+SWEEP_P = tuple(range(4, 65, 4))
+SWEEP_K = (5, 17)
+SWEEP_N = 513
+SWEEP_S = (1, 3)
+SWEEP_QUERY_P = (8, 32, 36, 64)      # the P that the device tests also run in query mode
+
+
+def instantiation(p, k):
+    """(P, qb, QL) of a call with p coordinates and k neighbours: knn_plan.hpp's padded_p and query_block, knn.hip's
+    queries_per_lane.  tests/test_knn_cpu.py holds this restatement to the two sources."""
+    P = (p + 3) // 4 * 4
+    qb = 256 if k <= 16 else 128 if k <= 32 else 64
+    return P, qb, 2 if P <= 32 and qb == 256 else 1
+
+
+def sweep(P=None):
+    """the (p, k, S) of the sweep, all of them or those of one P"""
+    return [(p, k, S) for PP in (SWEEP_P if P is None else (P,)) for p in (PP - 3, PP) for k in SWEEP_K for S in SWEEP_S]
+
+
+def queries_with_copies(X, nq, seed, make):
+    """nq queries from make(nq, p, seed), the first, the middle and the last of them copied from the data: the row
+    numbers copied, and the queries"""
+    n = X.shape[0]
+    rows = [1, n // 2, n - 1]
+    Q = make(nq, X.shape[1], seed)
+    Q[[0, nq // 2, nq - 1]] = X[rows]
+    return rows, Q
+
+
+HUGE = 1e200      # finite, and the square of any difference with an ordinary coordinate overflows to +inf
+
+
+def with_huge(n, p, seed):
+    """a lattice of n points (p >= 3) in which every fifth row or so has +-HUGE in coordinate 0, 2 or both: rows of the
+    same pattern are at exact finite squared distances from each other, rows of different patterns at +inf (an overflow
+    of finite coordinates); a pattern has n / 25 members or so, fewer than a list has places.  The data, and a query
+    set whose last two rows hold patterns no data row has (every candidate at +inf: the index alone orders them)."""
+    rng = np.random.default_rng(seed)
+    X = lattice(n, p, 4, seed)
+    patterns = [(HUGE, None), (-HUGE, None), (None, HUGE), (HUGE, HUGE), (-HUGE, HUGE)]
+    rows = rng.permutation(n)[: n // 5]
+    for t, r in enumerate(rows):
+        a, b = patterns[t % 5]
+        if a is not None:
+            X[r, 0] = a
+        if b is not None:
+            X[r, 2] = b
+    Q = np.concatenate([lattice(9, p, 4, seed + 1), X[rows[:6]], lattice(2, p, 4, seed + 2)])
+    Q[-2, 2] = -HUGE                 # no data row has this pattern
+    Q[-1, 1] = HUGE
+    return X, Q
 
 
 # ---- NumPy restatements ----------------------------------------------------------------------------------------------

@@ -51,18 +51,33 @@ def _f(a):
     return np.asfortranarray(np.asarray(a, dtype=np.float64))
 
 
-def knn(data, query=None, k=1, rows=None):
+def padded_rows(a, ld):
+    """a as the top rows of a column-major matrix of ld rows, the rows below them NaN (ld=None: a itself, column-major)"""
+    a = _f(a)
+    if ld is None:
+        return a
+    assert ld >= a.shape[0]
+    out = np.full((ld, a.shape[1]), np.nan, order="F")
+    out[:a.shape[0]] = a
+    return out
+
+
+def knn(data, query=None, k=1, rows=None, ld=None, ldq=None):
     """nn_idx (int32, 0-based), nn_d2, nn_dists: nq x k.  query=None: self mode.  rows=(q0, q1): those queries only (the
-    other rows of the result are not filled)"""
+    other rows of the result are not filled).  ld / ldq: hand the matrices over as the top rows of larger ones (leading
+    dimensions above the row counts; the rows below hold NaN)"""
     data = _f(data)
     n, p = data.shape
     q = None if query is None else _f(query)
     nq = n if q is None else q.shape[0]
+    data = padded_rows(data, ld)
+    q = None if q is None else padded_rows(q, ldq)
     q0, q1 = (0, nq) if rows is None else rows
     idx = np.zeros((nq, k), dtype=np.int32, order="F")
     d2, dist = np.zeros((nq, k), order="F"), np.zeros((nq, k), order="F")
-    load().knn_table(data.ctypes.data_as(f64p), n, n, None if q is None else q.ctypes.data_as(f64p), nq, nq, p, k, q0, q1,
-                     idx.ctypes.data_as(i32p), d2.ctypes.data_as(f64p), dist.ctypes.data_as(f64p))
+    load().knn_table(data.ctypes.data_as(f64p), n, data.shape[0], None if q is None else q.ctypes.data_as(f64p), nq,
+                     nq if q is None else q.shape[0], p, k, q0, q1, idx.ctypes.data_as(i32p), d2.ctypes.data_as(f64p),
+                     dist.ctypes.data_as(f64p))
     return dict(nn_idx=idx, nn_d2=d2, nn_dists=dist)
 
 

@@ -1,7 +1,10 @@
 """knn_parallel / prob_dist / LOF without a device: the CPU statement (tests/native/knn_ref.cpp over
 bigsnpr_amd/csrc/knn_step.hpp — the header the kernels use) against plain NumPy, the planner of knn_plan.hpp, and the
-argument checks of the mirror.  tests/test_gpu_knn.py holds the device to this statement bit for bit."""
+argument checks of the mirror.  tests/test_gpu_knn.py holds the device to this statement bit for bit.  The sweep of
+tests/knn_cases.py over the scan kernels is held here to the `case` lines of knn.hip (every compiled k_knn_scan<P, QL> has
+a shape) and the statement to NumPy at every P of it; tests/test_gpu_knn_shapes.py runs that sweep on the device."""
 import os
+import re
 import sys
 
 import numpy as np
@@ -47,6 +50,118 @@ def test_grid_of_duplicates_ties_across_the_kth_place():
     # the k-th and the first left-out candidate are at the same distance for most queries: only the index decides
     full = np.sort(cases.np_d2(X) + np.diag(np.full(600, np.inf)), axis=1)
     assert (full[:, 30] == full[:, 31]).mean() > 0.5
+
+
+# ---- the sweep over the scan kernels (tests/knn_cases.py) ------------------------------------------------------------------
+def compiled_scans():
+    """the (P, QL) of the `case P: return k_knn_scan<P, QL>;` lines of scan_of() in knn.hip"""
+    with open(os.path.join(ROOT, "bigsnpr_amd", "csrc", "knn.hip")) as f:
+        src = f.read()
+    found = re.findall(r"case\s+(\d+)\s*:\s*return\s+k_knn_scan<\s*(\d+)\s*,\s*(\d+)\s*>\s*;", src)
+    assert found and all(a == b for a, b, _ in found), found
+    pairs = [(int(P), int(QL)) for _, P, QL in found]
+    assert len(set(pairs)) == len(pairs) == len(re.findall(r"return\s+k_knn_scan<", src)), pairs      # no line missed
+    return src, set(pairs)
+
+
+def test_sweep_reaches_every_compiled_scan_kernel():
+    src, compiled = compiled_scans()
+    reached = {}
+    for p, k, S in cases.sweep():
+        P, qb, QL = cases.instantiation(p, k)
+        reached.setdefault((P, QL), []).append((p, k, S))
+    assert set(reached) == compiled, (sorted(compiled - set(reached)), sorted(set(reached) - compiled))
+    assert len(compiled) == 24
+    for shapes in reached.values():                                  # each with and without padding, on both slab counts
+        assert {P - p for P, p in ((cases.instantiation(p, k)[0], p) for p, k, S in shapes)} == {0, 3}
+        assert {S for p, k, S in shapes} == set(cases.SWEEP_S)
+    # both sides of the unroll switch U = (P * QL <= 32 ? 4 : 2)
+    assert re.search(r"constexpr int U = P \* QL <= 32 \? 4 : 2;", src)
+    assert {(16, 2), (32, 1), (36, 1)} <= compiled
+
+
+def test_sweep_helper_restates_the_header_and_the_dispatch():
+    src, _ = compiled_scans()
+    # cases.instantiation's QL is knn.hip's rule as it stands today
+    assert re.search(r"int queries_per_lane\(int P, int qb\) \{ return P <= 32 && qb >= 256 \? 2 : 1; \}", src)
+    L = ref.load()
+    for p in range(1, 65):
+        for k in range(1, 65):
+            P, qb, QL = cases.instantiation(p, k)
+            assert P == L.knn_padded_p(p) and qb == ref.plan(1000, 1000, k)["qb"] and qb in (64, 128, 256)
+            assert QL == (2 if P <= 32 and qb >= 256 else 1)
+    # the geometry the sweep's sizes are chosen for
+    n = cases.SWEEP_N
+    assert [ref.plan(n, n, k)["nqb"] for k in cases.SWEEP_K] == [3, 5] and n - 2 * 256 == 1
+    assert list(np.diff(ref.plan(n, n, 5, forced=3)["lo"])) == [171, 171, 171] and 171 % 32 == 11 and n % 32 == 1
+
+
+@pytest.mark.parametrize("P", cases.SWEEP_P)
+def test_twin_equals_numpy_across_the_sweep(P):
+    n = cases.SWEEP_N
+    for p in (P - 3, P):
+        X = cases.lattice(n, p, 4, seed=p)
+        full = cases.np_d2(X)
+        for k in cases.SWEEP_K:
+            got = ref.knn(X, None, k)
+            idx, d2 = cases.np_knn(X, None, k, d2=full)
+            assert np.array_equal(got["nn_idx"], idx), (p, k)
+            assert np.array_equal(got["nn_d2"], d2), (p, k)
+            assert np.array_equal(got["nn_dists"], np.sqrt(d2)), (p, k)
+            if P in cases.SWEEP_QUERY_P:
+                qb = cases.instantiation(p, k)[1]
+                rows, Q = cases.queries_with_copies(X, 2 * qb + 1, p + 100, lambda m, pp, s: cases.lattice(m, pp, 4, s))
+                got = ref.knn(X, Q, k)
+                idx, d2 = cases.np_knn(X, Q, k)
+                assert np.array_equal(got["nn_idx"], idx), (p, k)
+                assert np.array_equal(got["nn_d2"], d2), (p, k)
+                assert (got["nn_d2"][[0, qb, 2 * qb], 0] == 0).all()
+
+
+# ---- +inf squared distances from finite coordinates ------------------------------------------------------------------------
+def check_huge_table(got, idx, d2, n, k):
+    """got (the statement's or the device's table) equals NumPy's (idx, d2) where some squared distances are +inf"""
+    assert np.array_equal(got["nn_idx"], idx)
+    assert np.array_equal(got["nn_dists"], np.sqrt(d2))
+    assert (got["nn_idx"] < n).all() and (got["nn_idx"] >= 0).all()       # a candidate at +inf comes before an unfilled place
+    inf = np.isinf(got["nn_dists"])
+    assert inf.any() and not np.isnan(got["nn_dists"]).any()
+    assert (inf[:, :-1] <= inf[:, 1:]).all()                               # the candidates at +inf come last ...
+    both = inf[:, :-1] & inf[:, 1:]
+    assert both.any() and (np.diff(got["nn_idx"].astype(np.int64), axis=1)[both] > 0).all()      # ... in order of index
+
+
+@pytest.mark.parametrize("k", [5, 64])
+def test_infinite_squared_distances_order_like_any_value(k):
+    n = 70
+    X, Q = cases.with_huge(n, 5, seed=3)
+    assert np.isfinite(X).all() and np.isfinite(Q).all()
+    with np.errstate(over="ignore"):
+        full, fullq = cases.np_d2(X), cases.np_d2(X, Q)
+    assert not np.isnan(full).any() and np.isinf(full).any() and np.isinf(fullq[-2:]).all()
+    got = ref.knn(X, None, k)
+    idx, d2 = cases.np_knn(X, None, k, d2=full)
+    assert np.array_equal(got["nn_d2"], d2)
+    check_huge_table(got, idx, d2, n, k)
+    for kq in (k, n):                                    # k = n: every data point is listed, those at +inf included
+        got = ref.knn(X, Q, kq)
+        idx, d2 = cases.np_knn(X, Q, kq, d2=fullq)
+        assert np.array_equal(got["nn_d2"], d2)
+        check_huge_table(got, idx, d2, n, kq)
+        assert np.array_equal(got["nn_idx"][-2:], np.tile(np.arange(kq, dtype=np.int32), (2, 1)))     # all at +inf: by index
+    assert (np.sort(got["nn_idx"], axis=1) == np.arange(n)).all()
+
+
+# ---- leading dimensions above the row counts -------------------------------------------------------------------------------
+@pytest.mark.parametrize("p", [10, 33])
+def test_leading_dimension_above_the_row_count(p):
+    X, Q = cases.scores(150, p, 5), cases.scores(41, p, 6)
+    for q, k in ((None, 7), (Q, 7), (Q, 150)):
+        want = ref.knn(X, q, k)
+        got = ref.knn(X, q, k, ld=150 + 7, ldq=None if q is None else 41 + 3)     # the rows below hold NaN
+        for name in ("nn_idx", "nn_d2", "nn_dists"):
+            assert np.array_equal(got[name], want[name]), name
+        assert np.isfinite(got["nn_d2"]).all()
 
 
 # ---- random doubles -----------------------------------------------------------------------------------------------------
