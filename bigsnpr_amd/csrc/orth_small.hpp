@@ -19,7 +19,7 @@
 // that lost more than six digits in the projection, or whose pass-1 Gram matrix is not close to the
 // identity, raises `flag` and the driver redoes the step on the careful path.
 //
-// The same code runs on the device (svd.hip: Ctx = one workgroup, sync = __syncthreads) and on the
+// The same code runs on the device (svd_panel.hip: Ctx = one workgroup, sync = __syncthreads) and on the
 // host (tests/native: Ctx = one thread), so the CPU tests exercise the arithmetic the GPU runs.
 #pragma once
 #include <cmath>

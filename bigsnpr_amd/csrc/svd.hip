@@ -1,8 +1,8 @@
 // svd.hip — HIP backend of the block-Lanczos partial SVD (svd_driver.hpp) and the
 // bsn_bed_randomsvd entry point (replaces bed_randomSVD -> bigstatsr::big_randomSVD,
 // R/autoSVD.R:205-219).  The two matrix passes per step are op_cprod / op_prod
-// (matvec.hip); the tall-skinny fp64 panel algebra below is memory-bound on the basis Q
-// (n x p doubles) and is a few percent of a step.
+// (matvec.hip); the tall-skinny fp64 panel algebra between them is svd_panel.hip, and what a
+// call solves with (block, digits, schedule, second copy) is decided in svd_plan.hpp.
 #include <chrono>
 #include <unistd.h>
 #include <atomic>
@@ -17,496 +17,10 @@
 #include "bsn_internal.hpp"
 #include "orth_small.hpp"
 #include "svd_driver.hpp"
+#include "svd_panel.hpp"
+#include "svd_plan.hpp"
 
 namespace bsn {
-
-constexpr int kMaxB = 16;
-constexpr int kTP = 256;  // basis columns per LDS tile of k_gemm_nn
-
-__device__ __forceinline__ uint32_t hmix(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
-
-// rows [row0, row0 + n) of the n_total x b start block (a function of the global row index, so that
-// sample blocks of different ranks are pieces of the same matrix); rows past n_total are zero
-__global__ void k_random(double *W, int64_t ld, int64_t n, int b, uint32_t seed, int64_t row0, int64_t n_total) {
-  int64_t il = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  int j = blockIdx.y;
-  if (il >= n || j >= b) return;
-  const int64_t i = il + row0;
-  if (i >= n_total) {
-    W[il + j * ld] = 0.0;
-    return;
-  }
-  uint32_t h = hmix((uint32_t)i * 0x9E3779B1U + hmix(seed * 0x85EBCA6BU + (uint32_t)j + 0x1234567U));
-  uint32_t h2 = hmix(h ^ 0xDEADBEEFU);
-  // uniform in (-1, 1) with 53 random bits
-  double x = ((double)(((uint64_t)h << 21) ^ (uint64_t)h2) + 0.5) * (1.0 / 9007199254740992.0);
-  W[il + j * ld] = 2.0 * x - 1.0;
-}
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-struct __attribute__((aligned(8))) d2 {
-  double x, y;
-};
-constexpr int64_t kGemmRows = 1024;   // rows per workgroup of k_gemm_tn (4 waves x 256)
-
-// C (p x cb, leading dimension ldc) = A[:, :p]' B[:, :cb]: the tall-skinny TN product of the panel algebra
-// on the fp64 matrix pipe.  v_mfma_f64_16x16x4 with the 16 columns of an A tile as M, the (<= 16) columns
-// of B as N and four rows as K: lane l supplies A[row, tile*16 + (l & 15)] and B[row, l & 15] for row slot
-// l >> 4; which row a slot stands for is free as long as A and B agree, so a lane takes TWO consecutive
-// rows per 16-byte load (rows r + 2 (l >> 4) + {0, 1} of an 8-row group, two MFMAs): every load
-// instruction then reads 64 contiguous bytes per column, straight from global memory — A is read exactly
-// once, B once per 16 columns of A (round 2's VALU kernel re-read B once per FOUR columns of A and was
-// the largest item of a solve outside the streaming passes).
-// Workgroup (tile, rc) covers rows [rc, rc + 1) * kGemmRows with four waves and writes the 16 x 16 sums to
-// partial[rc][tile]; k_gemm_tn_reduce adds the chunks up.
-// NT: 16-column tiles of B (cb <= 16 NT); an A tile is loaded once for all of them.
-template <int NT>
-__global__ __launch_bounds__(256) void k_gemm_tn(const double *__restrict__ A, int64_t lda, int p,
-                                                 const double *__restrict__ B, int64_t ldb, int cb, int64_t n,
-                                                 double *partial) {
-  const int tile = blockIdx.x, rc = blockIdx.y, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int a = lane & 15, kq = lane >> 4;
-  // columns past p (past cb) are read from a valid one and discarded (masked): no branch around the loads
-  const int ca = tile * 16 + a < p ? tile * 16 + a : p - 1;
-  const double *Ap = A + (int64_t)ca * lda;
-  bool bval[NT];
-  const double *Bp[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    bval[t] = t * 16 + a < cb;
-    Bp[t] = B + (int64_t)(bval[t] ? t * 16 + a : 0) * ldb;
-  }
-  const int64_t c0 = (int64_t)rc * kGemmRows, c1 = c0 + kGemmRows < n ? c0 + kGemmRows : n;
-  const int64_t r0 = c0 + wave * (kGemmRows / 4);
-  const int64_t r1 = r0 + kGemmRows / 4 < c1 ? r0 + kGemmRows / 4 : c1;
-  v4d acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) acc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-  // groups of 32 rows through two register sets: the loads of a group are in flight while the MFMAs of the
-  // previous one run (a wave that waited out every group's memory round trip left the kernel latency-bound
-  // at a quarter of the bandwidth).  No branch around the loads: past the end the last group is loaded again.
-  d2 av0[4], bv0[NT][4], av1[4], bv1[NT][4];
-  auto ld = [&](int64_t rr, d2 (&av)[4], d2 (&bv)[NT][4]) {
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      av[u] = *(const d2 *)(Ap + rr + 8 * u + 2 * kq);
-#pragma unroll
-      for (int t = 0; t < NT; t++) bv[t][u] = *(const d2 *)(Bp[t] + rr + 8 * u + 2 * kq);
-    }
-  };
-  auto mm = [&](const d2 (&av)[4], const d2 (&bv)[NT][4]) {
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u].x, bval[t] ? bv[t][u].x : 0.0, acc[t], 0, 0, 0);
-        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u].y, bval[t] ? bv[t][u].y : 0.0, acc[t], 0, 0, 0);
-      }
-  };
-  const int64_t nfull = r1 > r0 ? (r1 - r0) / 32 : 0;
-  if (nfull > 0) {
-    ld(r0, av0, bv0);
-    for (int64_t g = 0; g < nfull; g += 2) {
-      ld(r0 + 32 * (g + 1 < nfull ? g + 1 : nfull - 1), av1, bv1);
-      mm(av0, bv0);
-      ld(r0 + 32 * (g + 2 < nfull ? g + 2 : nfull - 1), av0, bv0);
-      if (g + 1 < nfull) mm(av1, bv1);
-    }
-  }
-  int64_t r = r0 + 32 * nfull;
-  for (; r < r1; r += 8) {   // the ragged end of the last chunk
-    const int64_t i0 = r + 2 * kq, i1 = i0 + 1;
-    const double a0 = i0 < r1 ? Ap[i0] : 0.0, a1 = i1 < r1 ? Ap[i1] : 0.0;
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      const double b0 = (bval[t] && i0 < r1) ? Bp[t][i0] : 0.0, b1 = (bval[t] && i1 < r1) ? Bp[t][i1] : 0.0;
-      acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[t], 0, 0, 0);
-    }
-  }
-  // D: column of B = lane & 15, column of the A tile = (lane >> 4) + 4 * reg
-  __shared__ double red[4][256];
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    if (t > 0) __syncthreads();
-#pragma unroll
-    for (int g = 0; g < 4; g++) red[wave][(kq + 4 * g) * 16 + a] = acc[t][g];
-    __syncthreads();
-    partial[(((int64_t)rc * gridDim.x + tile) * NT + t) * 256 + tid] =
-        (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-  }
-}
-
-// C[tile*16 + mrow, ncol] = sum over the row chunks, in a fixed order (four interleaved running sums, then
-// their sum): identical on every rank and in every run.  (A single launch with a "last workgroup adds up"
-// tail was tried in round 3: the device-scope fences it needs write back the L2 of every XCD, 0.15 us per
-// workgroup, several times the product itself.)
-__global__ __launch_bounds__(1024) void k_gemm_tn_reduce(const double *__restrict__ partial, int nrc, int ntile, int p,
-                                                         int cb, double *C, int ldc) {
-  const int tile = blockIdx.x, bt = blockIdx.y, nt = gridDim.y, t = threadIdx.x & 255, part = threadIdx.x >> 8;
-  double sum = 0;
-#pragma unroll 4
-  for (int c = part; c < nrc; c += 4) sum += partial[(((int64_t)c * ntile + tile) * nt + bt) * 256 + t];
-  __shared__ double sp[4][256];
-  sp[part][t] = sum;
-  __syncthreads();
-  if (part == 0) {
-    sum = (sp[0][t] + sp[1][t]) + (sp[2][t] + sp[3][t]);
-    const int mrow = t >> 4, ncol = bt * 16 + (t & 15);
-    if (tile * 16 + mrow < p && ncol < cb) C[(tile * 16 + mrow) + (int64_t)ncol * ldc] = sum;
-  }
-}
-
-// Out[i, j] = alpha * In[i, j] + beta * sum_a Q[i, a] S[a, j],  j < nc <= 8; S (p x nc) in global
-__global__ __launch_bounds__(256) void k_gemm_nn(const double *__restrict__ Q, int64_t ldq, int p,
-                                                 const double *__restrict__ S, int nc,
-                                                 const double *In, int64_t ldi, double alpha,
-                                                 double beta, double *Out, int64_t ldo, int64_t n) {
-  extern __shared__ __attribute__((aligned(16))) double sS[];  // tile of S: TP x kMaxB
-  constexpr int TP = kTP;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  double acc[kMaxB];
-#pragma unroll
-  for (int j = 0; j < kMaxB; j++) acc[j] = 0;
-  for (int a0 = 0; a0 < p; a0 += TP) {
-    int ta = p - a0 < TP ? p - a0 : TP;
-    __syncthreads();
-    for (int t = threadIdx.x; t < ta * kMaxB; t += blockDim.x) {
-      int a = t / kMaxB, j = t % kMaxB;
-      sS[t] = j < nc ? S[(a0 + a) + (int64_t)j * p] : 0.0;
-    }
-    __syncthreads();
-    if (i < n) {
-      for (int a = 0; a < ta; a++) {
-        double q = Q[i + (int64_t)(a0 + a) * ldq];
-#pragma unroll
-        for (int j = 0; j < kMaxB; j++) acc[j] += q * sS[a * kMaxB + j];
-      }
-    }
-  }
-  if (i < n) {
-#pragma unroll
-    for (int j = 0; j < kMaxB; j++)
-      if (j < nc) {
-        double base = alpha != 0.0 ? alpha * In[i + (int64_t)j * ldi] : 0.0;
-        Out[i + (int64_t)j * ldo] = base + beta * acc[j];
-      }
-  }
-}
-
-__global__ void k_put_block(double *M, int ld, int r, const double *src) {   // M[:r, :r] (leading dimension ld) = src (r x r)
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < r * r) M[(t % r) + (int64_t)(t / r) * ld] = src[t];
-}
-
-// in place W[:, :r] = W[:, :cb] * M (cb x r), one thread per row
-__global__ void k_right_mult(double *W, int64_t ld, int64_t n, int cb, int r, const double *M) {
-  __shared__ double sM[kMaxB * kMaxB];
-  if ((int)threadIdx.x < cb * r) sM[threadIdx.x] = M[threadIdx.x];
-  __syncthreads();
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  double w[kMaxB], o[kMaxB];
-#pragma unroll
-  for (int j = 0; j < kMaxB; j++) w[j] = j < cb ? W[i + j * ld] : 0.0;
-#pragma unroll
-  for (int c = 0; c < kMaxB; c++) {
-    double s = 0;
-#pragma unroll
-    for (int j = 0; j < kMaxB; j++)
-      if (j < cb && c < r) s += w[j] * sM[j + c * cb];
-    o[c] = s;
-  }
-#pragma unroll
-  for (int c = 0; c < kMaxB; c++)
-    if (c < r) W[i + c * ld] = o[c];
-}
-
-// The small-matrix half of one pass of the two-pass orthonormalisation (orth_small.hpp) on one
-// workgroup; the coefficient iterate lives in LDS.  mx_clear: the column maxima that the following
-// k_update accumulates (rounding of the finished block) start from zero.
-struct DevCtx {
-  int tid, nt;
-  __device__ void sync() { __syncthreads(); }
-};
-__global__ __launch_bounds__(512) void k_orth2(OrthSmall a, unsigned long long *mx_clear) {
-  __shared__ double sCs[kOrthMaxP * kOrthMaxB];
-  __shared__ double sG[kOrthMaxB * kOrthMaxB], sR[kOrthMaxB * kOrthMaxB], sRi[kOrthMaxB * kOrthMaxB],
-      sRo[kOrthMaxB * kOrthMaxB], sD[kOrthMaxB * kOrthMaxB], sT[2 * kOrthMaxB + 4];
-  a.Cs = sCs;
-  a.Gs = sG;
-  a.Rs = sR;
-  a.Ris = sRi;
-  a.Ro = sRo;
-  a.Dv = sD;
-  a.tmp = sT;
-  if (mx_clear && threadIdx.x < kOrthMaxB) mx_clear[threadIdx.x] = 0ull;
-  DevCtx cx{(int)threadIdx.x, (int)blockDim.x};
-  orth_small(cx, a);
-}
-
-// W[i, :cb] <- (W[i, :cb] - Q[i, :p] C) Ri   in place, one thread per row (the tall half of a pass);
-// mx != null: also the column maxima of the result (bits of a non-negative double order like u64)
-template <int CBT>
-__global__ __launch_bounds__(256) void k_update(const double *__restrict__ Q, int64_t ldq, int p,
-                                                const double *__restrict__ C, const double *__restrict__ Ri,
-                                                int cb, double *W, int64_t ldw, int64_t n,
-                                                unsigned long long *mx) {
-  constexpr int TP = 128, ROWS = 4;   // a workgroup covers 1024 rows: few atomics on the column maxima
-  __shared__ double sS[TP * CBT], sRi[CBT * CBT], smx[4][CBT];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int t = tid; t < CBT * CBT; t += 256) {
-    const int j = t % CBT, c = t / CBT;
-    sRi[t] = (j < cb && c < cb) ? Ri[j + c * cb] : 0.0;
-  }
-  if (tid < 4 * CBT) smx[tid / CBT][tid % CBT] = 0.0;
-  const bool one_tile = p <= TP;
-  for (int it = 0; it < ROWS; it++) {
-    const int64_t i = ((int64_t)blockIdx.x * ROWS + it) * 256 + tid;
-    double acc[CBT];
-#pragma unroll
-    for (int j = 0; j < CBT; j++) acc[j] = 0;
-    for (int a0 = 0; a0 < p; a0 += TP) {
-      const int ta = p - a0 < TP ? p - a0 : TP;
-      if (!(one_tile && it > 0)) {   // (uniform) the coefficient tile stays in LDS when it is the only one
-        __syncthreads();
-        for (int t = tid; t < ta * CBT; t += 256) {
-          const int a = t / CBT, j = t % CBT;
-          sS[t] = j < cb ? C[(a0 + a) + (int64_t)j * p] : 0.0;
-        }
-        __syncthreads();
-      }
-      if (i < n) {
-        // (unrolled by 8: the eight loads of Q go out together instead of one memory round trip per column)
-#pragma unroll 8
-        for (int a = 0; a < ta; a++) {
-          const double q = Q[i + (int64_t)(a0 + a) * ldq];
-#pragma unroll
-          for (int j = 0; j < CBT; j++) acc[j] += q * sS[a * CBT + j];
-        }
-      }
-    }
-    if (p == 0 && it == 0) __syncthreads();   // sRi / smx are ready
-    double w[CBT];
-#pragma unroll
-    for (int j = 0; j < CBT; j++) w[j] = (i < n && j < cb) ? W[i + j * ldw] - acc[j] : 0.0;
-    // one output column at a time (the loop is kept rolled: 16 x 16 products unrolled need 300 registers)
-#pragma unroll 1
-    for (int c = 0; c < cb; c++) {
-      double s = 0;
-#pragma unroll
-      for (int j = 0; j < CBT; j++) s += w[j] * sRi[j + c * CBT];
-      if (i < n) W[i + c * ldw] = s;
-      if (mx) {
-        double m = fabs(s);
-        for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off));
-        if (lane == 0) smx[wave][c] = fmax(smx[wave][c], m);
-      }
-    }
-  }
-  if (mx) {
-    __syncthreads();
-    if (tid < cb) {
-      const double m = fmax(fmax(smx[0][tid], smx[1][tid]), fmax(smx[2][tid], smx[3][tid]));
-      atomicMax(&mx[tid], (unsigned long long)__double_as_longlong(m));
-    }
-  }
-}
-
-// ---- rounding of a finished basis block to the fixed-point grid of the streaming products ----
-// (svd_driver.hpp: the products are then exact for the stored vectors).  The scale is the largest
-// power of two with absmax * qs <= 0.98 * 2^(8S-1): one notch below the 0.99 the product's own
-// quantiser uses, so that re-quantising the rounded vector can only pick the same or a finer grid.
-__global__ void k_col_absmax(const double *W, int64_t ld, int64_t n, unsigned long long *mx) {
-  const int v = blockIdx.y;
-  double m = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    m = fmax(m, fabs(W[i + v * ld]));
-  for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off));
-  __shared__ double sm[16];
-  const int wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) sm[wave] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < nw; w++) m = fmax(m, sm[w]);
-    atomicMax(&mx[v], (unsigned long long)__double_as_longlong(m));
-  }
-}
-__global__ void k_round_cols(double *W, int64_t ld, int64_t n, const unsigned long long *mx, int slices) {
-  const int v = blockIdx.y;
-  const double m = __longlong_as_double((long long)mx[v]);
-  if (!(m > 0)) return;
-  int e;
-  frexp(ldexp(0.98, 8 * slices - 1) / m, &e);
-  const double qs = ldexp(1.0, e - 1), iq = ldexp(1.0, 1 - e);
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) W[i + v * ld] = (double)llrint(W[i + v * ld] * qs) * iq;
-}
-
-// ---- sample-block layout of a panel for the collectives ------------------------------------
-// full: n x cb column-major (ld n).  blk: [rank][column][row of the rank's block], blocks of nr
-// rows (the last one zero-padded) — the chunk of rank r is contiguous, which is what
-// reduce-scatter / all-gather exchange.
-__global__ void k_block(const double *__restrict__ full, int64_t n, int cb, int64_t nr, int world,
-                        double *__restrict__ blk) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)world * cb * nr) return;
-  const int64_t i = t % nr, j = (t / nr) % cb, r = t / (nr * cb);
-  const int64_t gi = r * nr + i;
-  blk[t] = gi < n ? full[gi + j * n] : 0.0;
-}
-__global__ void k_unblock(const double *__restrict__ blk, int64_t n, int cb, int64_t nr,
-                          double *__restrict__ full) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * cb) return;
-  const int64_t gi = t % n, j = t / n;
-  full[t] = blk[((gi / nr) * cb + j) * nr + gi % nr];
-}
-// ---- the all-gather of a finished basis block as the 16-bit integers it is rounded to (sharded solve, round 4) ----
-// mx[v] = max over the ranks of their column maxima (bit patterns of non-negative doubles order like integers)
-__global__ void k_max_over_ranks(const unsigned long long *__restrict__ all, int world, int cb,
-                                 unsigned long long *__restrict__ mx) {
-  const int v = threadIdx.x;
-  if (v >= cb) return;
-  unsigned long long m = 0;
-  for (int r = 0; r < world; r++) m = all[r * cb + v] > m ? all[r * cb + v] : m;
-  mx[v] = m;
-}
-// the rounding of k_round_cols on this rank's rows: the integers go to q (column-major, nr rows), the rounded values
-// back into W
-template <typename INT>   // int16_t up to 16 bits, int32_t up to 32
-__global__ void k_pack_int(double *__restrict__ W, int64_t nr, const unsigned long long *__restrict__ mx, int slices,
-                           INT *__restrict__ q) {
-  const int v = blockIdx.y;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nr) return;
-  const double m = __longlong_as_double((long long)mx[v]);
-  if (!(m > 0)) {
-    q[i + v * nr] = 0;
-    return;   // (an all-zero column stays as it is, like in k_round_cols)
-  }
-  int e;
-  frexp(ldexp(0.98, 8 * slices - 1) / m, &e);
-  const double qs = ldexp(1.0, e - 1), iq = ldexp(1.0, 1 - e);
-  const long long k = llrint(W[i + v * nr] * qs);
-  q[i + v * nr] = (INT)k;
-  W[i + v * nr] = (double)k * iq;
-}
-// all ranks' integers ([rank][column][row of the block]) -> the rounded block with all n rows (column-major, ld n)
-template <typename INT>
-__global__ void k_unpack_int(const INT *__restrict__ q, int64_t n, int cb, int64_t nr,
-                             const unsigned long long *__restrict__ mx, int slices, double *__restrict__ full) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= n * cb) return;
-  const int64_t gi = t % n, v = t / n;
-  const double m = __longlong_as_double((long long)mx[v]);
-  double val = 0.0;
-  if (m > 0) {
-    int e;
-    frexp(ldexp(0.98, 8 * slices - 1) / m, &e);
-    val = (double)q[((gi / nr) * cb + v) * nr + gi % nr] * ldexp(1.0, 1 - e);
-  }
-  full[t] = val;
-}
-
-// a received segment (rows x cb, ld rows) into rows [r0, r0 + rows) of the panel W (ld nr)
-__global__ void k_place_rows(const double *__restrict__ src, int64_t rows, int cb, int64_t r0, int64_t nr,
-                             double *__restrict__ W) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= rows * cb) return;
-  W[r0 + t % rows + (t / rows) * nr] = src[t];
-}
-// W (nr x cb, ld nr) = rows [row0, row0 + nr) of full (n x cb, ld n), zero past n
-__global__ void k_take_rows(const double *__restrict__ full, int64_t n, int cb, int64_t nr, int64_t row0,
-                            double *__restrict__ W) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= nr * cb) return;
-  const int64_t i = t % nr, j = t / nr;
-  W[t] = row0 + i < n ? full[row0 + i + j * n] : 0.0;
-}
-
-// ---- the launches of the panel kernels ------------------------------------------------------------------------
-// One free function per launch: grid, block, template choice and LDS size live here and nowhere else, so that the
-// backend below and the kernel-level test entries at the end of this file (bsn_panel_*) run the same launches.
-// doubles of `partial` that panel_gemm_tn writes for operands of `rows` rows and p columns of A
-inline size_t panel_partial_count(int64_t rows, int p) {
-  return (size_t)((rows + kGemmRows - 1) / kGemmRows) * (size_t)((p + 15) / 16) * 2 * 256;
-}
-// dC (p x cb, leading dimension ldc) = A[:, :p]' B[:, :cb] for operands with `rows` rows; cb <= 32
-void panel_gemm_tn(hipStream_t st, const double *A, int64_t lda, int p, const double *B, int64_t ldb, int cb, int64_t rows,
-                   double *dC, int ldc, double *partial) {
-  if (p <= 0 || cb <= 0) return;
-  dim3 grid((unsigned)((p + 15) / 16), (unsigned)((rows + kGemmRows - 1) / kGemmRows));
-  const int nt = (cb + 15) / 16;
-  if (nt == 1)
-    hipLaunchKernelGGL((k_gemm_tn<1>), grid, dim3(256), 0, st, A, lda, p, B, ldb, cb, rows, partial);
-  else if (nt == 2)
-    hipLaunchKernelGGL((k_gemm_tn<2>), grid, dim3(256), 0, st, A, lda, p, B, ldb, cb, rows, partial);
-  else
-    fail("internal: panel product with %d columns", cb);
-  hipLaunchKernelGGL(k_gemm_tn_reduce, dim3(grid.x, nt), dim3(1024), 0, st, partial, (int)grid.y, (int)grid.x, p, cb, dC, ldc);
-}
-void panel_gemm_nn(hipStream_t st, const double *Q, int64_t ldq, int p, const double *S, int nc, const double *In, int64_t ldi,
-                   double alpha, double beta, double *Out, int64_t ldo, int64_t n) {
-  hipLaunchKernelGGL(k_gemm_nn, dim3((unsigned)((n + 255) / 256)), dim3(256), kTP * kMaxB * 8, st, Q, ldq, p, S, nc, In, ldi,
-                     alpha, beta, Out, ldo, n);
-}
-void panel_right_mult(hipStream_t st, double *W, int64_t ld, int64_t n, int cb, int r, const double *M) {
-  hipLaunchKernelGGL(k_right_mult, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W, ld, n, cb, r, M);
-}
-void panel_update(hipStream_t st, const double *Q, int64_t ldq, int p, const double *C, const double *Ri, int cb, double *W,
-                  int64_t ldw, int64_t n, unsigned long long *mx) {
-  const dim3 rows((unsigned)((n + 1023) / 1024));
-  if (cb <= 8)
-    hipLaunchKernelGGL((k_update<8>), rows, dim3(256), 0, st, Q, ldq, p, C, Ri, cb, W, ldw, n, mx);
-  else
-    hipLaunchKernelGGL((k_update<16>), rows, dim3(256), 0, st, Q, ldq, p, C, Ri, cb, W, ldw, n, mx);
-}
-void panel_orth2(hipStream_t st, const OrthSmall &a, unsigned long long *mx_clear) {
-  hipLaunchKernelGGL(k_orth2, dim3(1), dim3(512), 0, st, a, mx_clear);
-}
-// wide: 256 workgroups per column (a whole panel on one GPU), else 64 (a rank's sample block)
-void panel_col_absmax(hipStream_t st, const double *X, int64_t ld, int64_t n, int cb, unsigned long long *mx, bool wide) {
-  hipLaunchKernelGGL(k_col_absmax, dim3(wide ? 256 : 64, cb), dim3(1024), 0, st, X, ld, n, mx);
-}
-void panel_round_cols(hipStream_t st, double *X, int64_t ld, int64_t n, int cb, const unsigned long long *mx, int slices) {
-  hipLaunchKernelGGL(k_round_cols, dim3((unsigned)((n + 255) / 256), cb), dim3(256), 0, st, X, ld, n, mx, slices);
-}
-void panel_block(hipStream_t st, const double *full, int64_t n, int cb, int64_t nr, int world, double *blk) {
-  const int64_t tot = (int64_t)world * cb * nr;
-  hipLaunchKernelGGL(k_block, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, full, n, cb, nr, world, blk);
-}
-void panel_unblock(hipStream_t st, const double *blk, int64_t n, int cb, int64_t nr, double *full) {
-  hipLaunchKernelGGL(k_unblock, dim3((unsigned)((n * cb + 255) / 256)), dim3(256), 0, st, blk, n, cb, nr, full);
-}
-void panel_place_rows(hipStream_t st, const double *src, int64_t rows, int cb, int64_t r0, int64_t nr, double *W) {
-  hipLaunchKernelGGL(k_place_rows, dim3((unsigned)((rows * cb + 255) / 256)), dim3(256), 0, st, src, rows, cb, r0, nr, W);
-}
-void panel_take_rows(hipStream_t st, const double *full, int64_t n, int cb, int64_t nr, int64_t row0, double *W) {
-  hipLaunchKernelGGL(k_take_rows, dim3((unsigned)((nr * cb + 255) / 256)), dim3(256), 0, st, full, n, cb, nr, row0, W);
-}
-void panel_max_over_ranks(hipStream_t st, const unsigned long long *all, int world, int cb, unsigned long long *mx) {
-  hipLaunchKernelGGL(k_max_over_ranks, dim3(1), dim3(64), 0, st, all, world, cb, mx);
-}
-// int16 up to 16 bits (slices <= 2), int32 up to 32: q is the rank's [column][row] block of integers
-void panel_pack_int(hipStream_t st, double *W, int64_t nr, int cb, const unsigned long long *mx, int slices, void *q) {
-  const dim3 gp((unsigned)((nr + 255) / 256), cb);
-  if (slices <= 2)
-    hipLaunchKernelGGL((k_pack_int<int16_t>), gp, dim3(256), 0, st, W, nr, mx, slices, (int16_t *)q);
-  else
-    hipLaunchKernelGGL((k_pack_int<int32_t>), gp, dim3(256), 0, st, W, nr, mx, slices, (int32_t *)q);
-}
-void panel_unpack_int(hipStream_t st, const void *q_all, int64_t n, int cb, int64_t nr, const unsigned long long *mx, int slices,
-                      double *full) {
-  const dim3 gu((unsigned)((n * cb + 255) / 256));
-  if (slices <= 2)
-    hipLaunchKernelGGL((k_unpack_int<int16_t>), gu, dim3(256), 0, st, (const int16_t *)q_all, n, cb, nr, mx, slices, full);
-  else
-    hipLaunchKernelGGL((k_unpack_int<int32_t>), gu, dim3(256), 0, st, (const int32_t *)q_all, n, cb, nr, mx, slices, full);
-}
 
 // Panels of length n (samples) are held by SAMPLE BLOCKS when the solve is distributed: rank r owns
 // rows [r nr, (r+1) nr) of the basis Q and of the working panel W, orthogonalises them locally and
@@ -761,8 +275,7 @@ struct HipSvdBackend : SvdBackend {
     guess_live = false;
     grams_early = false;
     op->preq_X = nullptr;
-    hipLaunchKernelGGL(k_random, dim3((unsigned)((nr + 255) / 256), bb), dim3(256), 0, st, Wc, nr, nr, bb, seed,
-                       row0, n);
+    panel_random(st, Wc, nr, nr, bb, seed, row0, n);
     BSN_HIP(hipGetLastError());
   }
   // the newest basis block with all n rows: Q itself on one GPU, the gathered copy otherwise
@@ -1341,8 +854,7 @@ struct HipSvdBackend : SvdBackend {
     // the device copy of Q'Q on the kept part: S'(Q'Q)S as the driver computed it (the identity up to rounding
     // unless the old basis was ill conditioned)
     copy_h2d(op->bed, dS.p, Mk, (size_t)keep * keep * 8);
-    hipLaunchKernelGGL(k_put_block, dim3((unsigned)((keep * keep + 255) / 256)), dim3(256), 0, st, ws.dM.p,
-                       kOrthMaxP, keep, dS.p);
+    panel_put_block(st, ws.dM.p, kOrthMaxP, keep, dS.p);
     BSN_HIP(hipGetLastError());
     return true;
   }
@@ -1624,6 +1136,409 @@ static bsn_bed *compacted_view(bsn_bed *bed, const int64_t *ind_row, int64_t n, 
   return fresh;
 }
 
+// ---- bsn_bed_randomsvd, step by step ------------------------------------------------------------------------------------
+namespace {
+
+// what one call carries from step to step
+struct SolveCall {
+  const bsn_svd_options *o;
+  // what the solve runs on: the caller's handle and lists, or (compacted) the copy of the selection, without lists
+  bsn_bed *bed;
+  const int64_t *ind_row, *ind_col;
+  int64_t n, m;
+  // the handle's device-resident code counts (bsn_bed::stats_cache) serve, and are fed by, a solve over all samples of
+  // a resident 2-bit image; on the compacted copy too, through the caller's handle and the caller's variant list
+  bsn_bed *owner = nullptr;
+  const int64_t *owner_cols = nullptr;
+  bool ooc = false;               // (round 5) an out-of-core handle: the passes of the solve walk the file in slabs
+  bool all_rows = false;          // all samples in file order
+  bool compacted = false;
+  bool fused = false;             // bed_scaleBinom evaluated on the device ...
+  bool served = false;            // ... from the counts on the handle, before the first launch
+  bool use_stats_cache = false;
+  StatsCols sel{nullptr, nullptr, 0, 0};
+  int32_t n_bad = 0;
+  std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  double t_compact = 0.0, t_create = 0.0;
+  float gpu_ms = 0;
+  double since() const {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+  }
+};
+
+// an out-of-core handle (HipSvdBackend, "out-of-core handle") covers all samples, and its variants in file order
+void check_selection(SolveCall &c) {
+  c.all_rows = c.n == c.bed->n;
+  for (int64_t i = 0; c.all_rows && c.ind_row && i < c.n; i++) c.all_rows = c.ind_row[i] == i;
+  if (!c.ooc) return;
+  if (c.o->comm || c.o->allreduce) fail("an out-of-core handle cannot be one shard of a sharded solve: shard the file instead");
+  const int64_t *ind_col = c.ind_col;
+  bool all_cols = c.m == c.bed->m, in_order = true;
+  for (int64_t j = 0; ind_col && j < c.m; j++) {
+    if (ind_col[j] != j) all_cols = false;
+    if (ind_col[j] < 0 || ind_col[j] >= c.bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)ind_col[j], (long long)c.bed->m);
+    if (j > 0 && ind_col[j] <= ind_col[j - 1]) in_order = false;
+  }
+  // (round 6) a LIST of variants in file order is served too — what bed_autoSVD solves over (ind.keep, sorted)
+  if (!c.all_rows || !in_order)
+    fail("bed_randomSVD on an out-of-core handle (the file's image does not fit the device: it streams its file) "
+         "covers all samples, and its variants in increasing file order; a subset small enough for the device is served "
+         "by a handle of its own (snp_subset / bsn_bed_subset_payload)");
+  c.ind_row = nullptr;
+  if (all_cols) c.ind_col = nullptr;
+}
+
+// (round 5) a list of variants that is not a contiguous range: the solve runs on a compacted copy of the selection
+void enter_compacted_view(SolveCall &c) {
+  c.bed->last_solve_on_sub = false;
+  c.owner = c.bed;
+  c.owner_cols = c.ind_col;
+  c.use_stats_cache = c.o->binom_scaling && !c.ooc && c.all_rows && stats_cache_enabled(c.owner);
+  if (bsn_bed *sub = compacted_view(c.bed, c.ind_row, c.n, c.ind_col, c.m)) {
+    c.bed->last_solve_on_sub = true;
+    if (c.ind_row == nullptr && c.n != c.bed->n) fail("internal: row count of a compacted solve");
+    c.bed = sub;
+    c.ind_row = nullptr;
+    c.ind_col = nullptr;
+    c.compacted = true;
+    c.t_compact = c.since();
+  }
+}
+
+// operator and workspace of the previous solve on this handle are reused (grow-only buffers)
+struct OpLend {
+  bsn_bed *bed;
+  std::unique_ptr<bsn_op> op;
+  explicit OpLend(bsn_bed *b) : bed(b), op(std::move(b->svd_op)) {
+    if (!op) op.reset(new bsn_op());
+    op->passes = 0;
+    op->prof_kind_override = -1;
+    for (const void *&pk : op->prof_kernel) pk = nullptr;   // (bsn_bed_streaming_kernels names the launches of THIS solve)
+    op->stats_pending = false;
+    op->na_poll = false;
+    op->no_na = false;
+  }
+  ~OpLend() { bed->svd_op = std::move(op); }
+};
+
+// the operator with its scaling: the caller's centre / scale, or bed_scaleBinom from counts that are on the handle
+// already, that ride along the first crossproduct pass, or that the host takes (a subset of the samples)
+void setup_scaling(SolveCall &c, bsn_op *op, const double *center, const double *scale) {
+  const bsn_svd_options *o = c.o;
+  bsn_bed *bed = c.bed;
+  const int64_t n = c.n, m = c.m;
+  c.sel = StatsCols{nullptr, nullptr, 0, m};
+  if (!o->binom_scaling) {
+    fill_op(op, bed, c.ind_row, n, c.ind_col, m, center, scale, false, c.ooc);
+    return;
+  }
+  fill_op(op, bed, c.ind_row, n, c.ind_col, m, nullptr, nullptr, true, c.ooc);
+  if (c.use_stats_cache) {
+    if (c.compacted) c.sel = StatsCols{c.owner_cols, owner_cols_device(c.owner, bed, c.owner_cols, m), 0, m};
+    else if (!op->cols_contig) c.sel = StatsCols{c.ind_col, op->d_cols.p, 0, m};
+    else c.sel.col0 = op->col0;
+    c.served = op->rows_identity && stats_cache_known(c.owner, c.sel);
+  }
+  if (c.served) {
+    // every variant's counts are on the handle: centre / scale before the first launch, no pass counts, and whether
+    // the missing-value plane is needed is known from the start
+    c.fused = true;
+    stats_from_cache(op, c.owner, c.sel);
+    if (c.compacted && !getenv("BSN_FORCE_NA_PLANE")) {   // (fill_op looked at the copy's record; the owner's is the one that is known)
+      bool all0 = (int64_t)c.owner->na_cnt.size() == c.owner->m;
+      for (int64_t j = 0; all0 && j < m; j++) all0 = c.owner->na_cnt[(size_t)c.owner_cols[j]] == 0;
+      op->no_na = all0;
+    }
+  } else if (op->rows_identity) {
+    // the counts ride along the first crossproduct pass; until they are known the general kernels run
+    op->stats_pending = true;
+    op->no_na = false;
+    c.fused = true;
+  } else {
+    std::vector<int32_t> cnt((size_t)4 * m);
+    counts_host(bed, c.ind_row, n, c.ind_col, m, cnt.data());
+    std::vector<double> ce, sc;
+    binom_scale_host(cnt, n, m, ce, sc, &c.n_bad);
+    copy_h2d(bed, op->d_center.p, ce.data(), (size_t)m * 8);
+    copy_h2d(bed, op->d_scale.p, sc.data(), (size_t)m * 8);
+    if (o->center_out) std::copy(ce.begin(), ce.end(), o->center_out);
+    if (o->scale_out) std::copy(sc.begin(), sc.end(), o->scale_out);
+  }
+}
+
+void configure_backend(HipSvdBackend &bk, const SolveCall &c, bsn_op *op) {
+  const bsn_svd_options *o = c.o;
+  bk.op = op;
+  bk.ooc = c.ooc;
+  bk.ooc_cols = c.ooc ? c.ind_col : nullptr;
+  bk.st = c.bed->stream;
+  bk.n = c.n;
+  bk.m_local = c.m;
+  bk.m_total = o->m_total > 0 ? o->m_total : c.m;
+  bk.hook = o->comm ? nullptr : o->allreduce;
+  bk.ctx = o->allreduce_ctx;
+  bk.comm = o->comm;
+  bk.rank = o->hook_rank;
+  bk.world = o->hook_world > 0 ? o->hook_world : 1;
+  bk.kmax = o->k;
+  if (bk.comm && bk.comm->device != c.bed->device) fail("the communicator was created on another device");
+  if (bk.hook && (bk.rank < 0 || bk.rank >= bk.world)) fail("hook_rank %d of %d", bk.rank, bk.world);
+  bk.setup_ranks();
+  bk.timing = getenv("BSN_TIMING") != nullptr;
+  bk.speculate = getenv("BSN_NO_SPECULATION") == nullptr;
+  bk.no_fused = getenv("BSN_NO_FUSED_STEP") != nullptr;
+  bk.early_on = !bk.dist && !c.ooc && !bk.no_fused && getenv("BSN_NO_EARLY_RITZ") == nullptr;
+  bk.fused_stats = c.fused && !c.served;
+  bk.warm_den = warm_den_of(o->warm_denominator);
+  const int64_t dim = bk.n < bk.m_total ? bk.n : bk.m_total;
+  if (o->k > dim) fail("'k' is larger than the dimensions of the matrix.");
+}
+
+// what plan_solve (svd_plan.hpp) reads: the options, the operator and the switches
+SolveFacts solve_facts(const SolveCall &c, const bsn_op *op, const HipSvdBackend &bk) {
+  const bsn_svd_options *o = c.o;
+  SolveFacts f;
+  f.k = o->k, f.tol = o->tol, f.slices = o->slices, f.block = o->block, f.vec_floor = o->vec_floor;
+  f.warm_start = o->warm_start, f.warm_denominator = o->warm_denominator;
+  f.max_basis = o->max_basis, f.max_restarts = o->max_restarts, f.seed = o->seed, f.verbose = o->verbose;
+  f.m = c.m, f.m_total = bk.m_total, f.n = c.n, f.cols_contig = op->cols_contig, f.col0 = op->col0;
+  f.fused = c.fused;
+  if (const char *e = getenv("BSN_VEC_FLOOR")) f.vec_floor_set = true, f.vec_floor_env = atof(e);   // (A/B and the accuracy sweeps of the tests)
+  if (const char *e = abl_getenv("BSN_START_SLICES")) f.start_slices_set = true, f.start_slices_env = atoi(e);
+  f.zq_split = abl_getenv("BSN_ZQ_SPLIT") != nullptr;
+  return f;
+}
+
+// The second copy of the image this solve reads (which one it wants: svd_plan.hpp).  Returns true when the sample-major
+// copy is to be started behind the call.
+// (round 6) on one GPU the FIRST such solve of a handle runs without the copy — its product passes take k_prod<2>, the
+// same sums, 55 ms more at 400K x 1M — and the copy is made BEHIND it (image_smaj_start at the end of the call: a helper
+// thread allocates 100 GB and queues the transposition on a stream of its own while the caller looks at its result);
+// later solves find it.  Inside the call the copy cost 90 ms (40 of allocation on an idle device, 51 of transposition)
+// to save 55; allocated BESIDE the running solve the same hipMalloc took 1 - 2.5 s and held up every allocation of the
+// solve (profiles/r06_cold.txt).  A caller that solves once never pays for it.  A sharded solve builds it up front:
+// every rank must take the same exchange pattern, and which passes find the copy would differ between ranks.
+bool choose_second_copy(bsn_bed *bed, const HipSvdBackend &bk, const SolvePlan &plan) {
+  bool have_smaj = false, smaj_after = false;
+  if (plan.wants_smaj) {
+    if (bk.dist || getenv("BSN_SMAJ_SYNC")) have_smaj = image_smaj(bed);
+    else if (bed->d_smaj || bed->smaj_job) have_smaj = image_smaj_poll(bed) || bed->smaj_job != nullptr;
+    else have_smaj = smaj_after = !bed->smaj_tried && bed->bits == 2 && !getenv("BSN_NO_SMAJ");
+  }
+  if (!have_smaj && plan.tile_ok) image_tile(bed);
+  return smaj_after;
+}
+
+// the exchange of a sharded solve by name (bsn_svd_info::exchange_mode); 0, no product pass has recorded one yet: the
+// one the switches will make it take
+const char *exchange_name(int mode) {
+  if (mode == 0) mode = getenv("BSN_NO_SEGMENTS") ? 1 : getenv("BSN_NO_OVERLAP") ? 2 : 3;
+  return mode == 3 ? "segments, reduce-scatters on a second stream" : mode == 2 ? "segments, one stream" : "whole pass";
+}
+
+// The solve, and its repeat on 56-bit products when the first one asks for it (needs_resolve, svd_plan.hpp); `plan` is
+// the one of the last attempt afterwards.  Between the two events on the handle's stream: c.gpu_ms.
+SvdResult solve_and_repeat(SolveCall &c, HipSvdBackend &bk, bsn_op *op, const SolveFacts &facts, SolvePlan &plan, double *d,
+                           double *u, double *v) {
+  const bsn_svd_options *o = c.o;
+  bsn_bed *bed = c.bed;
+  BSN_HIP(hipEventRecord(bed->ev0, bed->stream));
+  int wd_ms = o->exchange_timeout_ms;
+  if (wd_ms == 0)
+    if (const char *e = getenv("BSN_EXCHANGE_TIMEOUT_MS")) wd_ms = atoi(e);
+  ExchangeWatchdog watchdog(bk.comm, wd_ms);
+  if (bk.comm && wd_ms > 0) bk.progress = [&watchdog] { watchdog.kick(); };
+  if (bk.comm) {
+    double junk_ms[kCommClasses];
+    int junk_n[kCommClasses];
+    bk.comm->timing = o->exchange_timing != 0;
+    comm_time_collect(bk.comm, junk_ms, junk_n);   // (leftovers of a solve that failed)
+  }
+  struct TimingOff {
+    bsn_comm *c;
+    ~TimingOff() { if (c) c->timing = false; }
+  } timing_off{bk.comm};
+  SvdResult r;
+  try {
+    r = block_lanczos_svd(bk, plan.so, d, u, v);
+  } catch (const std::exception &ex) {
+    {   // the timing events of the launches that did run are of no use to anybody
+      double pms[kProfKinds];
+      int pc[kProfKinds];
+      prof_collect(op, pms, pc);
+    }
+    if (watchdog.fired.load())
+      fail("the exchange of the sharded solve did not finish within %d ms (exchange: %s) and the communicator was aborted; "
+           "what the solve saw: %s", wd_ms, exchange_name(bk.exchange_mode), ex.what());
+    throw;
+  }
+  // the precision schedule moves bsn_op::slices step by step (set_precision): the repeat and the verdict go by the digits
+  // the solve ENDED on, as they always have
+  plan.op_slices = op->slices;
+  if (needs_resolve(r, facts, plan)) {
+    // a Krylov space exhausted on rounded products (svd_driver.hpp): only matrices whose rank fits the basis get
+    // here, so the second solve — 56-bit digits, at most four vectors per pass — is cheap, and it is run whenever
+    // the coupling block is not negligible, met tolerance or not: a matrix this small deserves its exact values
+    if (o->verbose)
+      std::fprintf(stderr, "[bsn svd] %s on %d-bit products (relative residual %.3g, %d requested triplets below their resolution): "
+                           "again with 56-bit products\n", r.exhausted ? "Krylov space exhausted" : "triplets below the products' resolution",
+                   8 * op->slices, r.max_rel_resid, r.below_resolution);
+    plan = plan_resolve(plan);
+    op->slices = plan.op_slices;
+    const SvdResult r1 = r;
+    r = block_lanczos_svd(bk, plan.so, d, u, v);
+    r.niter += r1.niter;
+    r.nops += r1.nops;
+    r.restarts += r1.restarts;
+    plan.op_slices = op->slices;
+  }
+  bk.progress = nullptr;   // (the watchdog ends with this scope)
+  const double t_solve = c.since() - c.t_create;
+  if (o->verbose > 1 || bk.timing)
+    std::fprintf(stderr,
+                 "[bsn svd] host wall ms: op_create %.2f, solve %.2f = alloc %.2f + A'Q %.2f + AZ %.2f + grams %.2f + "
+                 "orth %.2f (GPU events %.2f) + round %.2f + finalize %.2f + host algebra %.2f\n",
+                 c.t_create, t_solve, bk.t_phase[0], bk.t_phase[1], bk.t_phase[2], bk.t_phase[3], bk.t_phase[4],
+                 bk.t_phase[7], bk.t_phase[5], bk.t_phase[6],
+                 t_solve - (bk.t_phase[0] + bk.t_phase[1] + bk.t_phase[2] + bk.t_phase[3] + bk.t_phase[4] +
+                            bk.t_phase[5] + bk.t_phase[6]));
+  BSN_HIP(hipEventRecord(bed->ev1, bed->stream));
+  BSN_HIP(hipEventSynchronize(bed->ev1));
+  BSN_HIP(hipEventElapsedTime(&c.gpu_ms, bed->ev0, bed->ev1));
+  return r;
+}
+
+// What the scaling inside the solve leaves behind: the per-variant completeness of the handle, the counts for the
+// handle's cache, the > 50 % missing count of bed_colstats (src/bed-fun.cpp:40-41) and the centre / scale actually used.
+void harvest_scaling(SolveCall &c, bsn_op *op) {
+  const bsn_svd_options *o = c.o;
+  bsn_bed *bed = c.bed, *owner = c.owner;
+  const int64_t m = c.m;
+  if (c.fused && !c.served) {
+    // by-products of the counting pass.  They come back through the workspace's pinned staging buffer: blocking copies
+    // into pageable memory were measured to leave the runtime with ~4 ms wake-up latencies on every later stream
+    // synchronisation of the process (tools/gpu/r02_h.sh).
+    SvdWorkspace &ws = *bed->svd_ws;
+    const int64_t chunk = 1 << 21;  // int32 per staged piece (8 MB)
+    int32_t *hp = (int32_t *)ws.pinned((size_t)chunk / 2);
+    if ((int64_t)bed->na_cnt.size() != bed->m) bed->na_cnt.assign((size_t)bed->m, -1);
+    // ... and the counts themselves, into the handle's cache for the next solve (the downloads below synchronise)
+    const bool feed = c.use_stats_cache && !op->stats_pending && op->m == m && (int64_t)op->d_counts.n >= 4 * m;
+    if (feed) stats_cache_store(owner, c.sel, op->d_counts.p, bed->stream);
+    if (feed && c.compacted && (int64_t)owner->na_cnt.size() != owner->m) owner->na_cnt.assign((size_t)owner->m, -1);
+    for (int64_t j0 = 0; j0 < m; j0 += chunk) {
+      const int64_t cnt = std::min<int64_t>(chunk, m - j0);
+      BSN_HIP(hipMemcpyAsync(hp, op->d_na.p + j0, (size_t)cnt * 4, hipMemcpyDeviceToHost, bed->stream));
+      BSN_HIP(hipStreamSynchronize(bed->stream));
+      if (c.ind_col) {
+        for (int64_t j = 0; j < cnt; j++) bed->na_cnt[(size_t)c.ind_col[j0 + j]] = hp[j];
+      } else {
+        std::memcpy(&bed->na_cnt[(size_t)j0], hp, (size_t)cnt * 4);
+      }
+      if (feed && c.compacted)
+        for (int64_t j = 0; j < cnt; j++) owner->na_cnt[(size_t)c.owner_cols[j0 + j]] = hp[j];
+    }
+  }
+  if (c.fused) {
+    if (op->h_na_total && op->h_na_total[1] >= 0) c.n_bad += (int32_t)op->h_na_total[1];
+    if (o->center_out) copy_d2h(bed, o->center_out, op->d_center.p, (size_t)m * 8);
+    if (o->scale_out) copy_d2h(bed, o->scale_out, op->d_scale.p, (size_t)m * 8);
+  }
+}
+
+// true, with the reason as the call's error text, when the triplets are not vouched for (return code 2)
+bool unconverged_verdict(SvdResult &r, const SolvePlan &plan) {
+  const SvdOptions &so = plan.so;
+  if (r.converged && r.below_resolution > 0) {
+    // (the digits were fixed by the caller: no second solve) the triplets the test left out are not vouched for
+    r.converged = 0;
+    char buf[320];
+    std::snprintf(buf, sizeof(buf),
+                  "%d of the %d requested singular triplets lie below what %d-bit products resolve (sigma below %.1e sigma_1): "
+                  "their values are not converged; ask for more digits (slices) or fewer triplets",
+                  r.below_resolution, so.k, 8 * plan.op_slices, std::sqrt(64.0) * so.resid_floor);
+    set_error(buf);
+    return true;
+  }
+  if (!r.converged) {
+    char buf[256];
+    std::snprintf(buf, sizeof(buf),
+                  "the Krylov basis is full (%d vectors) but only a relative residual of %.3g (tol %.3g) was "
+                  "reached for the %d requested singular triplets; increase max_basis or tol",
+                  r.basis, r.max_rel_resid, so.tol, so.k);
+    set_error(buf);
+    return true;
+  }
+  return false;
+}
+
+void fill_info(bsn_svd_info *info, const SolveCall &c, const HipSvdBackend &bk, bsn_op *op, const SvdResult &r,
+               const SolveFacts &facts, const SolvePlan &plan) {
+  const SvdOptions &so = plan.so;
+  const bsn_bed *bed = c.bed;
+  info->n_bad = c.n_bad;
+  info->fused_stats = c.fused ? 1 : 0;
+  info->niter = r.niter;
+  info->nops = (int32_t)op->passes;
+  info->basis = r.basis;
+  info->converged = r.converged;
+  info->max_rel_resid = r.max_rel_resid;
+  info->gpu_ms = c.gpu_ms;
+  double pms[kProfKinds];
+  int pc[kProfKinds];
+  prof_collect(op, pms, pc);
+  if (bk.sop) {   // out-of-core: the launches ran on the slab operator, one per slab
+    double p2[kProfKinds];
+    int c2[kProfKinds];
+    prof_collect(bk.sop.get(), p2, c2);
+    for (int t = 0; t < kProfKinds; t++) {
+      pms[t] += p2[t];
+      pc[t] += c2[t];
+      if (bk.sop->prof_kernel[t]) op->prof_kernel[t] = bk.sop->prof_kernel[t];
+    }
+  }
+  info->wide_cprod_ms = pms[4];
+  info->wide_prod_ms = pms[5];
+  info->n_wide_cprod = pc[4];
+  info->n_wide_prod = pc[5];
+  info->slices_max = r.slices_used_max > 0 ? r.slices_used_max : so.slices_base;
+  info->wide_steps = r.wide_steps;
+  info->lead_rel_resid = r.lead_rel_resid;
+  info->cprod_ms = pms[0];
+  info->prod_ms = pms[1];
+  info->n_cprod = pc[0];
+  info->n_prod = pc[1];
+  info->cprod_stats_ms = pms[2];
+  info->n_cprod_stats = pc[2];
+  info->warm_ms = pms[3];
+  info->warm_launches = bk.warm_launches;
+  info->warm_fraction = bk.m_sub > 0 && bk.m_op_full > 0 ? (double)bk.m_sub / (double)bk.m_op_full : 0.0;
+  info->block = so.block;
+  info->slices = so.slices_base;
+  info->tiled = (bed->d_tiled != nullptr && op->cols_contig && (op->col0 & 63) == 0) ? 1 : 0;
+  if (bed->d_smaj != nullptr && on_prodT(so, facts)) info->tiled = 2;   // (one launch of two column blocks per product pass: k_prodT)
+  info->segmented_passes = bk.n_seg_passes;
+  info->compact_gathers = bk.n_compact_gathers;
+  info->out_of_core = c.ooc ? 1 : 0;
+  info->na_free_steps[0] = op->bed->na_free[0];
+  info->na_free_steps[1] = op->bed->na_free[1];
+  info->na_skip = (op->na_skip_c ? 1 : 0) | (op->na_skip_p ? 2 : 0);
+  info->compacted = c.compacted ? 1 : 0;
+  info->compact_ms = c.t_compact;
+  info->exchange_mode = bk.exchange_mode;
+  info->early_ritz[0] = bk.n_guess;
+  info->early_ritz[1] = bk.guess_used;
+  for (int t = 0; t < 4; t++) info->exchange_ms[t] = 0, info->n_exchange[t] = 0;
+  if (bk.comm && c.o->exchange_timing) {
+    double ems[kCommClasses];
+    int en[kCommClasses];
+    comm_time_collect(bk.comm, ems, en);
+    for (int t = 0; t < 4 && t < kCommClasses; t++) info->exchange_ms[t] = ems[t], info->n_exchange[t] = en[t];
+  }
+}
+
+}  // namespace
+
 extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n,
                                  const int64_t *ind_col, int64_t m, const double *center,
                                  const double *scale, const bsn_svd_options *o, double *d, double *u,
@@ -1633,615 +1548,30 @@ extern "C" int bsn_bed_randomsvd(bsn_bed *bed, const int64_t *ind_row, int64_t n
     if (!o) fail("options must not be NULL");
     if (o->k < 1) fail("'k' must be at least 1.");
     RoctxRange whole("bsn_bed_randomsvd");
-    auto t_begin = std::chrono::steady_clock::now();
-    auto since = [&]() {
-      return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-    };
-    // (round 5) an out-of-core handle: the passes of the solve walk the file in slabs (HipSvdBackend, "out-of-core handle")
-    const bool ooc = bed->streamed();
-    if (ooc) {
-      if (o->comm || o->allreduce) fail("an out-of-core handle cannot be one shard of a sharded solve: shard the file instead");
-      bool all_rows = n == bed->n;
-      for (int64_t i = 0; all_rows && ind_row && i < n; i++) all_rows = ind_row[i] == i;
-      bool all_cols = m == bed->m, in_order = true;
-      for (int64_t j = 0; ind_col && j < m; j++) {
-        if (ind_col[j] != j) all_cols = false;
-        if (ind_col[j] < 0 || ind_col[j] >= bed->m) fail("Tested %lld < %lld. Subscript out of bounds (ind.col).", (long long)ind_col[j], (long long)bed->m);
-        if (j > 0 && ind_col[j] <= ind_col[j - 1]) in_order = false;
-      }
-      // (round 6) a LIST of variants in file order is served too — what bed_autoSVD solves over (ind.keep, sorted)
-      if (!all_rows || !in_order)
-        fail("bed_randomSVD on an out-of-core handle (the file's image does not fit the device: it streams its file) "
-             "covers all samples, and its variants in increasing file order; a subset small enough for the device is served "
-             "by a handle of its own (snp_subset / bsn_bed_subset_payload)");
-      ind_row = nullptr;
-      if (all_cols) ind_col = nullptr;
-    }
-    // (round 5) a list of variants that is not a contiguous range: the solve runs on a compacted copy of the selection
-    bool compacted = false;
-    double t_compact = 0.0;
-    bed->last_solve_on_sub = false;
-    // the handle's device-resident code counts (bsn_bed::stats_cache) serve, and are fed by, a solve over all samples of
-    // a resident 2-bit image; on the compacted copy too, through the caller's handle and the caller's variant list
-    bsn_bed *const owner = bed;
-    const int64_t *const owner_cols = ind_col;
-    bool rows_all = !ooc && n == bed->n;
-    for (int64_t i = 0; rows_all && ind_row && i < n; i++) rows_all = ind_row[i] == i;
-    const bool use_stats_cache = o->binom_scaling && rows_all && stats_cache_enabled(owner);
-    if (bsn_bed *sub = compacted_view(bed, ind_row, n, ind_col, m)) {
-      bed->last_solve_on_sub = true;
-      if (ind_row == nullptr && n != bed->n) fail("internal: row count of a compacted solve");
-      bed = sub;
-      ind_row = nullptr;
-      ind_col = nullptr;
-      compacted = true;
-      t_compact = since();
-    }
-    // operator and workspace of the previous solve on this handle are reused (grow-only buffers)
-    struct Lend {
-      bsn_bed *bed;
-      std::unique_ptr<bsn_op> op;
-      ~Lend() { bed->svd_op = std::move(op); }
-    } lend{bed, std::move(bed->svd_op)};
-    if (!lend.op) lend.op.reset(new bsn_op());
+    SolveCall c{o, bed, ind_row, ind_col, n, m};
+    c.ooc = bed->streamed();
+    check_selection(c);
+    enter_compacted_view(c);
+    OpLend lend(c.bed);
     bsn_op *op = lend.op.get();
-    op->passes = 0;
-    op->prof_kind_override = -1;
-    for (const void *&pk : op->prof_kernel) pk = nullptr;   // (bsn_bed_streaming_kernels names the launches of THIS solve)
-    op->stats_pending = false;
-    op->na_poll = false;
-    op->no_na = false;
-    if (!bed->svd_ws) bed->svd_ws = std::make_shared<SvdWorkspace>();
-    int32_t n_bad = 0;
-    bool fused = false, served = false;
-    StatsCols sel{nullptr, nullptr, 0, m};
-    if (o->binom_scaling) {
-      fill_op(op, bed, ind_row, n, ind_col, m, nullptr, nullptr, true, ooc);
-      if (use_stats_cache) {
-        if (compacted) sel = StatsCols{owner_cols, owner_cols_device(owner, bed, owner_cols, m), 0, m};
-        else if (!op->cols_contig) sel = StatsCols{ind_col, op->d_cols.p, 0, m};
-        else sel.col0 = op->col0;
-        served = op->rows_identity && stats_cache_known(owner, sel);
-      }
-      if (served) {
-        // every variant's counts are on the handle: centre / scale before the first launch, no pass counts, and whether
-        // the missing-value plane is needed is known from the start
-        fused = true;
-        stats_from_cache(op, owner, sel);
-        if (compacted && !getenv("BSN_FORCE_NA_PLANE")) {   // (fill_op looked at the copy's record; the owner's is the one that is known)
-          bool all0 = (int64_t)owner->na_cnt.size() == owner->m;
-          for (int64_t j = 0; all0 && j < m; j++) all0 = owner->na_cnt[(size_t)owner_cols[j]] == 0;
-          op->no_na = all0;
-        }
-      } else if (op->rows_identity) {
-        // the counts ride along the first crossproduct pass; until they are known the general kernels run
-        op->stats_pending = true;
-        op->no_na = false;
-        fused = true;
-      } else {
-        std::vector<int32_t> cnt((size_t)4 * m);
-        counts_host(bed, ind_row, n, ind_col, m, cnt.data());
-        std::vector<double> ce, sc;
-        binom_scale_host(cnt, n, m, ce, sc, &n_bad);
-        copy_h2d(bed, op->d_center.p, ce.data(), (size_t)m * 8);
-        copy_h2d(bed, op->d_scale.p, sc.data(), (size_t)m * 8);
-        if (o->center_out) std::copy(ce.begin(), ce.end(), o->center_out);
-        if (o->scale_out) std::copy(sc.begin(), sc.end(), o->scale_out);
-      }
-    } else {
-      fill_op(op, bed, ind_row, n, ind_col, m, center, scale, false, ooc);
-    }
-    const double t_create = since();
+    if (!c.bed->svd_ws) c.bed->svd_ws = std::make_shared<SvdWorkspace>();
+    setup_scaling(c, op, center, scale);
+    c.t_create = c.since();
     op->profile = true;
     if (o->slices > 7) fail("slices must be in 1..7");
-    HipSvdBackend bk(*bed->svd_ws);
-    bk.op = op;
-    bk.ooc = ooc;
-    bk.ooc_cols = ooc ? ind_col : nullptr;
-    bk.st = bed->stream;
-    bk.n = n;
-    bk.m_local = m;
-    bk.m_total = o->m_total > 0 ? o->m_total : m;
-    bk.hook = o->comm ? nullptr : o->allreduce;
-    bk.ctx = o->allreduce_ctx;
-    bk.comm = o->comm;
-    bk.rank = o->hook_rank;
-    bk.world = o->hook_world > 0 ? o->hook_world : 1;
-    bk.kmax = o->k;
-    if (bk.comm && bk.comm->device != bed->device) fail("the communicator was created on another device");
-    if (bk.hook && (bk.rank < 0 || bk.rank >= bk.world)) fail("hook_rank %d of %d", bk.rank, bk.world);
-    bk.setup_ranks();
-    bk.timing = getenv("BSN_TIMING") != nullptr;
-    bk.speculate = getenv("BSN_NO_SPECULATION") == nullptr;
-    bk.no_fused = getenv("BSN_NO_FUSED_STEP") != nullptr;
-    bk.early_on = !bk.dist && !ooc && !bk.no_fused && getenv("BSN_NO_EARLY_RITZ") == nullptr;
-    bk.fused_stats = fused && !served;
-    bk.warm_den = o->warm_denominator >= 2 ? o->warm_denominator : 16;
-    int64_t dim = bk.n < bk.m_total ? bk.n : bk.m_total;
-    if (o->k > dim) fail("'k' is larger than the dimensions of the matrix.");
-    SvdOptions so;
-    so.k = o->k;
-    so.tol = o->tol > 0 ? o->tol : 1e-4;
-    // Digit slices per fp64 value and vectors per pass.  Rounding a basis block to 8 S bits leaves a
-    // relative residual of about 1.2 * 2^(-8 S) on a converged pair (the Ritz VALUES are not
-    // affected, svd_driver.hpp), so S is the smallest width whose floor is below tol / 4; the
-    // block then fills the 16 MFMA columns of one column block (8 x 2, 5 x 3, 4 x 4, 3 x 5, 2 x 7).
-    // A block chosen by the caller gets as many slices as its column blocks hold anyway.
-    {
-      int s_tol = 2;
-      while (s_tol < 7 && 1.2 * std::ldexp(1.0, -8 * s_tol) > so.tol / 4) s_tol++;
-      if (o->slices > 0) s_tol = o->slices;
-      // One column block (16 MFMA columns) holds b1 vectors, two hold b2.  A pass with two column blocks costs
-      // 1.3x a pass with one (the two-block kernels are bound by the matrix pipe and the VALU issue port, not by
-      // HBM), but the solve needs fewer block steps: measured at 400K x 1M, tol 1e-4 (profiles/r03_block_vs_k.txt):
-      // k = 20: 4 steps of 16 vectors = 8.1 passes, 204 ms, against 6 steps of 8 = 12.1 passes, 219 ms;
-      // k <= 10: 5 steps of 8 = 193 ms against 4 steps of 16 = 208 ms.  The default is chosen for the time to
-      // the solution, not for pass throughput.
-      const int b1 = std::max(1, std::min(8, 16 / s_tol)), b2 = std::max(b1, std::min(kMaxB, 32 / s_tol));
-      // (Without the warm start — fewer than 262 144 variants over all ranks — the wide block saves one step of
-      // seven instead of two of six and loses: 50 against 35 ms on a 125 000-variant matrix.)
-      const bool warm_on = o->warm_start >= 0 && bk.m_total / bk.warm_den >= 16384;
-      int bb = o->block > 0 ? (o->block > kMaxB ? kMaxB : o->block) : (4 * o->k >= 7 * b1 && warm_on ? b2 : b1);
-      int ss = s_tol;
-      if (o->slices <= 0) {
-        const int nb = (bb * s_tol + 15) / 16;
-        ss = std::max(s_tol, std::min(7, 16 * nb / bb));
-      }
-      so.block = bb;
-      op->slices = ss;
-      // precision schedule (svd_driver.hpp): wider panels for the early steps when the vectors are wanted beyond the floor
-      // of `ss` digits; a caller who fixed the digits gets them at every step unless he also names a floor
-      double vf = o->vec_floor;
-      // (round 6: 1e-7, a tenth of north_star's 1e-6.  Round 5's 2.5e-7 left the vectors the ARITHMETIC limits — small matrices
-      // that take 20 - 30 block steps, where the leading pairs converge far below tol — at 1.5 - 1.8e-6 on the oracle's
-      // shapes; 1e-7 keeps the panels at 24 bits one or two steps longer there (0.5 - 0.97e-6: what uniform 24-bit panels
-      // give) and leaves the 400K x 1M solve on the same three wide steps, its vectors being where the Lanczos process
-      // is at tol: profiles/r06_vectors_small.txt, r06_vectors_c3.txt)
-      if (vf == 0.0) vf = o->slices > 0 ? -1.0 : 1e-7;
-      if (const char *e = getenv("BSN_VEC_FLOOR")) vf = atof(e);   // (A/B and the accuracy sweeps of the tests)
-      so.slices_base = ss;
-      so.slices_max = ss;
-      so.vec_floor = 0.0;
-      if (vf > 0) {
-        int sm = ss;
-        while (sm < 7 && 1.2 * std::ldexp(1.0, -8 * sm) > vf) sm++;
-        so.slices_max = sm;
-        so.vec_floor = vf;
-      }
-      // the START block only chooses where the iteration begins: an 8-bit grid serves, and the first full crossproduct
-      // pass — the one that also counts the codes — then carries `block` digit columns instead of twice as many
-      // (16 vectors: one column block, 21 instead of 26 ms per 100 GB; same residuals, same vectors)
-      so.slices_start = o->slices > 0 ? 0 : 1;
-      if (const char *e = abl_getenv("BSN_START_SLICES")) so.slices_start = atoi(e);
-      // columns standardised by bed_scaleBinom: a random vector is amplified by sqrt(n) (svd_driver.hpp)
-      // (the product pass scheduled apart from the grids, svd_driver.hpp: measured at 400K x 1M — 12 ms saved, the
-      // leading vectors at 9e-7 instead of 1.6e-7; at k = 10, 6e-6: the rounding of Z is heavier-tailed than the model,
-      // so the split stays an experiment, BSN_ZQ_SPLIT=1)
-      so.noise_gain = (fused && abl_getenv("BSN_ZQ_SPLIT")) ? std::sqrt((double)n) : 0.0;
-    }
-    // a solve streams the image a dozen times: the ONE-block kernels, which are bound by HBM, get their layout (a
-    // second copy in 64-variant x 256-B tiles, one extra pass of copying, kept on the handle) when the device has the
-    // room: 2 - 4 % per pass.  The two-block kernels are bound by instruction issue and gain nothing from it (k_prod<2>
-    // 23.65 ms on the plain image against 23.75 on the copy, k_cprod<2> 21.65 against 21.52: profiles/r03_shape_sweeps.txt),
-    // so the default solve at k >= 14 leaves the other half of the HBM alone; a copy that exists is used either way.
-    // ... and a solve with passes of two or three column blocks (16 vectors; 8 vectors on the 24-bit panels of the
-    // precision schedule) the sample-major copy: its product passes then run as k_prodT (k_cprod's shape; DESIGN.md
-    // 3.3b) instead of k_prod<2> with its transposes and 128 accumulators — and three column blocks exist on that copy
-    // only.  One second copy per handle: when the sample-major one is not to be had (no room, BSN_NO_SMAJ) the
-    // one-block passes of the solve still get theirs.
-    bool have_smaj = false;
-    // (round 6) on one GPU the FIRST such solve of a handle runs without the copy — its product passes take k_prod<2>, the
-    // same sums, 55 ms more at 400K x 1M — and the copy is made BEHIND it (image_smaj_start at the end of this call: a helper
-    // thread allocates 100 GB and queues the transposition on a stream of its own while the caller looks at its result);
-    // later solves find it.  Inside the call the copy cost 90 ms (40 of allocation on an idle device, 51 of transposition)
-    // to save 55; allocated BESIDE the running solve the same hipMalloc took 1 - 2.5 s and held up every allocation of the
-    // solve (profiles/r06_cold.txt).  A caller that solves once never pays for it.  A sharded solve builds it up front:
-    // every rank must take the same exchange pattern, and which passes find the copy would differ between ranks.
-    const bool wants_smaj = so.block * so.slices_max > 16 && op->cols_contig && (op->col0 & 511) == 0 && m >= 4096;
-    bool smaj_after = false;
-    if (wants_smaj) {
-      if (bk.dist || getenv("BSN_SMAJ_SYNC")) have_smaj = image_smaj(bed);
-      else if (bed->d_smaj || bed->smaj_job) have_smaj = image_smaj_poll(bed) || bed->smaj_job != nullptr;
-      else have_smaj = smaj_after = !bed->smaj_tried && bed->bits == 2 && !getenv("BSN_NO_SMAJ");
-    }
-    if (!have_smaj && so.block * so.slices_base <= 16 && op->cols_contig && (op->col0 & 63) == 0 && m >= 4096) image_tile(bed);
-    so.resid_floor = 1.2 * std::ldexp(1.0, -8 * op->slices);
-    // (two iterations since round 5: + 2.5 ms, every residual of the 400K x 1M solve 4 - 10 x lower at the same step)
-    so.warm = o->warm_start < 0 ? 0 : (o->warm_start == 0 ? 2 : o->warm_start);
-    so.max_basis = o->max_basis;
-    so.max_restarts = o->max_restarts == 0 ? 100 : o->max_restarts;
-    so.seed = o->seed ? o->seed : 1;
-    so.verbose = o->verbose;
-    BSN_HIP(hipEventRecord(bed->ev0, bed->stream));
-    int wd_ms = o->exchange_timeout_ms;
-    if (wd_ms == 0)
-      if (const char *e = getenv("BSN_EXCHANGE_TIMEOUT_MS")) wd_ms = atoi(e);
-    ExchangeWatchdog watchdog(bk.comm, wd_ms);
-    if (bk.comm && wd_ms > 0) bk.progress = [&watchdog] { watchdog.kick(); };
-    if (bk.comm) {
-      double junk_ms[kCommClasses];
-      int junk_n[kCommClasses];
-      bk.comm->timing = o->exchange_timing != 0;
-      comm_time_collect(bk.comm, junk_ms, junk_n);   // (leftovers of a solve that failed)
-    }
-    struct TimingOff {
-      bsn_comm *c;
-      ~TimingOff() { if (c) c->timing = false; }
-    } timing_off{bk.comm};
-    SvdResult r;
-    try {
-      r = block_lanczos_svd(bk, so, d, u, v);
-    } catch (const std::exception &ex) {
-      {   // the timing events of the launches that did run are of no use to anybody
-        double pms[kProfKinds];
-        int pc[kProfKinds];
-        prof_collect(op, pms, pc);
-      }
-      if (watchdog.fired.load())
-        fail("the exchange of the sharded solve did not finish within %d ms (exchange: %s) and the communicator was aborted; "
-             "what the solve saw: %s", wd_ms,
-             bk.exchange_mode == 3 ? "segments, reduce-scatters on a second stream" : bk.exchange_mode == 2 ? "segments, one stream"
-             : getenv("BSN_NO_SEGMENTS") ? "whole pass" : getenv("BSN_NO_OVERLAP") ? "segments, one stream" : "segments, reduce-scatters on a second stream",
-             ex.what());
-      throw;
-    }
-    // ... and (round 6) whenever requested triplets lie below what the rounded products resolve — sigma below
-    // 1.5e-4 sigma_1 on 16-bit panels: the driver leaves them out of its convergence test (they cannot meet it there) and
-    // says so; their VALUES need the wide products.  Rare: k beyond the numerical rank at 16 bits.
-    if (((r.exhausted && r.exhausted_resid > 1e-9) || r.below_resolution > 0) && o->slices <= 0 && op->slices < 7) {
-      // a Krylov space exhausted on rounded products (svd_driver.hpp): only matrices whose rank fits the basis get
-      // here, so the second solve — 56-bit digits, at most four vectors per pass — is cheap, and it is run whenever
-      // the coupling block is not negligible, met tolerance or not: a matrix this small deserves its exact values
-      if (o->verbose)
-        std::fprintf(stderr, "[bsn svd] %s on %d-bit products (relative residual %.3g, %d requested triplets below their resolution): "
-                             "again with 56-bit products\n", r.exhausted ? "Krylov space exhausted" : "triplets below the products' resolution",
-                     8 * op->slices, r.max_rel_resid, r.below_resolution);
-      op->slices = 7;
-      so.slices_base = so.slices_max = 7;
-      so.vec_floor = 0.0;
-      so.block = std::min(so.block, 32 / 7);
-      so.resid_floor = 1.2 * std::ldexp(1.0, -8 * op->slices);
-      const SvdResult r1 = r;
-      r = block_lanczos_svd(bk, so, d, u, v);
-      r.niter += r1.niter;
-      r.nops += r1.nops;
-      r.restarts += r1.restarts;
-    }
-    const double t_solve = since() - t_create;
-    if (o->verbose > 1 || bk.timing)
-      std::fprintf(stderr,
-                   "[bsn svd] host wall ms: op_create %.2f, solve %.2f = alloc %.2f + A'Q %.2f + AZ %.2f + grams %.2f + "
-                   "orth %.2f (GPU events %.2f) + round %.2f + finalize %.2f + host algebra %.2f\n",
-                   t_create, t_solve, bk.t_phase[0], bk.t_phase[1], bk.t_phase[2], bk.t_phase[3], bk.t_phase[4],
-                   bk.t_phase[7], bk.t_phase[5], bk.t_phase[6],
-                   t_solve - (bk.t_phase[0] + bk.t_phase[1] + bk.t_phase[2] + bk.t_phase[3] + bk.t_phase[4] +
-                              bk.t_phase[5] + bk.t_phase[6]));
-    BSN_HIP(hipEventRecord(bed->ev1, bed->stream));
-    BSN_HIP(hipEventSynchronize(bed->ev1));
-    float ms = 0;
-    BSN_HIP(hipEventElapsedTime(&ms, bed->ev0, bed->ev1));
-    if (fused && !served) {
-      // by-products of the counting pass: the scaling actually used, the > 50 % missing count of
-      // bed_colstats (src/bed-fun.cpp:40-41) and the per-variant completeness of the handle.  They
-      // come back through the workspace's pinned staging buffer: blocking copies into pageable memory
-      // were measured to leave the runtime with ~4 ms wake-up latencies on every later stream
-      // synchronisation of the process (tools/gpu/r02_h.sh).
-      SvdWorkspace &ws = *bed->svd_ws;
-      const int64_t chunk = 1 << 21;  // int32 per staged piece (8 MB)
-      int32_t *hp = (int32_t *)ws.pinned((size_t)chunk / 2);
-      if ((int64_t)bed->na_cnt.size() != bed->m) bed->na_cnt.assign((size_t)bed->m, -1);
-      // ... and the counts themselves, into the handle's cache for the next solve (the downloads below synchronise)
-      const bool feed = use_stats_cache && !op->stats_pending && op->m == m && (int64_t)op->d_counts.n >= 4 * m;
-      if (feed) stats_cache_store(owner, sel, op->d_counts.p, bed->stream);
-      if (feed && compacted && (int64_t)owner->na_cnt.size() != owner->m) owner->na_cnt.assign((size_t)owner->m, -1);
-      for (int64_t j0 = 0; j0 < m; j0 += chunk) {
-        const int64_t cnt = std::min<int64_t>(chunk, m - j0);
-        BSN_HIP(hipMemcpyAsync(hp, op->d_na.p + j0, (size_t)cnt * 4, hipMemcpyDeviceToHost, bed->stream));
-        BSN_HIP(hipStreamSynchronize(bed->stream));
-        if (ind_col) {
-          for (int64_t j = 0; j < cnt; j++) bed->na_cnt[(size_t)ind_col[j0 + j]] = hp[j];
-        } else {
-          std::memcpy(&bed->na_cnt[(size_t)j0], hp, (size_t)cnt * 4);
-        }
-        if (feed && compacted)
-          for (int64_t j = 0; j < cnt; j++) owner->na_cnt[(size_t)owner_cols[j0 + j]] = hp[j];
-      }
-    }
-    if (fused) {
-      if (op->h_na_total && op->h_na_total[1] >= 0) n_bad += (int32_t)op->h_na_total[1];
-      if (o->center_out) copy_d2h(bed, o->center_out, op->d_center.p, (size_t)m * 8);
-      if (o->scale_out) copy_d2h(bed, o->scale_out, op->d_scale.p, (size_t)m * 8);
-    }
-    if (r.converged && r.below_resolution > 0) {
-      // (the digits were fixed by the caller: no second solve) the triplets the test left out are not vouched for
-      unconverged = true;
-      r.converged = 0;
-      char buf[320];
-      std::snprintf(buf, sizeof(buf),
-                    "%d of the %d requested singular triplets lie below what %d-bit products resolve (sigma below %.1e sigma_1): "
-                    "their values are not converged; ask for more digits (slices) or fewer triplets",
-                    r.below_resolution, so.k, 8 * op->slices, std::sqrt(64.0) * so.resid_floor);
-      set_error(buf);
-    } else if (!r.converged) {
-      unconverged = true;
-      char buf[256];
-      std::snprintf(buf, sizeof(buf),
-                    "the Krylov basis is full (%d vectors) but only a relative residual of %.3g (tol %.3g) was "
-                    "reached for the %d requested singular triplets; increase max_basis or tol",
-                    r.basis, r.max_rel_resid, so.tol, so.k);
-      set_error(buf);
-    }
-    if (info) {
-      info->n_bad = n_bad;
-      info->fused_stats = fused ? 1 : 0;
-      info->niter = r.niter;
-      info->nops = (int32_t)op->passes;
-      info->basis = r.basis;
-      info->converged = r.converged;
-      info->max_rel_resid = r.max_rel_resid;
-      info->gpu_ms = ms;
-      double pms[kProfKinds];
-      int pc[kProfKinds];
-      prof_collect(op, pms, pc);
-      if (bk.sop) {   // out-of-core: the launches ran on the slab operator, one per slab
-        double p2[kProfKinds];
-        int c2[kProfKinds];
-        prof_collect(bk.sop.get(), p2, c2);
-        for (int t = 0; t < kProfKinds; t++) {
-          pms[t] += p2[t];
-          pc[t] += c2[t];
-          if (bk.sop->prof_kernel[t]) op->prof_kernel[t] = bk.sop->prof_kernel[t];
-        }
-      }
-      info->wide_cprod_ms = pms[4];
-      info->wide_prod_ms = pms[5];
-      info->n_wide_cprod = pc[4];
-      info->n_wide_prod = pc[5];
-      info->slices_max = r.slices_used_max > 0 ? r.slices_used_max : so.slices_base;
-      info->wide_steps = r.wide_steps;
-      info->lead_rel_resid = r.lead_rel_resid;
-      info->cprod_ms = pms[0];
-      info->prod_ms = pms[1];
-      info->n_cprod = pc[0];
-      info->n_prod = pc[1];
-      info->cprod_stats_ms = pms[2];
-      info->n_cprod_stats = pc[2];
-      info->warm_ms = pms[3];
-      info->warm_launches = bk.warm_launches;
-      info->warm_fraction = bk.m_sub > 0 && bk.m_op_full > 0 ? (double)bk.m_sub / (double)bk.m_op_full : 0.0;
-      info->block = so.block;
-      info->slices = so.slices_base;
-      info->tiled = (bed->d_tiled != nullptr && op->cols_contig && (op->col0 & 63) == 0) ? 1 : 0;
-      if (bed->d_smaj != nullptr && so.block * so.slices_max > 16 && so.block * so.slices_max <= 48 && op->cols_contig &&
-          (op->col0 & 511) == 0)
-        info->tiled = 2;   // (one launch of two column blocks per product pass: k_prodT)
-      info->segmented_passes = bk.n_seg_passes;
-      info->compact_gathers = bk.n_compact_gathers;
-      info->out_of_core = ooc ? 1 : 0;
-      info->na_free_steps[0] = op->bed->na_free[0];
-      info->na_free_steps[1] = op->bed->na_free[1];
-      info->na_skip = (op->na_skip_c ? 1 : 0) | (op->na_skip_p ? 2 : 0);
-      info->compacted = compacted ? 1 : 0;
-      info->compact_ms = t_compact;
-      info->exchange_mode = bk.exchange_mode;
-      info->early_ritz[0] = bk.n_guess;
-      info->early_ritz[1] = bk.guess_used;
-      for (int c = 0; c < 4; c++) info->exchange_ms[c] = 0, info->n_exchange[c] = 0;
-      if (bk.comm && o->exchange_timing) {
-        double ems[kCommClasses];
-        int en[kCommClasses];
-        comm_time_collect(bk.comm, ems, en);
-        for (int c = 0; c < 4 && c < kCommClasses; c++) info->exchange_ms[c] = ems[c], info->n_exchange[c] = en[c];
-      }
-    }
+    HipSvdBackend bk(*c.bed->svd_ws);
+    configure_backend(bk, c, op);
+    const SolveFacts facts = solve_facts(c, op, bk);
+    SolvePlan plan = plan_solve(facts);
+    op->slices = plan.op_slices;
+    const bool smaj_after = choose_second_copy(c.bed, bk, plan);
+    SvdResult r = solve_and_repeat(c, bk, op, facts, plan, d, u, v);
+    harvest_scaling(c, op);
+    unconverged = unconverged_verdict(r, plan);
+    if (info) fill_info(info, c, bk, op, r, facts, plan);
     // the sample-major copy for the NEXT solve, made beside the caller's own work — started last: on a box whose free
     // memory has to be scrubbed the allocation of 100 GB takes seconds and holds up every other call into the runtime
-    if (smaj_after && !bed->d_smaj && !bed->smaj_job) (void)image_smaj_start(bed);
+    if (smaj_after && !c.bed->d_smaj && !c.bed->smaj_job) (void)image_smaj_start(c.bed);
   });
   return rc != 0 ? rc : (unconverged ? 2 : 0);
 }
-
-// ---- kernel-level entries for the tests (tests/test_gpu_svd_panel.py) --------------------------------------------------
-// The panel kernels one at a time, through the launch functions the backend uses, on caller-owned device memory
-// (bsn_malloc / bsn_memcpy_h2d / bsn_memcpy_d2h).  Null stream, synchronised before returning.  Every argument is checked
-// on the host before the first launch: no call can launch out of bounds.
-namespace bsn {
-namespace {
-constexpr int kPanelMaxP = 4096;   // basis columns the entries accept (the solve's cap is far below)
-void panel_done() {
-  BSN_HIP(hipGetLastError());
-  BSN_HIP(hipStreamSynchronize(nullptr));
-}
-// rows of a "rank's" sample block in the one-device restatements of the sharded exchanges
-int64_t panel_block_rows(int64_t n, int world) { return ((n + world - 1) / world + 3) / 4 * 4; }
-}  // namespace
-}  // namespace bsn
-
-extern "C" {
-
-int bsn_panel_gemm_tn(const double *d_A, int64_t lda, int32_t p, const double *d_B, int64_t ldb, int32_t cb, int64_t rows,
-                      double *d_C, int32_t ldc) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_A || !d_B || !d_C) fail("bsn_panel_gemm_tn: null pointer");
-    if (cb > 32) fail("internal: panel product with %d columns", (int)cb);
-    if (p < 1 || p > kPanelMaxP || cb < 1 || rows < 1 || rows > ((int64_t)1 << 31) || lda < rows || ldb < rows || ldc < p)
-      fail("bsn_panel_gemm_tn: dimensions");
-    DevBuf<double> partial;
-    partial.ensure(panel_partial_count(rows, p));
-    panel_gemm_tn(nullptr, d_A, lda, p, d_B, ldb, cb, rows, d_C, ldc, partial.p);
-    panel_done();
-  });
-}
-
-int bsn_panel_gemm_nn(const double *d_Q, int64_t ldq, int32_t p, const double *d_S, int32_t nc, const double *d_In, int64_t ldi,
-                      double alpha, double beta, double *d_Out, int64_t ldo, int64_t n) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_Q || !d_S || !d_Out || (alpha != 0.0 && !d_In)) fail("bsn_panel_gemm_nn: null pointer");
-    if (p < 1 || p > kPanelMaxP || nc < 1 || nc > kMaxB || n < 1 || n > ((int64_t)1 << 31) || ldq < n || ldo < n ||
-        (alpha != 0.0 && ldi < n))
-      fail("bsn_panel_gemm_nn: dimensions (at most %d columns)", kMaxB);
-    panel_gemm_nn(nullptr, d_Q, ldq, p, d_S, nc, d_In, ldi, alpha, beta, d_Out, ldo, n);
-    panel_done();
-  });
-}
-
-int bsn_panel_right_mult(double *d_W, int64_t ld, int64_t n, int32_t cb, int32_t r, const double *d_M) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_W || !d_M) fail("bsn_panel_right_mult: null pointer");
-    if (cb < 1 || cb > kMaxB || r < 1 || r > kMaxB || cb * r > 256 || n < 1 || n > ((int64_t)1 << 31) || ld < n)
-      fail("bsn_panel_right_mult: dimensions (at most %d columns)", kMaxB);
-    panel_right_mult(nullptr, d_W, ld, n, cb, r, d_M);
-    panel_done();
-  });
-}
-
-int bsn_panel_update(const double *d_Q, int64_t ldq, int32_t p, const double *d_C, const double *d_Ri, int32_t cb, double *d_W,
-                     int64_t ldw, int64_t n, uint64_t *d_mx) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_Ri || !d_W || (p > 0 && (!d_Q || !d_C))) fail("bsn_panel_update: null pointer");
-    if (p < 0 || p > kPanelMaxP || cb < 1 || cb > kMaxB || n < 1 || n > ((int64_t)1 << 31) || ldw < n || (p > 0 && ldq < n))
-      fail("bsn_panel_update: dimensions (at most %d columns)", kMaxB);
-    panel_update(nullptr, d_Q, ldq, p, d_C, d_Ri, cb, d_W, ldw, n, (unsigned long long *)d_mx);
-    panel_done();
-  });
-}
-
-int bsn_panel_round_cols(double *d_X, int64_t ld, int64_t rows, int32_t cb, int32_t slices, int32_t have_mx, uint64_t *d_mx,
-                         int32_t wide_grid) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_X || !d_mx) fail("bsn_panel_round_cols: null pointer");
-    if (cb < 1 || cb > kMaxB || rows < 1 || rows > ((int64_t)1 << 31) || ld < rows || slices < 1 || slices > 7)
-      fail("bsn_panel_round_cols: dimensions (at most %d columns, 1 to 7 slices)", kMaxB);
-    unsigned long long *mx = (unsigned long long *)d_mx;
-    if (!have_mx) {
-      BSN_HIP(hipMemsetAsync(mx, 0, (size_t)cb * 8, nullptr));
-      panel_col_absmax(nullptr, d_X, ld, rows, cb, mx, wide_grid != 0);
-    }
-    panel_round_cols(nullptr, d_X, ld, rows, cb, mx, slices);
-    panel_done();
-  });
-}
-
-// returns -1 where HipSvdBackend::fused would (the caller takes the step-by-step path), 0 when the queue ran
-int bsn_panel_fused_orth(double *d_QW, int64_t nr, int32_t p, int32_t p0, int32_t cb, int32_t iters, double *flag_out,
-                         double *Rout_out) {
-  bool unsupported = false;
-  const int rc = guarded([&] {
-    require_gpu();
-    if (!d_QW || !flag_out || !Rout_out) fail("bsn_panel_fused_orth: null pointer");
-    if (p < 0 || cb < 1 || nr < 1 || nr > ((int64_t)1 << 31) || iters < 0 || iters > 8)
-      fail("bsn_panel_fused_orth: dimensions");
-    if (cb > kMaxB || p + cb > kOrthMaxP) {
-      unsupported = true;
-      return;
-    }
-    // the newest basis block is the cb columns in front of the panel, as in a solve
-    if ((p == 0 && p0 != 0) || (p > 0 && (p < cb || p0 != p - cb))) fail("bsn_panel_fused_orth: p0 must be p - cb");
-    constexpr int B2 = kMaxB * kMaxB;
-    const size_t pc = (size_t)p * cb, hg = (size_t)(p + cb) * cb;
-    DevBuf<double> dorth, dM, partial;
-    dorth.ensure((size_t)16 + 3 * B2 + 7 * (size_t)(p + cb + 4) * kMaxB);
-    dM.ensure((size_t)kOrthMaxP * kOrthMaxP);
-    partial.ensure(panel_partial_count(nr, p + cb));
-    hipStream_t st = nullptr;
-    double *Q = d_QW, *Wc = d_QW + (int64_t)p * nr;
-    // the device copy of Q'Q as the earlier steps of a solve would have left it (the newest block is folded in again below)
-    BSN_HIP(hipMemsetAsync(dM.p, 0, (size_t)kOrthMaxP * kOrthMaxP * 8, st));
-    for (int c0 = 0; c0 < p; c0 += 2 * kMaxB)
-      panel_gemm_tn(st, Q, nr, p, Q + (int64_t)c0 * nr, nr, std::min(2 * kMaxB, p - c0), nr, dM.p + (size_t)c0 * kOrthMaxP,
-                    kOrthMaxP, partial.p);
-    // ---- the queue of HipSvdBackend::fused: the same arena, the same order ----
-    unsigned long long *mx = (unsigned long long *)dorth.p;
-    double *flag = dorth.p + 16, *dRout = flag + 1, *dZtZ = dRout + B2, *X = dZtZ + pc, *HG1 = X + (p > 0 ? hg : 0),
-           *HG2 = HG1 + hg, *C = HG2 + hg, *Ct = C + pc, *Ri = Ct + pc;
-    const double *A0 = p > 0 ? Q : Wc;
-    BSN_HIP(hipMemsetAsync(flag, 0, (size_t)(1 + B2) * 8, st));
-    OrthSmall a;
-    a.p = p;
-    a.cb = cb;
-    a.p0 = p0;
-    a.QtQ = p > 0 ? X : nullptr;
-    a.ldq = p + cb;
-    a.M = dM.p;
-    a.ldm = kOrthMaxP;
-    a.C = C;
-    a.Ct = Ct;
-    a.Ri = Ri;
-    a.Rout = dRout;
-    a.flag = flag;
-    a.iters = iters;
-    a.Cs = a.Gs = a.Rs = a.Ris = a.Ro = a.Dv = a.tmp = nullptr;
-    for (int pass = 0; pass < 2; pass++) {
-      double *HG = pass == 0 ? HG1 : HG2;
-      if (pass == 0 && p > 0)
-        panel_gemm_tn(st, Q, nr, p + cb, Q + (int64_t)p0 * nr, nr, 2 * cb, nr, X, p + cb, partial.p);
-      else
-        panel_gemm_tn(st, A0, nr, p + cb, Wc, nr, cb, nr, HG, p + cb, partial.p);
-      a.pass = pass;
-      a.HG = HG;
-      unsigned long long *mxp = pass == 1 ? mx : nullptr;
-      panel_orth2(st, a, mxp);
-      panel_update(st, Q, nr, p, C, Ri, cb, Wc, nr, nr, mxp);
-    }
-    panel_done();
-    std::vector<double> h((size_t)1 + B2);
-    BSN_HIP(hipMemcpy(h.data(), flag, h.size() * 8, hipMemcpyDeviceToHost));
-    *flag_out = h[0];
-    for (int t = 0; t < cb * cb; t++) Rout_out[t] = h[1 + (size_t)t];
-  });
-  return rc != 0 ? rc : (unsupported ? -1 : 0);
-}
-
-int bsn_panel_compact_gather(const double *d_full, int64_t n, int32_t cb, int32_t world, int32_t slices, double *d_out) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_full || !d_out) fail("bsn_panel_compact_gather: null pointer");
-    if (n < 1 || n > ((int64_t)1 << 31) || cb < 1 || cb > kMaxB || world < 1 || world > 64 || slices < 1 || slices > 4)
-      fail("bsn_panel_compact_gather: dimensions (at most %d columns, 64 ranks, 4 slices)", kMaxB);
-    const int64_t nr = panel_block_rows(n, world);
-    const size_t blk = (size_t)nr * cb, isz = slices <= 2 ? 2 : 4;
-    DevBuf<double> Wr, q_all;
-    DevBuf<unsigned long long> gmax, mx;
-    Wr.ensure(blk * world);
-    q_all.ensure((blk * world * isz + 7) / 8);
-    gmax.ensure((size_t)world * kMaxB);
-    mx.ensure(kMaxB);
-    hipStream_t st = nullptr;
-    BSN_HIP(hipMemsetAsync(gmax.p, 0, (size_t)world * kMaxB * 8, st));
-    for (int r = 0; r < world; r++) {
-      panel_take_rows(st, d_full, n, cb, nr, (int64_t)r * nr, Wr.p + blk * r);
-      panel_col_absmax(st, Wr.p + blk * r, nr, nr, cb, gmax.p + (size_t)r * cb, false);
-    }
-    panel_max_over_ranks(st, gmax.p, world, cb, mx.p);
-    for (int r = 0; r < world; r++)
-      panel_pack_int(st, Wr.p + blk * r, nr, cb, mx.p, slices, (char *)q_all.p + blk * r * isz);
-    panel_unpack_int(st, q_all.p, n, cb, nr, mx.p, slices, d_out);
-    panel_done();
-  });
-}
-
-int bsn_panel_block_roundtrip(const double *d_full, int64_t n, int32_t cb, int32_t world, double *d_out, double *d_placed) {
-  return guarded([&] {
-    require_gpu();
-    if (!d_full || !d_out || !d_placed) fail("bsn_panel_block_roundtrip: null pointer");
-    if (n < 1 || n > ((int64_t)1 << 31) || cb < 1 || cb > kMaxB || world < 1 || world > 64)
-      fail("bsn_panel_block_roundtrip: dimensions (at most %d columns, 64 ranks)", kMaxB);
-    const int64_t nr = panel_block_rows(n, world);
-    DevBuf<double> blk;
-    blk.ensure((size_t)world * cb * nr);
-    hipStream_t st = nullptr;
-    panel_block(st, d_full, n, cb, nr, world, blk.p);
-    panel_unblock(st, blk.p, n, cb, nr, d_out);
-    // every rank's chunk (nr x cb) as a received segment into its rows of a panel with world * nr rows
-    for (int r = 0; r < world; r++)
-      panel_place_rows(st, blk.p + (size_t)r * cb * nr, nr, cb, (int64_t)r * nr, (int64_t)world * nr, d_placed);
-    panel_done();
-  });
-}
-
-}  // extern "C"

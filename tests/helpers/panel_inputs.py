@@ -1,4 +1,4 @@
-"""Inputs, statements and comparisons of tests/test_gpu_svd_panel.py (the panel kernels of bigsnpr_amd/csrc/svd.hip reached
+"""Inputs, statements and comparisons of tests/test_gpu_svd_panel.py (the panel kernels of bigsnpr_amd/csrc/svd_panel.hip reached
 through the bsn_panel_* entries), plain numpy, seeded, no GPU.  tests/test_panel_inputs_cpu.py shows without a GPU that the
 listed shapes have teeth: the tiling of k_gemm_tn / k_gemm_tn_reduce and of k_update restated here passes every comparison,
 and each named mutant of it fails at least one.

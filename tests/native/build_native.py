@@ -10,7 +10,7 @@ SO = os.path.join(HERE, "libnative_test_san.so" if SAN else "libnative_test.so")
 
 def build():
     src = os.path.join(HERE, "native_test.cpp")
-    deps = [src] + [os.path.join(ROOT, "bigsnpr_amd", "csrc", f) for f in ("svd_driver.hpp", "dense_small.hpp", "orth_small.hpp", "ld_plan.hpp", "byte_plan.hpp", "prod_plan.hpp")]
+    deps = [src] + [os.path.join(ROOT, "bigsnpr_amd", "csrc", f) for f in ("svd_driver.hpp", "dense_small.hpp", "orth_small.hpp", "ld_plan.hpp", "byte_plan.hpp", "prod_plan.hpp", "svd_plan.hpp")]
     if not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in deps):
         flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"] if SAN else ["-O2"]
         subprocess.check_call(["g++"] + flags + ["-std=c++17", "-fPIC", "-shared", "-Wall",

@@ -3,7 +3,7 @@
 // that the driver logic — including the column-sharded multi-rank path with an all-reduce
 // hook — can be tested without a GPU (gloo, world_size 2).  Not part of the product.
 // Also the kernel choice of the windowed-LD band (ld_plan.hpp) and the launch geometry and kernel choice of the streaming
-// products (prod_plan.hpp), which are plain C++ for the same reason.
+// products (prod_plan.hpp) and the solve plan of bsn_bed_randomsvd (svd_plan.hpp), which are plain C++ for the same reason.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -13,6 +13,7 @@
 #include "orth_small.hpp"
 #include "prod_plan.hpp"
 #include "svd_driver.hpp"
+#include "svd_plan.hpp"
 
 using namespace bsn;
 
@@ -451,4 +452,44 @@ void nt_choose_prodT(int NB, int has_q, int warm, int na_skip, int sparse_ok, in
   const ProdTKernel k = choose_prodT(NB, has_q != 0, warm != 0, na_skip != 0, sparse_ok != 0);
   out[0] = k.NB, out[1] = k.hasq, out[2] = k.tag, out[3] = k.sgb, out[4] = k.naskip, out[5] = k.sparse;
 }
+
+// ---- svd_plan.hpp (tests/test_svd_plan_cpu.py) ----
+// facts: k, tol, slices, block, vec_floor, warm_start, warm_denominator, max_basis, max_restarts, seed, verbose, m, m_total, n,
+//        cols_contig, col0, fused, BSN_VEC_FLOOR set, its value, BSN_START_SLICES set, its value, BSN_ZQ_SPLIT set
+static SolveFacts svd_facts_of(const double *f) {
+  SolveFacts s;
+  s.k = (int)f[0], s.tol = f[1], s.slices = (int)f[2], s.block = (int)f[3], s.vec_floor = f[4], s.warm_start = (int)f[5];
+  s.warm_denominator = (int)f[6], s.max_basis = (int)f[7], s.max_restarts = (int)f[8], s.seed = (uint32_t)f[9], s.verbose = (int)f[10];
+  s.m = (int64_t)f[11], s.m_total = (int64_t)f[12], s.n = (int64_t)f[13], s.cols_contig = f[14] != 0, s.col0 = (int64_t)f[15];
+  s.fused = f[16] != 0, s.vec_floor_set = f[17] != 0, s.vec_floor_env = f[18], s.start_slices_set = f[19] != 0;
+  s.start_slices_env = (int)f[20], s.zq_split = f[21] != 0;
+  return s;
+}
+// plan: k, tol, block, slices_base, slices_max, vec_floor, slices_start, resid_floor, noise_gain, warm, max_basis, max_restarts,
+//       seed, verbose, op_slices, warm_on, wants_smaj, tile_ok
+static void svd_plan_out(const SolvePlan &p, double *o) {
+  const SvdOptions &so = p.so;
+  o[0] = so.k, o[1] = so.tol, o[2] = so.block, o[3] = so.slices_base, o[4] = so.slices_max, o[5] = so.vec_floor, o[6] = so.slices_start;
+  o[7] = so.resid_floor, o[8] = so.noise_gain, o[9] = so.warm, o[10] = so.max_basis, o[11] = so.max_restarts, o[12] = so.seed;
+  o[13] = so.verbose, o[14] = p.op_slices, o[15] = p.warm_on, o[16] = p.wants_smaj, o[17] = p.tile_ok;
+}
+static SolvePlan svd_plan_in(const double *o) {
+  SolvePlan p;
+  SvdOptions &so = p.so;
+  so.k = (int)o[0], so.tol = o[1], so.block = (int)o[2], so.slices_base = (int)o[3], so.slices_max = (int)o[4], so.vec_floor = o[5];
+  so.slices_start = (int)o[6], so.resid_floor = o[7], so.noise_gain = o[8], so.warm = (int)o[9], so.max_basis = (int)o[10];
+  so.max_restarts = (int)o[11], so.seed = (uint32_t)o[12], so.verbose = (int)o[13];
+  p.op_slices = (int)o[14], p.warm_on = o[15] != 0, p.wants_smaj = o[16] != 0, p.tile_ok = o[17] != 0;
+  return p;
+}
+void nt_svd_plan(const double *facts, double *out) { svd_plan_out(plan_solve(svd_facts_of(facts)), out); }
+// the 56-bit repeat of a plan (both in the layout of nt_svd_plan's out)
+void nt_svd_plan_resolve(const double *plan, double *out) { svd_plan_out(plan_resolve(svd_plan_in(plan)), out); }
+int nt_svd_needs_resolve(int exhausted, double exhausted_resid, int below_resolution, const double *facts, const double *plan) {
+  SvdResult r;
+  r.exhausted = exhausted, r.exhausted_resid = exhausted_resid, r.below_resolution = below_resolution;
+  return needs_resolve(r, svd_facts_of(facts), svd_plan_in(plan)) ? 1 : 0;
+}
+// bsn_svd_info::tiled == 2 for a solve that ran with `plan` on a handle that has the sample-major copy
+int nt_svd_on_prodT(const double *facts, const double *plan) { return on_prodT(svd_plan_in(plan).so, svd_facts_of(facts)) ? 1 : 0; }
 }

@@ -1,4 +1,4 @@
-"""The panel kernels of bigsnpr_amd/csrc/svd.hip one at a time, through the bsn_panel_* entries (the launch functions the solve
+"""The panel kernels of bigsnpr_amd/csrc/svd_panel.hip one at a time, through the bsn_panel_* entries (the launch functions the solve
 itself uses), past their tile and loop edges: k_gemm_tn<1|2> + k_gemm_tn_reduce, k_gemm_nn, k_right_mult, k_update<8|16>,
 k_col_absmax + k_round_cols, k_take_rows / k_max_over_ranks / k_pack_int / k_unpack_int, k_block / k_unblock / k_place_rows, and
 the device queue of the fused block step (k_orth2 between the tall kernels).

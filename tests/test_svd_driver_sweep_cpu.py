@@ -22,6 +22,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tests", "native"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
 CAP_S = 240.0
 
@@ -32,18 +33,36 @@ def nt():
     return C.CDLL(build_native.build())
 
 
+def _auto_plan(nt, b):
+    """svd.hip's automatic mode as svd_plan.hpp decides it at the sweep's tolerance: the digits and the schedule of the
+    first solve, and its repeat for a block of b vectors"""
+    import svd_plan_calls as P
+    first = P.plan(nt, tol=1e-4)
+    return first, P.resolve(nt, dict(first, block=b))
+
+
+def test_the_plan_is_the_one_the_sweep_was_written_for(nt):
+    for b in (1, 2, 4, 8, 16):
+        first, again = _auto_plan(nt, b)
+        assert (first["slices_base"], first["vec_floor"], first["slices_max"], first["slices_start"]) == (2, 1e-7, 3, 1)
+        assert (again["slices_base"], again["slices_max"], again["vec_floor"], again["block"]) == (7, 7, 0.0, min(b, 4))
+        # (the one thing the sweep did otherwise: its repeat began on the 56-bit grid; the product's begins on the 8-bit one)
+        assert again["slices_start"] == 1
+
+
 def _auto_solve(nt, T, A, k, block, seed):
     """svd.hip's automatic mode: 16-bit base + schedule; 56-bit products when the driver says so"""
     b = block if block else 8
-    nt.nt_set_slices(2)
-    nt.nt_set_schedule(C.c_double(1e-7), 3, 1)
-    r = T.host_svd(nt, A, k, tol=1e-4, block=b, seed=seed)
+    first, again = _auto_plan(nt, b)
+    nt.nt_set_slices(int(first["slices_base"]))
+    nt.nt_set_schedule(C.c_double(first["vec_floor"]), int(first["slices_max"]), int(first["slices_start"]))
+    r = T.host_svd(nt, A, k, tol=first["tol"], block=b, seed=seed)
     if r["refused"]:
         return r
     if r["resolve"]:
-        nt.nt_set_slices(7)
-        nt.nt_set_schedule(C.c_double(0.0), 0, 0)
-        r = T.host_svd(nt, A, k, tol=1e-4, block=min(b, 4), seed=seed)
+        nt.nt_set_slices(int(again["slices_base"]))
+        nt.nt_set_schedule(C.c_double(again["vec_floor"]), int(again["slices_max"]), int(again["slices_start"]))
+        r = T.host_svd(nt, A, k, tol=again["tol"], block=int(again["block"]), seed=seed)
     return r
 
 
