@@ -116,6 +116,14 @@ SIGNATURES = {
     "bsn_pca_oadp_proj": (C.c_int, [f64p, f64p, f64p, i64, i64, f64p]),
     "bsn_bed_project_pca": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, f64p, f64p, f64p, f64p]),
     "bsn_project_last_ms": (C.c_int, [f64p]),
+    "bsn_qp_max_k": (C.c_int, []),
+    "bsn_qp_simplex": (C.c_int, [f64p, i64, f64p, i64, C.c_int32, f64p, i32p, i64p]),
+    "bsn_ancestry_moments": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, i64, i64, C.c_int32] + [f64p] * 7),
+    "bsn_ancestry_summary": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, f64p, i64, i64, i64, f64p, C.c_int32, C.c_int32, f64p, f64p,
+                                       f64p, i32p]),
+    "bsn_bed_ancestry": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p,
+                                   i32p]),
+    "bsn_ancestry_last_ms": (C.c_int, [f64p]),
     "bsn_mult_lin_reg":(C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
     "bsn_univ_linreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p, f64p]),
     "bsn_univ_logreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, C.c_double, C.c_int32, f64p, f64p, i32p]),

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "bsn_internal.hpp"
+#include "lane_group.hpp"
 #include "oadp_step.hpp"
 
 namespace bsn {
@@ -23,23 +24,7 @@ namespace {
 // device milliseconds of the last call of this process (bsn_project_last_ms): the product and row-norm passes, the OADP launch
 double g_last_ms[2] = {0.0, 0.0};
 
-constexpr int kWave = 64;
-
-template <int W>
-struct LaneGroup {
-  static constexpr int width = W;
-  int lane;
-  __device__ __forceinline__ double sum(double x) const {
-#pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, W);
-    return x;
-  }
-  __device__ __forceinline__ void sync() const {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-};
+constexpr int kWave = kLaneGroupWave;   // LaneGroup: lane_group.hpp
 
 // XV, out: n x K column-major; one sample per group of W lanes, 64 / W samples per workgroup of one wave
 template <int W>

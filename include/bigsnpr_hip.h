@@ -438,6 +438,45 @@ int bsn_bed_project_pca(bsn_bed *bed, const int64_t *ind_row, int64_t n, const i
  * passes (0 for bsn_pca_oadp_proj), [1] the OADP launch.  One record per process, written without a lock. */
 int bsn_project_last_ms(double *ms_out /* 2 */);
 
+/* ---- ancestry proportions from allele frequencies (ancestry.hip) ---------------------------------------------------------
+ * snp_ancestry_summary (R/ancestry-summary.R:31-74; Privé 2022) for many frequency vectors at once, and for every sample of
+ * a genotype image (frequency = genotype / 2).  quadprog::solve.QP and Matrix::nearPD, which the reference calls, are
+ * external to its tree: parity with their numbers is not pinned; the rule is stated in csrc/qp_step.hpp and
+ * pinned against a CPU statement compiled from that header.
+ * The primitive: B problems   minimise 1/2 w'D w - d'w   s.t.  w >= 0,  sum w = 1 (sum_to_one) or sum w <= 1,   that share
+ * D (K x K, column-major, symmetric positive definite), by the dual active-set method of Goldfarb & Idnani, one group of
+ * lanes per problem.  dvec: K x B column-major; w_out: B x K column-major; steps_out [B]: active-set steps, -1: a NaN or an
+ * infinity in d (a NaN row), -2: the step cap was reached (a NaN row; counted in n_failed).  Host buffers.  Refused with
+ * a message before any launch: K < 1, K > 60 (bsn_qp_max_k), a D whose Cholesky factorisation fails. */
+int bsn_qp_max_k(void);
+int bsn_qp_simplex(const double *D, int64_t K, const double *dvec, int64_t B, int32_t sum_to_one, double *w_out,
+                   int32_t *steps_out, int64_t *n_failed);
+/* The moment pass over P (M x L), X0 (M x K) and F (M x B, B may be 0: F is not read), column-major with leading
+ * dimensions >= M; on_device != 0: the three are device pointers (bsn_malloc), else host.  Host results, column-major and
+ * compact, each may be NULL: PtX0 = P'X0 (L x K), PtF (L x B), G0 = X0'X0 (K x K), X0tF (K x B), the column sums csX0 [K]
+ * and csF [B], the column sums of squares sqF [B].  fp64; rows in slabs of 4096 whose partial sums are added in ascending
+ * order (the same bits in every run); BSN_ANC_SLABS=<s> forces the number of slabs.  1 <= K <= 60, 1 <= L <= 64. */
+int bsn_ancestry_moments(const double *P, int64_t ldp, const double *X0, int64_t ldx, const double *F, int64_t ldf, int64_t M,
+                         int64_t L, int64_t K, int64_t B, int32_t on_device, double *PtX0, double *PtF, double *G0,
+                         double *X0tF, double *csX0, double *csF, double *sqF);
+/* The moment pass, then one program per column of F: X = P'X0, y = (P'f) o correction [L], dvec = X'y, D = Dmat — which the
+ * caller derives from X (Matrix::nearPD of X'X in the reference).  w, cor_each (cor(X0[, k], f)): B x K column-major;
+ * cor_pred (cor(X0 w, f)) and steps: B.  Matrices as for bsn_ancestry_moments; everything else host. */
+int bsn_ancestry_summary(const double *F, int64_t ldf, int64_t B, const double *X0, int64_t ldx, const double *P, int64_t ldp,
+                         const double *correction, int64_t M, int64_t L, int64_t K, const double *Dmat, int32_t sum_to_one,
+                         int32_t on_device, double *w, double *cor_each, double *cor_pred, int32_t *steps);
+/* The same for the n selected samples of a resident 2-bit image, f = g / 2 over the m selected variants: X0 (m x K), P
+ * (m x L), Xproj = P'X0 (L x K), compact host matrices.  One product pass A~ [P | X0 | c | 1] with centre 2 c and scale 2,
+ * c_j = mean_k X0[j, k] (a missing genotype counts as c_j: a sample's result depends on its own row alone), the row sums of
+ * squares, a moment pass over the tables, then the program kernel on the device buffers.  Results n x K / n as above.
+ * A byte image (dosages) or a generic FBM.code256 handle is refused with a message. */
+int bsn_bed_ancestry(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const double *X0,
+                     const double *P, const double *correction, int64_t L, int64_t K, const double *Dmat, const double *Xproj,
+                     int32_t sum_to_one, double *w, double *cor_each, double *cor_pred, int32_t *steps);
+/* device milliseconds (HIP events) of the last of the four calls above in this process: [0] the genotype pass (product and
+ * row norms), [1] the moment pass, [2] the program kernel.  One record per process, written without a lock. */
+int bsn_ancestry_last_ms(double *ms_out /* 3 */);
+
 /* The genotype-touching part of snp_grid_PRS (R/SCT.R:201-262), which in the
  * reference is one snp_PRS call (R/PRS.R:36-76 -> bigstatsr::big_prodVec) per clumping set:
  * scores for C column sets x T thresholds in a single sweep, one n x C GEMM per threshold bin.
