@@ -1,5 +1,7 @@
-"""Shared by tests/test_ancestry_cpu.py and tests/test_gpu_ancestry.py: the quadratic programs of the case list C1 with
-the checks against the definition (feasibility, KKT), and the planted-mixture tables of C3 on the golden .bed files."""
+"""Shared by tests/test_ancestry_cpu.py, tests/test_gpu_ancestry.py and tests/test_gpu_ancestry_shapes.py: the quadratic
+programs of the case list C1 with the checks against the definition (feasibility, KKT), the planted-mixture tables of C3 on
+the golden .bed files, and the synthetic tables of the shape sweep (a correction that is not all ones, every group width)."""
+import functools
 import os
 
 import numpy as np
@@ -48,6 +50,23 @@ def check_solution(D, d, w, sum_to_one, what=""):
     res = kkt_residuals(D, d, w, sum_to_one)
     assert max(res) <= tol, (what, res, tol)
     return max(res) / tol
+
+
+def same_minimiser(D, d, got, want, s1, what):
+    """one device solution against the statement's on the same D and d: objectives, and the C1 checks on the device's w;
+    returns the worst KKT residual over tol_kkt"""
+    f, fr = objective(D, d, got), objective(D, d, want)
+    assert abs(f - fr) <= 1e-12 * (1.0 + abs(fr)), (what, f, fr)
+    return check_solution(D, d, got, s1, what)
+
+
+def group_width(K):
+    """lanes of a wave that k_anc_qp gives one problem"""
+    return 8 if K <= 8 else 16 if K <= 16 else 32 if K <= 32 else 64
+
+
+def per_workgroup(K):
+    return 64 // group_width(K)
 
 
 def slsqp(D, d, sum_to_one):
@@ -136,6 +155,11 @@ def tables(G, groups, L):
     """X0: the allele frequency of every group (list of row-index arrays), m x K; P: the first L right singular vectors of
     the binomially scaled matrix, divided by the scale, m x L; correction: ones"""
     X0 = np.asfortranarray(np.stack([np.nanmean(G[g], axis=0) / 2.0 for g in groups], axis=1))
+    return X0, projection(G, L), np.ones(L)
+
+
+def projection(G, L):
+    """P of tables()"""
     p = np.nanmean(G, axis=0) / 2.0
     scale = np.sqrt(2.0 * p * (1.0 - p))
     ok = scale > 0
@@ -145,7 +169,7 @@ def tables(G, groups, L):
     V = np.linalg.svd(Z, full_matrices=False)[2][:L].T
     P = np.zeros_like(V)
     P[ok] = V[ok] / scale[ok, None]
-    return X0, np.asfortranarray(P), np.ones(L)
+    return np.asfortranarray(P)
 
 
 def example_tables(L):
@@ -167,3 +191,122 @@ def missing_tables(K=5, L=3):
     groups = [np.arange(k, G.shape[0], K) for k in range(K)]
     X0, P, corr = tables(G, groups, L)
     return dict(G=G, X0=X0, P=P, corr=corr)
+
+
+# ---- the shape sweep: synthetic tables with a real correction ----------------------------------------------------------------
+def synthetic_tables(n, m, K, L, seed, na=0.0):
+    """dict(G, X0, P, corr).  X0 (m x K): a base frequency U(0.1, 0.9) per variant plus 0.12 N(0, 1) per population, clipped
+    to [0.02, 0.98] (no NaN, whatever `na`); G (n x m doubles, NaN = missing): sample i drawn binomial(2, .) from population
+    i mod K, a share `na` of the cells missing; P as tables() forms it; corr = 1 + 0.013 j^1.5: distinct and increasing, as
+    the reference's corrections are (up to about 7.5 at L = 64)"""
+    assert n >= L + 6, "the centred n x m matrix must have L directions"
+    rng = np.random.default_rng(seed)
+    base = rng.uniform(0.1, 0.9, size=m)
+    X0 = np.clip(base[:, None] + 0.12 * rng.normal(size=(m, K)), 0.02, 0.98)
+    G = rng.binomial(2, X0[:, np.arange(n) % K].T).astype(np.float64)
+    if na > 0:
+        G[rng.uniform(size=(n, m)) < na] = np.nan
+    G = np.asfortranarray(G)
+    return dict(G=G, X0=np.asfortranarray(X0), P=projection(G, L), corr=1.0 + 0.013 * np.arange(L) ** 1.5)
+
+
+# two K per group width of k_anc_qp, on both sides of each boundary, then two tables with L < K (cond(Dmat) about 1e8)
+SHAPE_SWEEP = [(1, 1), (8, 8), (9, 12), (16, 20), (17, 20), (32, 40), (33, 40), (60, 64), (19, 5), (60, 10)]
+RANK_DEFICIENT = [(19, 5), (60, 10)]
+SWEEP_SEED = {kl: 7000 + 100 * kl[0] + kl[1] for kl in SHAPE_SWEEP}   # chosen in tests/test_ancestry_cpu.py (the input claims)
+
+
+def sweep_counts(K):
+    """problem counts around a workgroup of k_anc_qp"""
+    pw = per_workgroup(K)
+    return sorted({b for b in (1, pw - 1, pw, pw + 1, 4 * pw + 3) if b >= 1})
+
+
+def sweep_dims(K, L):
+    """(n, m) of the image of one sweep entry: m is no multiple of 4, 64 or 512; n holds the largest problem count and the
+    L directions"""
+    return max(4 * per_workgroup(K) + 3, L + 6), 301 if K <= 19 else 523
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_tables(K, L, na=0.0):
+    """the tables of one sweep entry; made once, shared by the tests and left unchanged"""
+    n, m = sweep_dims(K, L)
+    t = synthetic_tables(n, m, K, L, SWEEP_SEED[(K, L)], na)
+    for a in t.values():
+        a.setflags(write=False)
+    return t
+
+
+def fill_missing(G, X0):
+    """a missing cell counts as 2 c_j, c_j = mean_k X0[j, k]: what bed_ancestry makes of it"""
+    return np.where(np.isnan(G), 2.0 * X0.mean(axis=1)[None, :], G)
+
+
+def frequency_columns(t, B, seed):
+    """M x B frequency columns for the summary path, column b a function of (seed, b) alone, cycling through: a planted
+    sparse mixture X0 w; the same mixture shrunk by 0.6 (under sum_to_one = False the sum constraint is inactive); a genotype
+    row of G divided by 2 (noise: several bounds active, cor_pred well below 1).  No column is constant."""
+    X0 = t["X0"]
+    M, K = X0.shape
+    Gf = fill_missing(t["G"], X0)
+    F = np.empty((M, B), order="F")
+    for b in range(B):
+        rng = np.random.default_rng([seed, b])
+        w = np.zeros(K)
+        support = rng.choice(K, size=min(K, 3), replace=False)
+        w[support] = rng.dirichlet(np.ones(support.size) * 2.0)
+        kind = b % 3
+        F[:, b] = X0 @ w if kind == 0 else 0.6 * (X0 @ w) if kind == 1 else Gf[rng.integers(Gf.shape[0])] / 2.0
+        assert F[:, b].max() > F[:, b].min()
+    return F
+
+
+def definition_d(t, F):
+    """d = X'((P'f) o corr) of every column of F in numpy, K x B, with X = P'X0"""
+    X = t["P"].T @ t["X0"]
+    return X.T @ ((t["P"].T @ F) * t["corr"][:, None])
+
+
+def corrcoef_reference(X0, F, w):
+    """(cor_each: B x K, cor_pred: B) by np.corrcoef; a prediction without variance gives NaN"""
+    B, K = w.shape
+    each, pred = np.empty((B, K)), np.empty(B)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for b in range(B):
+            each[b] = [np.corrcoef(X0[:, k], F[:, b])[0, 1] for k in range(K)]
+            pred[b] = np.corrcoef(X0 @ w[b], F[:, b])[0, 1]
+    return each, pred
+
+
+def assert_correlations(got_each, got_pred, want_each, want_pred, what):
+    """within 1e-10, NaN at the same places"""
+    for got, want in ((got_each, want_each), (got_pred, want_pred)):
+        assert np.array_equal(np.isnan(got), np.isnan(want)), (what, got, want)
+        ok = ~np.isnan(want)
+        assert (np.abs(got[ok] - want[ok]) <= 1e-10).all(), (what, np.abs(got[ok] - want[ok]).max())
+
+
+def proven_drops(w, steps):
+    """a lower bound on the partial steps (a constraint leaving the active set) of one solve: the final active set has at
+    most #zeros + 1 members, and steps = adds + drops, so drops >= (steps - #zeros - 1) / 2"""
+    return (int(steps) - int((np.asarray(w) == 0).sum()) - 1) // 2
+
+
+def twin_settled(solve, A, trials=3):
+    """Which problems the statement itself determines to a tenth of the 1e-10 that cor_pred is held to: solve(A) -> the
+    statement's results for the frequency columns / genotype rows A; it is run again on A (1 + 2^-53 u), u uniform in
+    [-1, 1] — one rounding of its input, the size of the difference between two orders of summation — and a problem counts
+    as settled when no trial moves its cor_pred by more than 1e-11.  Where cond(Dmat) is about 1e8 the minimiser is
+    determined to about 1e-8 along the directions that Dmat hardly sees, and cor_pred = cor(X0 w, f) sees those directions:
+    on such a problem two correct solvers differ by more than 1e-10 (measured on the sweep: 2.4e-10 on the columns of
+    (19, 5), 3.5e-11 on (60, 10); 3e-15 wherever cond(Dmat) <= 1e6), so the statement's number is no reference there."""
+    rng = np.random.default_rng(53)
+    base = solve(A)["cor_pred"]
+    ok = np.ones(base.size, dtype=bool)
+    for _ in range(trials):
+        cp = solve(A * (1.0 + 2.0 ** -53 * rng.uniform(-1.0, 1.0, size=A.shape)))["cor_pred"]
+        both_nan = np.isnan(cp) & np.isnan(base)
+        with np.errstate(invalid="ignore"):
+            ok &= both_nan | (np.abs(cp - base) <= 1e-11)
+    return ok

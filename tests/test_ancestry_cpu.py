@@ -1,7 +1,9 @@
 """snp_ancestry_summary without a device: the CPU statement of the quadratic program (tests/native/ancestry_ref.cpp over
 bigsnpr_amd/csrc/qp_step.hpp) against the program's definition, nearPD against its properties, a planted mixture on the
-golden example.bed, and the host mirror's checks and messages.  tests/test_gpu_ancestry.py holds the kernels to that
-statement."""
+golden example.bed, the host mirror's checks and messages, and the statement on the synthetic tables of the shape sweep
+(a correction that is not all ones).  tests/test_gpu_ancestry.py and tests/test_gpu_ancestry_shapes.py hold the kernels to
+that statement."""
+import functools
 import os
 import subprocess
 import sys
@@ -216,3 +218,118 @@ def test_mirror_min_cor():
     assert out.shape == (2, K) and np.isnan(out[0]).all() and np.isfinite(out[1]).all()
     out = anc._finish_summary(False, np.array([False, True]), w.copy(), ce, np.array([0.9, 0.9]), steps, None, ms, 0.4)
     assert np.isfinite(out[0]).all() and np.isnan(out[1]).all()
+
+
+# ---- C5: the shape sweep (a correction that is not all ones, every group width of the kernel) -----------------------------------
+# Under sum_to_one = False the shrunk mixture 0.6 X0 w leaves the sum constraint inactive only where the correction does not
+# undo the shrinking: the unconstrained minimiser of such a column sums to 0.6 1'A w, A = Dmat^-1 X' diag(corr) X, and on
+# these three tables every column sum of A is above 1 / 0.6 (smallest 2.38, 3.10 and 3.77: most of the K - 1 directions
+# between the populations lie at loadings whose correction is 2 and more), so every mixture of the simplex ends at sum w = 1.
+# Each group width keeps a table with an inactive sum: (17, 20) and (19, 5) for 32 lanes, (60, 10) for 64.
+SUM_ALWAYS_ONE = [(32, 40), (33, 40), (60, 64)]
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_problem(K, L, na, s1):
+    """one sweep entry on the twin: the problems the device sweep solves (the frequency columns of the summary path for
+    na = 0, the first rows of the image with its missing cells filled for na > 0), Dmat and d by the definition in numpy"""
+    t = cases.sweep_tables(K, L, na)
+    X = t["P"].T @ t["X0"]
+    D, ok = anc.nearPD(X.T @ X)
+    assert ok
+    B = cases.sweep_counts(K)[-1]
+    if na == 0.0:
+        F = cases.frequency_columns(t, B, cases.SWEEP_SEED[(K, L)])
+        A, twin = F, lambda A: ref.ancestry_summary(A, t["X0"], t["P"], t["corr"], D, s1)   # noqa: E731
+    else:
+        Gf = cases.fill_missing(t["G"], t["X0"])[:B]
+        F = np.asfortranarray(Gf.T / 2.0)
+        A, twin = Gf, lambda A: ref.ancestry_rows(A, t["X0"], t["P"], t["corr"], D, s1)   # noqa: E731
+    return dict(t=t, D=D, F=F, d=cases.definition_d(t, F), r=twin(A), settled=cases.twin_settled(twin, A))
+
+
+@pytest.mark.parametrize("s1", [True, False])
+@pytest.mark.parametrize("na", [0.0, 0.02], ids=["summary", "rows"])
+@pytest.mark.parametrize("K,L", cases.SHAPE_SWEEP)
+def test_sweep_against_the_definition(K, L, na, s1):
+    p = sweep_problem(K, L, na, s1)
+    t, D, F, d, r = p["t"], p["D"], p["F"], p["d"], p["r"]
+    B = F.shape[1]
+    assert t["corr"].size == L and (np.diff(t["corr"]) > 0).all() and t["corr"][0] == 1.0
+    assert not np.isnan(t["X0"]).any() and np.isnan(t["G"]).any() == (na > 0)
+    assert (r["steps"] >= 0).all() and (r["steps"] <= ref.load().qp_iter_cap(K)).all()
+    worst = max(cases.check_solution(D, d[:, b], r["w"][b], s1, (K, L, na, s1, b)) for b in range(B))
+    each, pred = cases.corrcoef_reference(t["X0"], F, r["w"])
+    cases.assert_correlations(r["cor_each"], r["cor_pred"], each, pred, (K, L, na, s1))
+    ok = ~np.isnan(pred)
+    err = max(np.abs(r["cor_each"] - each).max(), np.abs(r["cor_pred"][ok] - pred[ok]).max() if ok.any() else 0.0)
+    ones = ref.ancestry_summary(F, t["X0"], t["P"], np.ones(L), D, s1)["w"]
+    print("K %d L %d na %g sum_to_one %d: worst KKT residual / tol_kkt = %.3g, worst correlation error %.3g, the correction moves w by "
+          "%.3g" % (K, L, na, s1, worst, err, np.abs(r["w"] - ones).max()))
+    if K == 1 and not s1:
+        # sum w <= 1 alone: w = 0 wherever d <= 0, and the prediction has no variance there
+        zero = r["w"][:, 0] == 0
+        assert np.array_equal(zero, d[0] <= 0) and np.array_equal(np.isnan(r["cor_pred"]), zero)
+    else:
+        assert ok.all()
+
+
+def test_sweep_conditioning():
+    cond = {kl: np.linalg.cond(sweep_problem(*kl, 0.0, True)["D"]) for kl in cases.SHAPE_SWEEP}
+    print({kl: "%.3g" % c for kl, c in cond.items()})
+    for W in (8, 16, 32, 64):
+        assert any(c <= 1e4 for (K, L), c in cond.items() if cases.group_width(K) == W), W     # w itself is compared there
+    for kl in cases.RANK_DEFICIENT:
+        assert cond[kl] > 1e7, (kl, cond[kl])
+
+
+def test_sweep_sum_constraint_both_ways():
+    inactive_at = set()
+    for K, L in cases.SHAPE_SWEEP:
+        sums = sweep_problem(K, L, 0.0, False)["r"]["w"].sum(axis=1)
+        assert (np.abs(sums - 1.0) <= 1e-12).any(), (K, L, sums)
+        if (K, L) in SUM_ALWAYS_ONE:
+            assert (np.abs(sums - 1.0) <= 1e-12).all(), (K, L, sums)
+        else:
+            assert (sums < 1.0 - 1e-6).any(), (K, L, sums)
+            inactive_at.add(cases.group_width(K))
+    assert inactive_at == {8, 16, 32, 64}
+
+
+def test_sweep_partial_steps_at_every_width():
+    # a constraint leaves the active set (the row rotations of R and J) in some problem of the device sweep, at every width
+    for W in (8, 16, 32, 64):
+        drops = [cases.proven_drops(p["r"]["w"][b], p["r"]["steps"][b])
+                 for K, L in cases.SHAPE_SWEEP if cases.group_width(K) == W for na in (0.0, 0.02) for s1 in (True, False)
+                 for p in [sweep_problem(K, L, na, s1)] for b in range(p["F"].shape[1])]
+        print("%d lanes: most partial steps proven in one problem: %d" % (W, max(drops)))
+        assert max(drops) >= 1, W
+
+
+def test_sweep_generators():
+    K, L = 17, 20
+    t = cases.sweep_tables(K, L, 0.02)
+    n, m = cases.sweep_dims(K, L)
+    assert t["G"].shape == (n, m) and t["X0"].shape == (m, K) and t["P"].shape == (m, L) and m % 4 and m % 64
+    assert t["X0"].min() >= 0.02 and t["X0"].max() <= 0.98 and 0.005 < np.isnan(t["G"]).mean() < 0.04
+    assert abs(t["corr"][-1] - (1.0 + 0.013 * 19 ** 1.5)) < 1e-15
+    F9, F4 = cases.frequency_columns(t, 9, 5), cases.frequency_columns(t, 4, 5)
+    assert np.array_equal(F9[:, :4], F4) and not np.isnan(F9).any()          # a column depends on (seed, b) alone
+    lo, hi = t["X0"].min(axis=1), t["X0"].max(axis=1)
+    assert (F9[:, 0] >= lo - 1e-15).all() and (F9[:, 0] <= hi + 1e-15).all()                 # a mixture of the columns of X0
+    assert (F9[:, 1] >= 0.6 * lo - 1e-15).all() and (F9[:, 1] <= 0.6 * hi + 1e-15).all()     # shrunk by 0.6
+    assert (np.isin(F9[:, 2], [0.0, 0.5, 1.0]) | (F9[:, 2] == t["X0"].mean(axis=1))).all()   # a genotype row / 2
+    assert cases.proven_drops(np.array([0.0, 0.5, 0.5]), 6) == 2 and cases.proven_drops(np.array([0.0, 0.0, 1.0]), 3) == 0
+    with pytest.raises(AssertionError):
+        cases.synthetic_tables(L + 5, 50, 3, L, 1)
+
+
+def test_sweep_where_the_statement_is_a_reference_for_cor_pred():
+    # the device's cor_pred is held to the statement's on the settled problems: all of them, but for some of the tables with L < K
+    for K, L in cases.SHAPE_SWEEP:
+        for na in (0.0, 0.02):
+            for s1 in (True, False):
+                p = sweep_problem(K, L, na, s1)
+                left = int((~p["settled"]).sum())
+                print("K %d L %d na %g sum_to_one %d: %d of %d problems not settled" % (K, L, na, s1, left, p["settled"].size))
+                assert left == 0 or (K, L) in cases.RANK_DEFICIENT, (K, L, na, s1, p["settled"])

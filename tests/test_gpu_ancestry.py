@@ -27,16 +27,7 @@ def ba():
     return bigsnpr_amd
 
 
-def per_workgroup(K):
-    return 64 // (8 if K <= 8 else 16 if K <= 16 else 32 if K <= 32 else 64)
-
-
-def same_minimiser(D, d, got, want, s1, what):
-    """one device solution against the statement's on the same D and d: objectives, w where D is well conditioned, and the
-    C1 checks on the device's w"""
-    f, fr = cases.objective(D, d, got), cases.objective(D, d, want)
-    assert abs(f - fr) <= 1e-12 * (1.0 + abs(fr)), (what, f, fr)
-    cases.check_solution(D, d, got, s1, what)
+per_workgroup, same_minimiser = cases.per_workgroup, cases.same_minimiser
 
 
 # ---- G1 ----------------------------------------------------------------------------------------------------------------
