@@ -29,6 +29,8 @@ from .ibd import bed_ibd, bed_ibdQC, ibd_last_ms, indep_pairwise, prune_walk  # 
 from .outliers import LOF, knn_last_stats, knn_parallel, lof_matrix, prob_dist, rob_maha  # noqa: F401,E402
 from .ancestry import (AncestryProportions, ancestry_last_ms, ancestry_moments, bed_ancestry, nearPD, qp_simplex,  # noqa: F401,E402
                        snp_ancestry_summary)
+from .scores import (AUC, AUCBoot, BootAUC, auc_boot_draws, auc_last_ms, big_prodMat, boot_statistics, pcor,  # noqa: F401,E402
+                     snp_grid_AUC)
 from .qc import bed_hwe, bed_plinkQC, bed_plinkRmSamples, hwe_exact_counts, qc_classes, qc_last_ms  # noqa: F401,E402
 from .sct import seq_log, snp_grid_clumping, snp_grid_PRS, snp_grid_stacking  # noqa: F401,E402
 from .plr import BigSpReg, big_spLinReg, big_spLogReg  # noqa: F401,E402

@@ -124,6 +124,12 @@ SIGNATURES = {
     "bsn_bed_ancestry": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, i64, f64p, f64p, C.c_int32, f64p, f64p, f64p,
                                    i32p]),
     "bsn_ancestry_last_ms": (C.c_int, [f64p]),
+    "bsn_bed_prodmat": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, f64p, i64, f64p, vp]),
+    "bsn_auc": (C.c_int, [vp, C.c_int32, C.c_int32, i64, i64, i64, i64, i64p, i64, u8p, f64p]),
+    "bsn_auc_boot": (C.c_int, [vp, C.c_int32, C.c_int32, i64, i64, i64, u8p, i64, C.c_uint64, f64p]),
+    "bsn_auc_boot_draws": (C.c_int, [i64, i64, C.c_uint64, i32p]),
+    "bsn_pcor_moments": (C.c_int, [vp, C.c_int32, C.c_int32, i64, i64, i64, f64p, i64, f64p, f64p, f64p]),
+    "bsn_auc_last_ms": (C.c_int, [f64p]),
     "bsn_mult_lin_reg":(C.c_int, [vp, i64p, i64, i64p, i64, f64p, i64, f64p]),
     "bsn_univ_linreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, f64p, f64p]),
     "bsn_univ_logreg": (C.c_int, [vp, i64p, i64, i64p, i64, f64p, f64p, i64, C.c_double, C.c_int32, f64p, f64p, i32p]),

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbigsnpr_hip.so")
 SOURCES = ["image.hip", "matvec.hip", "svd.hip", "svd_panel.hip", "ld.hip", "runtime.hip", "handle.hip", "api.hip", "comm.hip", "tcross.hip", "robust.hip",
-           "sparse_ld.hip", "gwas.hip", "impute.hip", "fastimpute.hip", "ldsplit.hip", "plr.hip", "popstat.hip", "project.hip", "bgen.hip", "king.hip", "qc.hip", "ibd.hip", "knn.hip", "ancestry.hip"]
+           "sparse_ld.hip", "gwas.hip", "impute.hip", "fastimpute.hip", "ldsplit.hip", "plr.hip", "popstat.hip", "project.hip", "bgen.hip", "king.hip", "qc.hip", "ibd.hip", "knn.hip", "ancestry.hip", "auc.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC]

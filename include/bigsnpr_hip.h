@@ -929,6 +929,37 @@ int bsn_sfbm_ldsplit(const bsn_sfbm *s, double thr_r2, double max_r2, int32_t mi
                      double *cost2_out, double *perc_kept_out, int32_t *n_block_ok_out, int32_t *all_last_out,
                      int32_t *levels_run_out, double *seconds_out);
 
+/* ---- scoring a grid of models: big_prodMat, AUC, AUCBoot, pcor (bigsnpr_amd/csrc/auc.hip, the rule in auc_step.hpp) ---------
+ * Score matrices are column-major, fp64 (is_f32 = 0) or fp32 (is_f32 != 0), in host memory (on_device = 0) or in device memory
+ * of the caller (bsn_malloc, or the d_XV of bsn_bed_prodmat); `ld` is the leading dimension in elements.  Null stream,
+ * synchronised before returning.  BSN_AUC_BATCH=<n> allows at most n columns per sort batch and n replicates per bootstrap
+ * launch; every n gives the same bits. */
+/* bigstatsr::big_prodMat on a genotype image: XV (n x K) = A~[ind_row, ind_col] A, through the product pass of
+ * bsn_bed_prod_and_rowsumssq.  center / scale: both NULL or both m values.  XV (host) and d_XV (device, n x K, leading dimension
+ * n) may each be NULL, not both.  A column of A that holds a NaN comes back as a column of NaN. */
+int bsn_bed_prodmat(bsn_bed *bed, const int64_t *ind_row, int64_t n, const int64_t *ind_col, int64_t m, const double *center,
+                    const double *scale, const double *A, int64_t K, double *XV, double *d_XV);
+/* AUC of K score columns against one 0 / 1 target (n values, one per selected row): twoU = 2 #{case > control} + #{case = control}
+ * in exact integers, auc_out[j] = twoU / (2 n1 n0).  `pred` has n_src rows and K * n_sum columns; result column j is the fp64 sum,
+ * ascending, of the columns j, j + K, ..., j + (n_sum - 1) K (n_sum = 1: the column itself; n_sum = chromosomes: snp_grid_AUC).
+ * ind_row: NULL (n = n_src) or n row indices.  Refused by name: a NaN (the message names the first such column), a target value
+ * other than 0 / 1, one class only, 2^31 rows or more, no room for one column's workspace. */
+int bsn_auc(const void *pred, int32_t is_f32, int32_t on_device, int64_t ld, int64_t n_src, int64_t K, int64_t n_sum,
+            const int64_t *ind_row, int64_t n, const uint8_t *target, double *auc_out);
+/* nboot bootstrap replicates of the AUC of each of K columns (replicates_out: nboot x K, column-major).  Replicate b draws n rows
+ * by the rule of auc_step.hpp from (b, seed) alone: every column sees the same resamples.  A replicate without a case or without
+ * a control is NaN. */
+int bsn_auc_boot(const void *pred, int32_t is_f32, int32_t on_device, int64_t ld, int64_t n, int64_t K, const uint8_t *target,
+                 int64_t nboot, uint64_t seed, double *replicates_out);
+/* FOR TESTS: the n rows that replicate b draws, generated on the device */
+int bsn_auc_boot_draws(int64_t n, int64_t b, uint64_t seed, int32_t *rows_out);
+/* pcor's device part: for every column x of the score matrix, with Q (n x p, p <= 31, host, orthonormal columns) and r_y (n, host),
+ * e = x - Q Q'x, ee_out = e'e, ery_out = e'r_y.  Two passes over fixed row slabs, no atomics: the same bits in every run. */
+int bsn_pcor_moments(const void *x, int32_t is_f32, int32_t on_device, int64_t ld, int64_t n, int64_t K, const double *Q, int64_t p,
+                     const double *ry, double *ee_out, double *ery_out);
+/* device milliseconds of the last call above in this process: key pass, sort, group + evaluation kernels, bootstrap kernel, pcor */
+int bsn_auc_last_ms(double *ms_out);
+
 /* ---- the panel kernels of bsn_bed_randomsvd one at a time: FOR TESTS, not part of the drop-in surface ----------------------
  * The tall-skinny fp64 algebra between the streaming passes of a solve (bigsnpr_amd/csrc/svd.hip), through the launch
  * functions the solve itself uses, on DEVICE matrices of the caller (column-major; bsn_malloc / bsn_memcpy_h2d /
